@@ -52,7 +52,12 @@ def main():
                     "rocprofv3 --pmc, N = 1 only); 0: take it from the committed PMC pass; default: 1 for a full run, 0 when --cpu-seconds 0 trims it")
     ap.add_argument("--proof", type=int, default=1, help="0: skip the untimed proof-of-work sample (tools/profile.sh does, so that the "
                     "kernel-trace average covers full-size launches only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                    "(rank 0) as DIR/<name>.npy in float32: hard bits, iterations and converged flags of a fixed, seeded sample of the "
+                    "frames (all of them when they fit; bits_frames.npy: their indices), at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.live_traffic < 0:
         args.live_traffic = 1 if args.cpu_seconds > 0 else 0
 
@@ -145,6 +150,8 @@ def main():
     t1 = time.perf_counter()
     launches, kernel_ms = dec.kernel_time()
     dec.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, bits, iters_t, conv_t)   # before anything below decodes into the same buffers
     # error statistics of the last step (outside the timed region)
     last = (args.warmup + args.steps - 1) % nbuf
     wrong = (bits[:, :k] != msg[last]).sum(dim=1)
@@ -219,6 +226,31 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT = 64_000_000     # bytes, all files of --dump-outputs together
+
+
+def dump_outputs(out_dir, torch, bits, iters_t, conv_t):
+    """--dump-outputs: what the last timed step handed its caller -- hard bits [B][N], iterations [B], converged flags [B] -- for the
+    same fixed sample of frames (every frame when they fit), as float32 .npy files; bits_frames.npy (float64) names the frames.
+    The sample depends on B and N only, so two builds run with the same arguments write arrays that compare element for element."""
+    import numpy as np
+    B, N = bits.shape
+    n = min(B, (DUMP_LIMIT - 4096) // (4 * N + 4 + 4 + 8))       # (4096: the four .npy headers)
+    frames = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    idx = torch.from_numpy(frames).to(bits.device)
+    arrays = {"bits": bits.index_select(0, idx), "iters": iters_t.index_select(0, idx), "converged": conv_t.index_select(0, idx)}
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, t.float().cpu().numpy())
+        total += os.path.getsize(path)
+    path = os.path.join(out_dir, "bits_frames.npy")
+    np.save(path, frames.astype(np.float64))
+    total += os.path.getsize(path)
+    assert total <= DUMP_LIMIT, total
 
 
 def layered_leg(args, E, torch, dev, sp, B, f16pk, ebn0):

@@ -158,3 +158,28 @@ def test_rccl_collectives_run_with_one_rank():
              env={"LDPC_BENCH_FORCE_DIST": "1"}, only_line=False)
     assert d["n_gpus"] == 1 and "rehearsal" not in d and d["proof_of_work"]["ok"]
     assert abs(d["value"] - 2 * 2048 * 4096 / (d["ms_per_step"] * 2e-3) / 1e6) / d["value"] < 0.02
+
+
+def test_dump_outputs_are_the_last_timed_step_and_repeat_exactly(tmp_path):
+    """--dump-outputs DIR: the last timed step's hard bits, iterations and converged flags as float32 .npy files (2 048 frames fit
+    in the 64 MB bound whole), identical in a second run with the same arguments; --steps sets the timed launches.  4 dB: most
+    frames converge, after differing numbers of turns."""
+    import numpy as np
+    from tests.helpers import load
+    args = ["--steps", "3", "--warmup", "1", "--batch", "2048", "--ebn0", "4", "--cpu-seconds", "0", "--fp16-leg", "0", "--proof", "0", "--live-traffic", "0"]
+    runs = []
+    for name in ("a", "b"):
+        d = _run([sys.executable, "bench.py", "--dump-outputs", str(tmp_path / name)] + args)
+        assert d["steps"] == 3 and d["roofline"]["launches"] == 3 and d["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["bits.npy", "bits_frames.npy", "converged.npy", "iters.npy"]
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64_000_000
+        runs.append((d, {f[:-4]: np.load(tmp_path / name / f) for f in files}))
+    (d, a), (_, b) = runs
+    for k in a:
+        assert a[k].dtype == (np.float64 if k == "bits_frames" else np.float32) and np.array_equal(a[k], b[k]), k
+    H = load("jpl.4096.4.5").H.astype(np.float32)
+    assert a["bits"].shape == (2048, H.shape[1]) and np.array_equal(a["bits_frames"], np.arange(2048))
+    assert abs(a["iters"].astype(np.float64).mean() - d["mean_iters"]) < 1e-9
+    ok = a["converged"] == 1
+    assert ok.sum() > 1024 and not ((a["bits"][ok] @ H.T) % 2).any()     # a converged frame is a codeword

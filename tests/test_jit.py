@@ -58,14 +58,27 @@ def test_hiprtc_compiles_without_a_gpu_and_caches(name):
 
 
 def test_both_compiler_routes_build_the_same_kernel(tmp_path, monkeypatch):
-    """hipcc --genco (a child process; default when the tool chain is installed) and hiprtc (in-process)"""
+    """hipcc --genco (a child process; default when the tool chain is installed) and hiprtc (in-process).  HIPCC names a
+    wrapper that logs each call and runs the tool chain: the hipcc route must go through it, hiprtc must not; a compile
+    time of 0 would be a cache hit (how long a compile takes depends on the host, so no bound is put on it)"""
+    real = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    calls = tmp_path / "calls.txt"
+    wrapper = tmp_path / "hipcc"
+    wrapper.write_text(f'#!/bin/sh\necho "$@" >> "{calls}"\n"{real}" "$@"\n')
+    wrapper.chmod(0o755)
+    monkeypatch.setenv("HIPCC", str(wrapper))
     code = synthetic("small-2x4-sz32").hip_code(E)
     names = {}
     for route in ("hiprtc", "hipcc"):
         monkeypatch.setenv("LDPC_JIT_COMPILER", route)
         monkeypatch.setenv("LDPC_JIT_NOCACHE", "1")
         names[route], cached, sec = code.jit_prepare("min")
-        assert not cached and sec > 0.5
+        assert not cached and sec > 0
+        log = calls.read_text().splitlines() if calls.exists() else []
+        if route == "hiprtc":
+            assert log == []
+        else:
+            assert len(log) == 1 and log[0].startswith("--genco ") and log[0].endswith("/out.hsaco")
     assert names["hiprtc"] == names["hipcc"]
 
 
