@@ -5,7 +5,8 @@
 // trips and barriers (profiles/r01_fused_v2_f32_minsum_pmc.json).  Here a frame (sz = 128) is owned by
 // FOUR waves: pair 0 (threads 0..127) holds the even block rows, pair 1 (threads 128..255) the odd ones,
 // thread (pair, r) = row r of every circulant of its pair's block rows.  78 messages + <= 24 channel-LLR
-// registers per thread -> 128 VGPRs -> 4 waves per SIMD, 16 waves per CU (4 frames, as before).
+// registers per thread -> 128 VGPRs -> 4 waves per SIMD, 16 waves per CU (4 frames, as before); for min-sum half of the
+// channel-LLR copies sit in LDS instead (SPLIT_ORIG_LDS), which keeps the 128 free of spills.
 // For sz < 64 a workgroup holds 64/sz frames interleaved lane by lane (sz = 32: wave 0 = pair 0 and wave 1 =
 // pair 1 of two frames); loop control then runs on a workgroup-uniform "done" mask, see split_body.
 // No cross-lane combine is needed (a check row is still handled by one thread) and the graph stays a
@@ -18,6 +19,13 @@
 // consecutive contributions of a column alternate between the pairs, which balances the rounds.
 #include <stdio.h>
 
+// f32 min-sum, sz = 128: 12 of the 24 round-0 LLR copies per thread live in LDS (12 KB per workgroup, 34.8 KB in all: four
+// workgroups still fit a CU's 160 KB) -- 127 VGPRs and no scratch at 4 waves/SIMD instead of 71 spilled registers.  Measured on
+// jpl.4096, 65 536 frames, 2 dB / 3 dB (profiles/r05_split_ab.txt): 0 copies 18.55 / 8.68 ms, 8: 18.29 / 8.36 (26 spilled),
+// 12: 18.20 / 8.26, 16: 18.42 / 8.36.
+#ifndef SPLIT_ORIG_LDS
+#define SPLIT_ORIG_LDS 12
+#endif
 #include "fused_split_body.h"
 
 #ifndef SPLIT_WAVES_PER_EU

@@ -8,6 +8,12 @@
 #ifndef SPLIT_ORIG_REGS
 #define SPLIT_ORIG_REGS 1
 #endif
+// round-0 channel-LLR copies of the f32 min-sum instances with sz >= 64 that live in a lane-private LDS area instead of VGPRs
+// (the first SPLIT_ORIG_LDS slots; the rest stay in registers).  fused_split.hip sets it for its ahead-of-time instances;
+// run-time compiled instances keep every copy in registers.
+#ifndef SPLIT_ORIG_LDS
+#define SPLIT_ORIG_LDS 0
+#endif
 // wave priority while in phase A (check rows: long stretches of independent VALU work) and in phase B (column
 // rounds: short, LDS-bound, barrier-separated).  Measured on jpl.4096, 65 536 frames: A=0/B=0 20.72 ms,
 // A=0/B=2 20.90, A=2/B=0 20.24 (A = 1, 2 or 3 alike).  The priority is raised after the first phase B only:
@@ -106,9 +112,24 @@ struct Split {
     }
 };
 
-template <typename CT, int SZ, class Plan, class T, int P, int Q, int I0, int I1>
+// LDS of a workgroup: lam (block column after block column), one syndrome word per wave, then NOL slots of round-0 LLR copies,
+// slot-major and one word per thread (lane-private: written and read by the same thread only, conflict-free, no barrier)
+template <typename CT, int VARIANT, class Plan, int SZ, class T>
+struct SplitLds {
+    static constexpr int V = QcGeom<SZ>::V, VT = QcGeom<SZ>::VT, THREADS = Plan::NP * VT, NW = THREADS / 64, ES = sizeof(CT);
+    static constexpr int LAM_BYTES = (Plan::NBC * V * ES + 15) / 16 * 16;
+    static constexpr int ORIG_OFF = LAM_BYTES + (4 * NW + 15) / 16 * 16;
+    static constexpr int NOL_WANT = (VARIANT == LDPC_V_MINSUM && ES == 4 && SZ >= 64 && SPLIT_ORIG_REGS) ? SPLIT_ORIG_LDS : 0;
+    static constexpr int NOL = NOL_WANT < Split<Plan, T>::NORIG ? NOL_WANT : Split<Plan, T>::NORIG;
+    static constexpr int BYTES = NOL ? ORIG_OFF + NOL * THREADS * ES : LAM_BYTES + 4 * NW;
+    // byte offset of slot os of the thread in group P at lane offset p4 (= its lane index * ES): an immediate + p4
+    static constexpr uint32_t orig_at(int P, int os) { return ORIG_OFF + (uint32_t)(os * THREADS + P * VT) * ES; }
+};
+
+template <typename CT, int VARIANT, int SZ, class Plan, class T, int P, int Q, int I0, int I1>
 __device__ __forceinline__ void split_round_chunk(char *lds, uint32_t p4, uint32_t vmask, const CT *msg, const CT *orig_rot, const float *gllr, uint32_t r0) {
     using S = Split<Plan, T>;
+    using L = SplitLds<CT, VARIANT, Plan, SZ, T>;
     constexpr uint32_t ES = sizeof(CT), CPW = QcGeom<SZ>::CPW, V = QcGeom<SZ>::V;
     asm volatile("" : "+v"(p4));
     if constexpr (Q == 0) {
@@ -118,7 +139,8 @@ __device__ __forceinline__ void split_round_chunk(char *lds, uint32_t p4, uint32
             constexpr int e = S::nth(Q, P, decltype(ic)::value);
             constexpr int ms = S::slot(e), os = S::oslot(T::bc[e]);
             CT o;
-            if constexpr (SPLIT_ORIG_REGS) o = orig_rot[os]; else o = (CT)gllr[T::bc[e] * SZ + ((r0 + T::rot[e]) % SZ)];
+            if constexpr (SPLIT_ORIG_REGS && os < L::NOL) o = lds_ld<CT>(lds + L::orig_at(P, os), p4);
+            else if constexpr (SPLIT_ORIG_REGS) o = orig_rot[os]; else o = (CT)gllr[T::bc[e] * SZ + ((r0 + T::rot[e]) % SZ)];
             lds_st<CT>(lds + T::bc[e] * V * ES, qc_wrap(p4 + T::rot[e] * CPW * ES, vmask), msg[ms] + o);
         });
         return;
@@ -139,12 +161,12 @@ __device__ __forceinline__ void split_round_chunk(char *lds, uint32_t p4, uint32
     });
     asm volatile("" ::: "memory");
 }
-template <typename CT, int SZ, class Plan, class T, int P, int Q, int I0>
+template <typename CT, int VARIANT, int SZ, class Plan, class T, int P, int Q, int I0>
 __device__ __forceinline__ void split_round(char *lds, uint32_t p4, uint32_t vmask, const CT *msg, const CT *orig_rot, const float *gllr, uint32_t r0) {
     constexpr int CNT = Split<Plan, T>::count(Q, P), CH = SZ < 64 ? SPLIT_CH_SMALL : SPLIT_CH;
     if constexpr (I0 < CNT) {
-        split_round_chunk<CT, SZ, Plan, T, P, Q, I0, (I0 + CH < CNT ? I0 + CH : CNT)>(lds, p4, vmask, msg, orig_rot, gllr, r0);
-        split_round<CT, SZ, Plan, T, P, Q, I0 + CH>(lds, p4, vmask, msg, orig_rot, gllr, r0);
+        split_round_chunk<CT, VARIANT, SZ, Plan, T, P, Q, I0, (I0 + CH < CNT ? I0 + CH : CNT)>(lds, p4, vmask, msg, orig_rot, gllr, r0);
+        split_round<CT, VARIANT, SZ, Plan, T, P, Q, I0 + CH>(lds, p4, vmask, msg, orig_rot, gllr, r0);
     }
 }
 
@@ -188,6 +210,11 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
     for (int i = 0; i < S::NMSG; i++) msg[i] = CT(0);  // Orig.hs:64-65
 #pragma unroll
     for (int i = 0; i < (SPLIT_ORIG_REGS ? S::NORIG : 1); i++) orig[i] = CT(0);
+    using L = SplitLds<CT, VARIANT, Plan, SZ, T>;
+    static_assert(L::NOL == 0 || L::BYTES <= 65536, "LDS of one workgroup");
+    auto put_orig = [&](int os, CT v) {   // (os is a constant after inlining)
+        if (os < L::NOL) lds_st<CT>(lds + L::orig_at(P, os), p4, v); else orig[os] = v;
+    };
     // ---- lam <- LLRs (or the given lam): pair P fills the block columns bc with bc % 2 == P.  One dispatch on the
     // LLR element type around ALL of the thread's loads (46 of them): they issue back to back.
     // Every channel LLR is read from global memory ONCE (the input may be page-locked HOST memory read over PCIe,
@@ -211,7 +238,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
                 if constexpr (SPLIT_ORIG_REGS && S::oowner(bc) == P) {
                     constexpr int e0 = Rounds<T>::round0_edge(bc);
                     constexpr int os = S::oslot(bc);
-                    orig[os] = maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, fN + bc * SZ + ((r0 + T::rot[e0]) % SZ)), A.llr_round16);
+                    put_orig(os, maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, fN + bc * SZ + ((r0 + T::rot[e0]) % SZ)), A.llr_round16));
                 }
             });
         }
@@ -236,7 +263,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
             if constexpr (SPLIT_ORIG_REGS && S::oowner(bc) == P) {
                 constexpr int e0 = Rounds<T>::round0_edge(bc);
                 constexpr int os = S::oslot(bc);
-                orig[os] = lds_ld<CT>(lds + bc * V * ES, qc_wrap(p4 + T::rot[e0] * CPW * ES, vmask));
+                put_orig(os, lds_ld<CT>(lds + bc * V * ES, qc_wrap(p4 + T::rot[e0] * CPW * ES, vmask)));
             }
         });
     }
@@ -355,7 +382,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
         if (done != FULL) {
             __builtin_amdgcn_s_setprio(SPLIT_PRIO_B);
             static_for<0, Rounds<T>::num_rounds()>([&](auto qc) {
-                split_round<CT, SZ, Plan, T, P, decltype(qc)::value, 0>(lds, p4, vmask, msg, orig, reinterpret_cast<const float *>(A.llr) + fN, r0);
+                split_round<CT, VARIANT, SZ, Plan, T, P, decltype(qc)::value, 0>(lds, p4, vmask, msg, orig, reinterpret_cast<const float *>(A.llr) + fN, r0);
                 __syncthreads();  // the next round adds into the same columns
             });
             __builtin_amdgcn_s_setprio(SPLIT_PRIO_A);
@@ -424,7 +451,7 @@ template <typename CT, int VARIANT, class Plan, int SZ, class T>
 __device__ __forceinline__ void split_kernel_body(const FusedArgs &A) {
     using G = SplitGeom<Plan, SZ>;
     static_assert(SZ >= 2, "circulant size");
-    __shared__ __attribute__((aligned(16))) char lds[(Plan::NBC * G::V * (int)sizeof(CT) + 15) / 16 * 16 + 4 * G::NW];
+    __shared__ __attribute__((aligned(16))) char lds[SplitLds<CT, VARIANT, Plan, SZ, T>::BYTES];
     const uint32_t tid = threadIdx.x;
     const uint32_t pair = __builtin_amdgcn_readfirstlane(tid / G::VT);  // wave-uniform (VT is a multiple of 64)
     static_for<0, Plan::NP>([&](auto pc) {
