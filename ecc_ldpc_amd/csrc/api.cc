@@ -9,10 +9,8 @@
 #include <mutex>
 #include <new>
 
-#include "internal.h"
-#include "fused.h"
+#include "backend.h"
 #include "jit.h"
-#include "layered_qc.h"
 #include "sim.h"
 
 namespace ldpc {
@@ -48,11 +46,9 @@ using ldpc::set_error;
 
 struct ldpc_ctx {
     const ldpc_code *code = nullptr;
-    int variant = 0, dtype = 0, max_batch = 0, Bp = 0, path = LDPC_PATH_FLOOD, device = 0, schedule = LDPC_SCHED_FLOODING;
+    int max_batch = 0, device = 0, schedule = LDPC_SCHED_FLOODING;
     hipStream_t stream = nullptr;
-    ldpc::FloodState flood;
-    ldpc::FusedState *fused = nullptr;
-    ldpc::LayeredQcState *lqc = nullptr;   // layered schedule on a QC code: frame-per-workgroup kernel, state in HBM (layered_qc.hip)
+    ldpc::Backend *backend = nullptr;   // the context's decoder (select.cc make_backend)
     // staging of the host-pointer entry points, allocated on first use.  kSlots slots, each with its own stream
     // running H2D -> decode -> D2H for one chunk, so that the copies of one chunk overlap the decode of another
     // (fused paths are stateless on the device; the flood path keeps per-context BP state and uses slot 0 with
@@ -378,11 +374,6 @@ void ldpc_ctx_destroy(ldpc_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
-    ldpc::flood_graph_release(ctx->flood);
-    hipFree(ctx->flood.msg); hipFree(ctx->flood.scratch); hipFree(ctx->flood.lam); hipFree(ctx->flood.orig);
-    hipFree(ctx->flood.dev.unsat); hipFree(ctx->flood.dev.iters); hipFree(ctx->flood.dev.conv); hipFree(ctx->flood.dev.done);
-    (void)hipFree(ctx->flood.dev.big); (void)hipFree(ctx->flood.dev.kexp);
-    (void)hipFree(ctx->flood.d_layer_ptr);
     for (int i = 1; i < ldpc_ctx::kSlots; i++) if (ctx->pstream[i]) hipStreamSynchronize(ctx->pstream[i]);
     for (int i = 0; i < ldpc_ctx::kSlots; i++) { hipFree(ctx->d_in[i]); hipFree(ctx->d_bits[i]); hipFree(ctx->d_iters[i]); hipFree(ctx->d_conv[i]); hipFree(ctx->d_final[i]); }
     for (int i = 1; i < ldpc_ctx::kSlots; i++) if (ctx->pstream[i]) hipStreamDestroy(ctx->pstream[i]);
@@ -390,8 +381,7 @@ void ldpc_ctx_destroy(ldpc_ctx *ctx) {
     if (ctx->h_small_out) (void)hipHostFree(ctx->h_small_out);
     (void)hipFree(ctx->d_small_out); (void)hipFree(ctx->d_small_in);
     (void)hipFree(ctx->d_zc_iters); (void)hipFree(ctx->d_zc_conv); (void)hipFree(ctx->d_unpacked); (void)hipFree(ctx->d_packed);
-    if (ctx->fused) ldpc::fused_destroy(ctx->fused);
-    ldpc::layered_qc_destroy(ctx->lqc);
+    delete ctx->backend;
     ctx->timer.destroy();
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -454,113 +444,20 @@ ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cf
     ldpc_code_dev tabs;
     if (code_upload(code, device, &tabs) != LDPC_OK) return nullptr;
 
-    if (dtype == LDPC_F16PK && (variant != LDPC_MINSUM || path == LDPC_PATH_FLOOD)) {
-        set_error(LDPC_EUNSUPPORTED, "LDPC_F16PK (packed fp16 arithmetic, two frames per lane) exists for min-sum on the on-chip path");
-        return nullptr;
-    }
-    const bool layered_fused_ok = schedule == LDPC_SCHED_LAYERED && sum_order == LDPC_SUM_REFERENCE && ldpc::fused_layered_why_not(*code, variant, dtype) == nullptr;
-    if (schedule == LDPC_SCHED_LAYERED) {
-        if (dtype == LDPC_F16 && (!layered_fused_ok || path == LDPC_PATH_FLOOD)) {
-            // from HBM: lam stored in fp16 for the frame-per-workgroup min-sum record kernel of QC codes (r03); nothing else
-            const char *why = sum_order == LDPC_SUM_REFERENCE ? ldpc::layered_qc_why_not(*code, variant, dtype, 0) : "parity modes are f64";
-            if (why) { set_error(LDPC_EUNSUPPORTED, "the layered schedule from HBM with fp16 storage: %s", why); return nullptr; }
-        }
-        if (code->max_row_deg > 32) { set_error(LDPC_EUNSUPPORTED, "layered schedule: check rows above weight 32 (this code has %d)", code->max_row_deg); return nullptr; }
-    }
-    const bool fused_ok = layered_fused_ok ||
-                          (schedule == LDPC_SCHED_FLOODING && variant != LDPC_TANH_CM && variant != LDPC_TANH_CUDA32 && sum_order == LDPC_SUM_REFERENCE && ldpc::fused_supported(*code, variant, dtype));
-    if ((path == LDPC_PATH_FUSED || dtype == LDPC_F16PK) && !fused_ok) {
-        if (schedule == LDPC_SCHED_LAYERED) { set_error(LDPC_EUNSUPPORTED, "no on-chip kernel for the layered schedule on this code / rule / type (%s); LDPC_PATH_FLOOD keeps the state in HBM", ldpc::fused_layered_why_not(*code, variant, dtype)); return nullptr; }
-        set_error(LDPC_EUNSUPPORTED, "no fused kernel for this code/variant/dtype (%s)", ldpc::fused_why_not(*code, variant, dtype));
-        return nullptr;
-    }
+    ldpc::Backend *backend = ldpc::make_backend(*code, tabs, variant, dtype, schedule, sum_order, path, max_batch);
+    if (!backend) return nullptr;
     ldpc_ctx *ctx = new (std::nothrow) ldpc_ctx();
-    if (!ctx) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
-    ctx->code = code; ctx->variant = variant; ctx->dtype = dtype; ctx->max_batch = max_batch; ctx->device = device; ctx->schedule = schedule;
-    ctx->Bp = (max_batch + 63) / 64 * 64;
-    ctx->path = (path == LDPC_PATH_AUTO) ? ((fused_ok && (layered_fused_ok || ldpc::fused_preferred(*code, variant, dtype))) ? LDPC_PATH_FUSED : LDPC_PATH_FLOOD) : path;
-
-#define CTX_HIP(x)                                                       \
-    do {                                                                 \
-        hipError_t e_ = (x);                                             \
-        if (e_ != hipSuccess) {                                          \
-            set_error(e_ == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "%s: %s", #x, hipGetErrorString(e_)); \
-            ldpc_ctx_destroy(ctx);                                       \
-            return nullptr;                                              \
-        }                                                                \
-    } while (0)
-
-    CTX_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    const size_t es = ldpc::flood_elem_size(dtype);
-    const size_t Bp = (size_t)ctx->Bp;
-    ldpc::FloodDev &d = ctx->flood.dev;
-    d.M = code->M; d.N = code->N; d.E = code->E; d.Bp = ctx->Bp;
-    d.row_ptr = tabs.row_ptr; d.col_idx = tabs.col_idx; d.col_ptr = tabs.col_ptr; d.csc_edge = tabs.csc_edge;
-    d.unsat = nullptr; d.iters = nullptr; d.conv = nullptr; d.done = nullptr;
-    d.wide_rows = 0;
-    d.cm_order = variant == LDPC_TANH_CM ? LDPC_SUM_ARRAYLET : (variant == LDPC_TANH_CUDA32 ? 3 : sum_order);   // (3: ((orig + ne_1) + ne_2) + ..., common.h:161-171)
-    d.saturate = (variant == LDPC_MINSUM && dtype == LDPC_F32) ? 1 : 0;   // (fp16 storage saturates at +-65504 by its own rule)
-    d.big = nullptr; d.kexp = nullptr;
-    // ONE predicate for both paths: rows of weight <= 4 take the pair-product form of the tanh rule exactly when the on-chip path of
-    // this code is the generic kernel (whose DMAX = 4 instance is written that way) -- a plain graph, or a QC description the
-    // split family does not take (circulant size below 16, LDPC_JIT=0, ...).  Such a QC code then also runs its flood path on the
-    // batch-major kernels, which know the form; a QC code of the split family uses the chained form everywhere (flood_qc_kernel too).
-    d.pairs4 = (variant == LDPC_TANH && dtype != LDPC_F64 && code->max_row_deg <= 4 &&
-                (code->sz == 0 || ldpc::jit_split_why_not(*code, variant, LDPC_F32) != nullptr)) ? 1 : 0;
-    ctx->flood.variant = variant; ctx->flood.dtype = dtype; ctx->flood.timer = &ctx->timer;
+    if (!ctx) { delete backend; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    ctx->code = code; ctx->max_batch = max_batch; ctx->device = device; ctx->schedule = schedule; ctx->backend = backend;
+    backend->timer = &ctx->timer;
+    hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        set_error(e == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking): %s", hipGetErrorString(e));
+        ldpc_ctx_destroy(ctx);
+        return nullptr;
+    }
     // (the staging buffers of the host-pointer entry points are allocated on first use: a context driven
     //  through ldpc_decode_batch_dev with 65 536 frames would otherwise park 3 GB of HBM)
-    const int qc_flooding = schedule == LDPC_SCHED_FLOODING ? 1 : 0;
-    if (ctx->path == LDPC_PATH_FLOOD && sum_order == LDPC_SUM_REFERENCE && variant != LDPC_TANH_CUDA32 && !(d.pairs4 && qc_flooding) && ldpc::layered_qc_why_not(*code, variant, dtype, qc_flooding) == nullptr) {
-        // QC code, either schedule: one workgroup per frame, state in HBM (a frame stops when ITS rule fires);
-        // any other H, fp16 storage and the arraylet-cm parity mode: the batch-major kernels below
-        ctx->lqc = ldpc::layered_qc_create(*code, variant, dtype, max_batch, qc_flooding);
-        if (!ctx->lqc) { ldpc_ctx_destroy(ctx); return nullptr; }
-        ldpc::layered_qc_set_timer(ctx->lqc, &ctx->timer);
-    } else if (ctx->path == LDPC_PATH_FLOOD) {
-        CTX_HIP(hipMalloc(&ctx->flood.msg, std::max<size_t>((size_t)code->E, 1) * Bp * es));
-        // scratch is only touched by rows whose degree has no register kernel
-        bool need_scratch = false;
-        const char *wz = getenv("LDPC_FLOOD_WIDE");   // LDPC_FLOOD_WIDE=0: rows of weight 9..32 through the O(d^2) fallback (A/B)
-        const bool paddable = !(variant != LDPC_MINSUM && dtype == LDPC_F64) && !(wz && !strcmp(wz, "0"));
-        for (int m = 0; m < code->M; m++) {
-            int dg = code->row_ptr[m + 1] - code->row_ptr[m];
-            if (dg <= 8 || dg == 18) continue;
-            if (paddable && dg <= 32) { ctx->flood.has_wide_rows = true; d.wide_rows = 1; }   // padded register rows (second CN instance)
-            else need_scratch = true;                                    // O(d^2) fallback writes through scratch
-        }
-        if (need_scratch) CTX_HIP(hipMalloc(&ctx->flood.scratch, std::max<size_t>((size_t)code->E, 1) * Bp * es));
-        CTX_HIP(hipMalloc(&ctx->flood.lam, (size_t)code->N * Bp * es));
-        CTX_HIP(hipMalloc(&ctx->flood.orig, (size_t)code->N * Bp * es));
-        CTX_HIP(hipMalloc((void **)&d.unsat, sizeof(int32_t) * Bp));
-        CTX_HIP(hipMalloc((void **)&d.iters, sizeof(int32_t) * Bp));
-        CTX_HIP(hipMalloc((void **)&d.conv, Bp));
-        CTX_HIP(hipMalloc((void **)&d.done, Bp));
-        if (d.saturate) { CTX_HIP(hipMalloc((void **)&d.big, sizeof(int32_t) * Bp)); CTX_HIP(hipMalloc((void **)&d.kexp, sizeof(int32_t) * Bp)); }
-        if (schedule == LDPC_SCHED_LAYERED) {
-            ctx->flood.layered = true;
-            ctx->flood.n_layers = (int)code->layer_ptr.size() - 1;
-            ctx->flood.max_row_deg = code->max_row_deg;
-            CTX_HIP(hipMalloc((void **)&ctx->flood.d_layer_ptr, sizeof(int32_t) * code->layer_ptr.size()));
-            CTX_HIP(hipMemcpy(ctx->flood.d_layer_ptr, code->layer_ptr.data(), sizeof(int32_t) * code->layer_ptr.size(), hipMemcpyHostToDevice));
-        }
-    } else {
-        ctx->fused = schedule == LDPC_SCHED_LAYERED ? ldpc::fused_layered_create(*code, variant, dtype, max_batch) : ldpc::fused_create(*code, variant, dtype, max_batch);
-        if (!ctx->fused && schedule == LDPC_SCHED_LAYERED && path == LDPC_PATH_AUTO && dtype != LDPC_F16PK &&
-            ldpc::layered_qc_why_not(*code, variant, dtype, 0) == nullptr) {
-            // the on-chip layered kernel of this code is compiled at run time and that failed (no compiler on this host, or it
-            // rejected the instance): under LDPC_PATH_AUTO the context keeps its state in HBM instead, as fused_create() falls back
-            // to its table-driven kernels for the flooding schedule
-            fprintf(stderr, "libldpc_hip: on-chip layered kernel unavailable (%s); the context runs the layered schedule from HBM\n", ldpc_last_error());
-            ctx->path = LDPC_PATH_FLOOD;
-            ctx->lqc = ldpc::layered_qc_create(*code, variant, dtype, max_batch, 0);
-            if (!ctx->lqc) { ldpc_ctx_destroy(ctx); return nullptr; }
-            ldpc::layered_qc_set_timer(ctx->lqc, &ctx->timer);
-            return ctx;
-        }
-        if (!ctx->fused) { ldpc_ctx_destroy(ctx); return nullptr; }
-        ldpc::fused_set_timer(ctx->fused, &ctx->timer);
-    }
     return ctx;
 }
 
@@ -568,7 +465,7 @@ ldpc_ctx *ldpc_ctx_create(const ldpc_code *code, int variant, int dtype, int max
     return ldpc_ctx_create_ex(code, variant, dtype, max_batch, LDPC_PATH_AUTO);
 }
 
-int ldpc_ctx_path(const ldpc_ctx *ctx) { return ctx ? ctx->path : set_error(LDPC_EINVAL, "null ctx"); }
+int ldpc_ctx_path(const ldpc_ctx *ctx) { return ctx ? ctx->backend->path : set_error(LDPC_EINVAL, "null ctx"); }
 
 void *ldpc_host_alloc(size_t bytes) {
     void *p = nullptr;
@@ -597,14 +494,7 @@ static int check_call(ldpc_ctx *ctx, int max_iters, int batch) {
 static int decode_dev(ldpc_ctx *ctx, hipStream_t st, int max_iters, int batch, const void *d_llr, int fmt,
                       uint8_t *d_bits, int32_t *d_iters, uint8_t *d_conv, double *d_final, double *d_trace) {
     if (batch == 0) return LDPC_OK;
-    if (ctx->path == LDPC_PATH_FUSED)
-        return ldpc::fused_decode(*ctx->fused, st, max_iters, batch, d_llr, fmt, d_bits, d_iters, d_conv, d_final, d_trace);
-    if (ctx->lqc) return ldpc::layered_qc_decode(*ctx->lqc, st, max_iters, batch, d_llr, fmt, d_bits, d_iters, d_conv, d_final, d_trace);
-    int rc = ldpc::flood_decode(ctx->flood, st, max_iters, batch, d_llr, fmt, d_bits, d_final, d_trace);
-    if (rc != LDPC_OK) return rc;
-    if (d_iters) HIPCHK(hipMemcpyAsync(d_iters, ctx->flood.dev.iters, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToDevice, st));
-    if (d_conv) HIPCHK(hipMemcpyAsync(d_conv, ctx->flood.dev.conv, (size_t)batch, hipMemcpyDeviceToDevice, st));
-    return LDPC_OK;
+    return ctx->backend->decode(st, max_iters, batch, d_llr, fmt, d_bits, d_iters, d_conv, d_final, d_trace);
 }
 
 // frames per pipelined chunk of the host-pointer entry points (fused paths)
@@ -613,7 +503,7 @@ static constexpr int kHostChunk = 8192;
 static int ensure_staging(ldpc_ctx *ctx, bool want_final) {
     const size_t N = (size_t)ctx->code->N;
     if (!ctx->d_in[0]) {
-        const bool pipelined = ctx->path == LDPC_PATH_FUSED && ctx->max_batch > kHostChunk;
+        const bool pipelined = ctx->backend->path == LDPC_PATH_FUSED && ctx->max_batch > kHostChunk;
         ctx->chunk = pipelined ? kHostChunk : ctx->max_batch;
         ctx->slots = pipelined ? std::min(ldpc_ctx::kSlots, (ctx->max_batch + kHostChunk - 1) / kHostChunk) : 1;
         ctx->pstream[0] = ctx->stream;
@@ -662,12 +552,7 @@ static int decode_host(ldpc_ctx *ctx, int max_iters, int batch, const void *llr,
     // compute of the other workgroups.  Measured (65 536 jpl.4096 frames, min-sum): f32 26.9 ms vs 57.9 ms through
     // the chunked copy pipeline, fp16 LLRs 24.6 vs 44.7 ms (copies issued next to the decode kernel did not overlap
     // with it on this platform: pipeline time = copy time + kernel time).
-    // (Not flood_qc_kernel: it re-reads the channel LLRs from the input in every variable-node pass, N values per frame
-    // and turn, which over PCIe would be ~70 GB for 65 536 jpl.4096 frames.  The batch-major flood kernels copy the
-    // input to their own `orig` once, the layered kernel reads it once into lam.)
-    const bool reads_once = ctx->path == LDPC_PATH_FLOOD ? (!ctx->lqc || ctx->schedule == LDPC_SCHED_LAYERED)
-                                                         : ldpc::fused_reads_llr_once(*ctx->fused, max_iters);
-    if (!final_lam && !trace_lam && batch > ldpc_ctx::kSmallFrames && reads_once) {
+    if (!final_lam && !trace_lam && batch > ldpc_ctx::kSmallFrames && ctx->backend->reads_llr_once(max_iters)) {
         void *z_llr = pinned_device_ptr(llr), *z_bits = pinned_device_ptr(bits);
         if (z_llr && z_bits) {
             int32_t *z_it = (int32_t *)pinned_device_ptr(iters);
@@ -877,12 +762,7 @@ int ldpc_debug_step(ldpc_ctx *ctx, int batch, const double *orig, const double *
     if (ce == hipSuccess) ce = hipMemcpyAsync(d_lam, lam, B * N * 8, hipMemcpyHostToDevice, st);
     if (ce == hipSuccess) ce = hipMemcpyAsync(d_ne, ne, B * E * 8, hipMemcpyHostToDevice, st);
     if (ce != hipSuccess) rc = set_error(LDPC_EHIP, "debug_step upload: %s", hipGetErrorString(ce));
-    else if (ctx->path == LDPC_PATH_FUSED)
-        rc = ldpc::fused_step(*ctx->fused, st, batch, d_orig, d_lam, d_ne, d_ne_out, d_lam_out, d_syn);
-    else if (ctx->lqc)
-        rc = ldpc::layered_qc_step(*ctx->lqc, st, batch, d_orig, d_lam, d_ne, d_ne_out, d_lam_out, d_syn);
-    else
-        rc = ldpc::flood_step(ctx->flood, st, batch, d_orig, d_lam, d_ne, d_ne_out, d_lam_out, d_syn);
+    else rc = ctx->backend->step(st, batch, d_orig, d_lam, d_ne, d_ne_out, d_lam_out, d_syn);
     if (rc == LDPC_OK) {
         ce = hipMemcpyAsync(ne_out, d_ne_out, B * E * 8, hipMemcpyDeviceToHost, st);
         if (ce == hipSuccess) ce = hipMemcpyAsync(lam_out, d_lam_out, B * N * 8, hipMemcpyDeviceToHost, st);
@@ -912,35 +792,25 @@ int ldpc_ctx_kernel_time(ldpc_ctx *ctx, int *launches, double *total_ms) {
 }
 
 const char *ldpc_ctx_kernel_name(const ldpc_ctx *ctx) {
-    if (!ctx) return "";
-    if (ctx->path == LDPC_PATH_FUSED && ctx->fused) return ldpc::fused_kernel_name(*ctx->fused);
-    if (ctx->lqc) return ldpc::layered_qc_launch_info(*ctx->lqc).name;
-    return ctx->schedule == LDPC_SCHED_LAYERED ? "layered_kernel" : "flood_cn_kernel";
+    return ctx ? ctx->backend->kernel_name() : "";
 }
 
 int ldpc_ctx_kernel_geometry(const ldpc_ctx *ctx, int *threads_per_workgroup, int *frames_per_workgroup) {
     if (!ctx) return set_error(LDPC_EINVAL, "null ctx");
-    int t = 0, f = 0;
-    if (ctx->path == LDPC_PATH_FUSED && ctx->fused) { const ldpc::LaunchInfo &li = ldpc::fused_launch_info(*ctx->fused); t = li.threads; f = li.frames_per_wg; }
-    if (ctx->lqc) { const ldpc::LaunchInfo &li = ldpc::layered_qc_launch_info(*ctx->lqc); t = li.threads; f = li.frames_per_wg; }
-    if (threads_per_workgroup) *threads_per_workgroup = t;
-    if (frames_per_workgroup) *frames_per_workgroup = f;
+    const ldpc::LaunchInfo &li = ctx->backend->info;
+    if (threads_per_workgroup) *threads_per_workgroup = li.threads;
+    if (frames_per_workgroup) *frames_per_workgroup = li.frames_per_wg;
     return LDPC_OK;
 }
 
 // ------------------------------------------------------------------------------- run-time specialised kernels
 const char *ldpc_jit_cache_dir(void) { return ldpc::jit_cache_dir(); }
 
-static int jit_kind_of(int dtype, int schedule) {
-    if (schedule == LDPC_SCHED_LAYERED) return dtype == LDPC_F16PK ? ldpc::JIT_LAYERED_PK16 : ldpc::JIT_LAYERED;
-    return dtype == LDPC_F16PK ? ldpc::JIT_PK16 : ldpc::JIT_SPLIT;
-}
-
 long ldpc_jit_source_for(const ldpc_code *code, int variant, int dtype, int schedule, char *buf, size_t cap) {
     if (!code) return set_error(LDPC_EINVAL, "null code");
     if (schedule != LDPC_SCHED_FLOODING && schedule != LDPC_SCHED_LAYERED) return set_error(LDPC_EINVAL, "unknown schedule %d", schedule);
     try {
-        const int kind = jit_kind_of(dtype, schedule);
+        const int kind = ldpc::jit_kind_of(dtype, schedule);
         const char *why = ldpc::jit_split_why_not(*code, variant, dtype, kind);
         if (why) return set_error(LDPC_EUNSUPPORTED, "%s", why);
         const std::string src = ldpc::jit_split_source(*code, variant, dtype, nullptr, kind);
@@ -953,7 +823,7 @@ int ldpc_jit_prepare_for(const ldpc_code *code, int variant, int dtype, int sche
     if (!code) return set_error(LDPC_EINVAL, "null code");
     if (schedule != LDPC_SCHED_FLOODING && schedule != LDPC_SCHED_LAYERED) return set_error(LDPC_EINVAL, "unknown schedule %d", schedule);
     try {
-        const int kind = jit_kind_of(dtype, schedule);
+        const int kind = ldpc::jit_kind_of(dtype, schedule);
         const char *why = ldpc::jit_split_why_not(*code, variant, dtype, kind);
         if (why) return set_error(LDPC_EUNSUPPORTED, "%s", why);
         ldpc::JitKernel g;

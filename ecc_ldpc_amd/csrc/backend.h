@@ -1,0 +1,39 @@
+// backend.h -- the one decoder a context owns (host side).  Every kernel family implements this interface in its own
+// translation unit and owns its own buffers; make_backend (select.cc) decides which family and instance a context gets.
+#pragma once
+#include "internal.h"
+
+namespace ldpc {
+
+struct Backend {
+    int path = LDPC_PATH_FUSED;   // what ldpc_ctx_path reports: LDPC_PATH_FUSED (state on-chip) or LDPC_PATH_FLOOD (state in HBM)
+    KernelTimer *timer = nullptr; // the context's event bracket around the dominant kernel (set by the context after creation)
+    // the dominant kernel's name and geometry (ldpc_ctx_kernel_name / _geometry): set at creation, or by the first decode launch of
+    // families whose instance depends on the call
+    LaunchInfo info;
+    virtual ~Backend() {}
+    // d_llr [batch][N] of element type llr_fmt (LLR_F32 / LLR_F64 / LLR_F16); device outputs, all but d_bits may be null
+    virtual int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                       uint8_t *d_conv, double *d_final, double *d_trace) = 0;
+    // one teacher-forced iteration from given (lam, ne) in f64 (ldpc_debug_step), or LDPC_EUNSUPPORTED with the reason
+    virtual int step(hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne, double *d_ne_out,
+                     double *d_lam_out, uint8_t *d_syn) = 0;
+    virtual const char *kernel_name() const { return info.name; }
+    // whether decode() reads every channel LLR from memory exactly once (then the LLRs may sit in page-locked HOST memory and be
+    // read over PCIe by the kernel itself: api.cc zero-copy path)
+    virtual bool reads_llr_once(int max_iters) const = 0;
+};
+
+// The decoder for a validated context configuration (api.cc ldpc_ctx_create_cfg), on the calling thread's current device, whose
+// graph tables are `tabs`.  nullptr + set_error when no kernel serves the configuration or creating it failed.
+Backend *make_backend(const ldpc_code &c, const ldpc_code_dev &tabs, int variant, int dtype, int schedule, int sum_order, int path,
+                      int max_batch);
+
+// null when the row-layered schedule's layers are the block rows of the code's QC description, else why not
+const char *layers_why_not(const ldpc_code &c);
+
+// batch-major flood path for any H (flood.hip), flooding or layered schedule; pairs4: see FloodDev
+Backend *flood_create(const ldpc_code &c, const ldpc_code_dev &tabs, int variant, int dtype, int schedule, int sum_order, int pairs4,
+                      int max_batch);
+
+}  // namespace ldpc

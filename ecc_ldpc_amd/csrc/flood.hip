@@ -23,8 +23,10 @@
 // the B_iter of SURVEY.md section 8d.
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
+
 #include "ldpc_math.h"
-#include "internal.h"
+#include "backend.h"
 
 namespace ldpc {
 
@@ -769,7 +771,40 @@ __global__ __launch_bounds__(kWave *kLayerWaves) void layered_kernel(FloodDev d,
     }
 }
 
-// ------------------------------------------------------------------ host-side launch sequences
+// ------------------------------------------------------------------ host side
+struct FloodState : Backend {
+    FloodDev dev{};
+    int variant = 0, dtype = 0;
+    bool has_wide_rows = false;   // some check row has weight 9..32 (not 18): second CN kernel instance
+    void *msg = nullptr, *scratch = nullptr, *lam = nullptr, *orig = nullptr;
+    // row-layered schedule (extension; layered_kernel): layers as row ranges, device copy owned by this state
+    bool layered = false;
+    int n_layers = 0, max_row_deg = 0;
+    int32_t *d_layer_ptr = nullptr;
+    // The turn loop (2 launches per turn, no host decision inside: finished frames are frozen on the device)
+    // touches only this context's buffers, so it is captured once per max_iters into a hipGraph and
+    // replayed: one graph launch instead of 2*max_iters + 2 kernel launches.  graph_release() frees it.
+    hipGraphExec_t turn_graph = nullptr;
+    int graph_iters = -1;
+
+    ~FloodState() override {
+        graph_release();
+        (void)hipFree(msg); (void)hipFree(scratch); (void)hipFree(lam); (void)hipFree(orig); (void)hipFree(d_layer_ptr);
+        (void)hipFree(dev.unsat); (void)hipFree(dev.iters); (void)hipFree(dev.conv); (void)hipFree(dev.done); (void)hipFree(dev.big); (void)hipFree(dev.kexp);
+    }
+    int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+               uint8_t *d_conv, double *d_final, double *d_trace) override;
+    int step(hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne, double *d_ne_out,
+             double *d_lam_out, uint8_t *d_syn) override;
+    const char *kernel_name() const override { return layered ? "layered_kernel" : "flood_cn_kernel"; }
+    // (the input is copied to `orig` once)
+    bool reads_llr_once(int) const override { return true; }
+    void graph_release() {
+        if (turn_graph) { (void)hipGraphExecDestroy(turn_graph); turn_graph = nullptr; }
+        graph_iters = -1;
+    }
+};
+
 #define HIPCHK(x)                                                             \
     do {                                                                      \
         hipError_t e_ = (x);                                                  \
@@ -815,7 +850,7 @@ static int run_turns(FloodState &s, hipStream_t st, int max_iters, int batch, do
     const bool timing = s.timer && s.timer->enabled;
     if (graph_wanted() && !d_trace && !timing && st != nullptr && max_iters > 0) {
         if (!s.turn_graph || s.graph_iters != max_iters) {   // (the loop's grids cover the context's Bp frames, whatever `batch` is)
-            flood_graph_release(s);
+            s.graph_release();
             hipGraph_t g = nullptr;
             hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
             if (e == hipSuccess) {
@@ -979,22 +1014,75 @@ static int layered_step_impl(FloodState &s, hipStream_t st, int batch, const dou
         default: return set_error(LDPC_EUNSUPPORTED, "the layered schedule exists for f32 and f64");                                    \
     }
 
-int flood_decode(FloodState &s, hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt,
-                 uint8_t *d_bits, double *d_final, double *d_trace) {
+static int decode_any(FloodState &s, hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits,
+                      double *d_final, double *d_trace) {
     if (s.layered) { DISPATCH_NO_F16(layered_decode_impl, s, st, max_iters, batch, d_llr, llr_fmt, d_bits, d_final, d_trace) }
     DISPATCH(decode_impl, s, st, max_iters, batch, d_llr, llr_fmt, d_bits, d_final, d_trace)
 }
-int flood_step(FloodState &s, hipStream_t st, int batch, const double *d_orig, const double *d_lam,
-               const double *d_ne, double *d_ne_out, double *d_lam_out, uint8_t *d_syn) {
-    if (s.layered) { DISPATCH_NO_F16(layered_step_impl, s, st, batch, d_orig, d_lam, d_ne, d_ne_out, d_lam_out, d_syn) }
+
+int FloodState::decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                       uint8_t *d_conv, double *d_final, double *d_trace) {
+    int rc = decode_any(*this, st, max_iters, batch, d_llr, llr_fmt, d_bits, d_final, d_trace);
+    if (rc != LDPC_OK) return rc;
+    if (d_iters) HIPCHK(hipMemcpyAsync(d_iters, dev.iters, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToDevice, st));
+    if (d_conv) HIPCHK(hipMemcpyAsync(d_conv, dev.conv, (size_t)batch, hipMemcpyDeviceToDevice, st));
+    return LDPC_OK;
+}
+
+int FloodState::step(hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne, double *d_ne_out,
+                     double *d_lam_out, uint8_t *d_syn) {
+    FloodState &s = *this;
+    if (layered) { DISPATCH_NO_F16(layered_step_impl, s, st, batch, d_orig, d_lam, d_ne, d_ne_out, d_lam_out, d_syn) }
     DISPATCH(step_impl, s, st, batch, d_orig, d_lam, d_ne, d_ne_out, d_lam_out, d_syn)
 }
 
-void flood_graph_release(FloodState &s) {
-    if (s.turn_graph) { (void)hipGraphExecDestroy(s.turn_graph); s.turn_graph = nullptr; }
-    s.graph_iters = -1;
+Backend *flood_create(const ldpc_code &c, const ldpc_code_dev &tabs, int variant, int dtype, int schedule, int sum_order, int pairs4,
+                      int max_batch) {
+    FloodState *s = new (std::nothrow) FloodState();
+    if (!s) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    s->path = LDPC_PATH_FLOOD; s->variant = variant; s->dtype = dtype;
+    const size_t es = dtype == LDPC_F64 ? 8 : (dtype == LDPC_F16 ? 2 : 4);
+    const size_t Bp = (size_t)(max_batch + 63) / 64 * 64;
+    FloodDev &d = s->dev;
+    d.M = c.M; d.N = c.N; d.E = c.E; d.Bp = (int)Bp;
+    d.row_ptr = tabs.row_ptr; d.col_idx = tabs.col_idx; d.col_ptr = tabs.col_ptr; d.csc_edge = tabs.csc_edge;
+    d.cm_order = variant == LDPC_TANH_CM ? LDPC_SUM_ARRAYLET : (variant == LDPC_TANH_CUDA32 ? 3 : sum_order);   // (3: ((orig + ne_1) + ne_2) + ..., common.h:161-171)
+    d.saturate = (variant == LDPC_MINSUM && dtype == LDPC_F32) ? 1 : 0;   // (fp16 storage saturates at +-65504 by its own rule)
+    d.pairs4 = pairs4;
+    // scratch is only touched by rows whose degree has no register kernel
+    bool need_scratch = false;
+    const char *wz = getenv("LDPC_FLOOD_WIDE");   // LDPC_FLOOD_WIDE=0: rows of weight 9..32 through the O(d^2) fallback (A/B)
+    const bool paddable = !(variant != LDPC_MINSUM && dtype == LDPC_F64) && !(wz && !strcmp(wz, "0"));
+    for (int m = 0; m < c.M; m++) {
+        int dg = c.row_ptr[m + 1] - c.row_ptr[m];
+        if (dg <= 8 || dg == 18) continue;
+        if (paddable && dg <= 32) { s->has_wide_rows = true; d.wide_rows = 1; }   // padded register rows (second CN instance)
+        else need_scratch = true;                                    // O(d^2) fallback writes through scratch
+    }
+    hipError_t e = hipMalloc(&s->msg, std::max<size_t>((size_t)c.E, 1) * Bp * es);
+    if (e == hipSuccess && need_scratch) e = hipMalloc(&s->scratch, std::max<size_t>((size_t)c.E, 1) * Bp * es);
+    if (e == hipSuccess) e = hipMalloc(&s->lam, (size_t)c.N * Bp * es);
+    if (e == hipSuccess) e = hipMalloc(&s->orig, (size_t)c.N * Bp * es);
+    if (e == hipSuccess) e = hipMalloc((void **)&d.unsat, sizeof(int32_t) * Bp);
+    if (e == hipSuccess) e = hipMalloc((void **)&d.iters, sizeof(int32_t) * Bp);
+    if (e == hipSuccess) e = hipMalloc((void **)&d.conv, Bp);
+    if (e == hipSuccess) e = hipMalloc((void **)&d.done, Bp);
+    if (e == hipSuccess && d.saturate) e = hipMalloc((void **)&d.big, sizeof(int32_t) * Bp);
+    if (e == hipSuccess && d.saturate) e = hipMalloc((void **)&d.kexp, sizeof(int32_t) * Bp);
+    if (schedule == LDPC_SCHED_LAYERED) {
+        s->layered = true;
+        s->n_layers = (int)c.layer_ptr.size() - 1;
+        s->max_row_deg = c.max_row_deg;
+        if (e == hipSuccess) e = hipMalloc((void **)&s->d_layer_ptr, sizeof(int32_t) * c.layer_ptr.size());
+        if (e == hipSuccess) e = hipMemcpy(s->d_layer_ptr, c.layer_ptr.data(), sizeof(int32_t) * c.layer_ptr.size(), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        set_error(e == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "flood_create (%zu frames x %zu bytes of state): %s", Bp,
+                  (2 * (size_t)c.E + 2 * (size_t)c.N) * es, hipGetErrorString(e));
+        delete s;
+        return nullptr;
+    }
+    return s;
 }
-
-size_t flood_elem_size(int dtype) { return dtype == LDPC_F64 ? 8 : (dtype == LDPC_F16 ? 2 : 4); }
 
 }  // namespace ldpc

@@ -631,7 +631,7 @@ __global__ __launch_bounds__(THREADS, (DMAX <= 8 ? (THREADS > 512 ? 4 : THREADS 
 }
 
 // ------------------------------------------------------------------ host side
-struct CsrState {
+struct CsrState : Backend {
     const void *attr_kern = nullptr; size_t attr_lds = 0;      // the kernel whose dynamic-LDS limit this context has raised, and to what
     const void *stage_kern = nullptr; bool stage_ok = false;   // batched kernel: whether the LLR staging area fits without costing a resident workgroup
     int variant = 0, dtype = 0, M = 0, N = 0, E = 0, dmax = 0, cdmax = 0, round16 = 0;
@@ -644,8 +644,17 @@ struct CsrState {
     size_t resident_lds = 0;
     const void *resident_kern = nullptr;
     uint32_t *d_cpack = nullptr, *d_rpack = nullptr;  // OSH instance: packed column-slot / row-slot offsets per thread
-    KernelTimer *timer = nullptr;
-    LaunchInfo info;
+
+    ~CsrState() override {
+        (void)hipFree(d_ell); (void)hipFree(d_csc); (void)hipFree(d_row_ptr); (void)hipFree(d_ell_b); (void)hipFree(d_csc_b); (void)hipFree(d_row_of_pos);
+        (void)hipFree(d_col_of_pos); (void)hipFree(d_counter); (void)hipFree(d_cpack); (void)hipFree(d_rpack);
+    }
+    int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+               uint8_t *d_conv, double *d_final, double *d_trace) override;
+    int step(hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne, double *d_ne_out,
+             double *d_lam_out, uint8_t *d_syn) override;
+    const char *kernel_name() const override;
+    bool reads_llr_once(int) const override { return true; }
 };
 
 static int pick_dmax(int maxdeg) { return maxdeg <= 4 ? 4 : maxdeg <= 6 ? 6 : maxdeg <= 8 ? 8 : maxdeg <= 20 ? 20 : maxdeg <= 32 ? 32 : 0; }
@@ -784,12 +793,6 @@ const char *fused_csr_why_not(const ldpc_code &c, int variant, int dtype) {
     return nullptr;
 }
 
-void fused_csr_destroy(CsrState *s) {
-    if (!s) return;
-    (void)hipFree(s->d_ell); (void)hipFree(s->d_csc); (void)hipFree(s->d_row_ptr);
-    (void)hipFree(s->d_ell_b); (void)hipFree(s->d_csc_b); (void)hipFree(s->d_row_of_pos); (void)hipFree(s->d_col_of_pos); (void)hipFree(s->d_counter); (void)hipFree(s->d_cpack); (void)hipFree(s->d_rpack);
-    delete s;
-}
 
 // which batched instance (if any) serves this shape: 0 = none (row-by-row kernel)
 static int batched_shape(const CsrState &s) {
@@ -807,12 +810,10 @@ static int batched_shape(const CsrState &s) {
     return 0;
 }
 
-CsrState *fused_csr_create(const ldpc_code &c, int variant, int dtype) {
-    const char *why = fused_csr_why_not(c, variant, dtype);
-    if (why) { set_error(LDPC_EUNSUPPORTED, "%s", why); return nullptr; }
+Backend *fused_csr_create(const ldpc_code &c, int variant, int dtype, int round16) {
     CsrState *s = new (std::nothrow) CsrState();
     if (!s) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
-    s->variant = variant; s->dtype = dtype; s->M = c.M; s->N = c.N; s->E = c.E;
+    s->variant = variant; s->dtype = dtype; s->M = c.M; s->N = c.N; s->E = c.E; s->round16 = round16;
     s->dmax = pick_dmax(c.max_row_deg); s->cdmax = c.max_col_deg;
     {   // LDPC_CSR_BATCHED=0: row-by-row kernel; LDPC_CSR_NOCACHE: its indices re-read from memory every turn
         const char *bz = getenv("LDPC_CSR_BATCHED");
@@ -896,16 +897,15 @@ CsrState *fused_csr_create(const ldpc_code &c, int variant, int dtype) {
         if (e == hipSuccess) e = up(&s->d_row_of_pos, P.row_of_pos);
         if (e == hipSuccess) e = up(&s->d_col_of_pos, P.col_of_pos);
     }
-    if (e != hipSuccess) { set_error(LDPC_EHIP, "fused_csr_create: %s", hipGetErrorString(e)); fused_csr_destroy(s); return nullptr; }
+    if (e != hipSuccess) { set_error(LDPC_EHIP, "fused_csr_create: %s", hipGetErrorString(e)); delete s; return nullptr; }
     return s;
 }
 
-void fused_csr_set_timer(CsrState *s, KernelTimer *t) { if (s) s->timer = t; }
-const LaunchInfo &fused_csr_launch_info(const CsrState &s) { return s.info; }
-const char *fused_csr_kernel_name(const CsrState &s) {
-    return (s.dtype == LDPC_F32 && s.d_ell_b && s.want_batched && batched_shape(s)) ? "fused_csr_batched_kernel" : "fused_csr_kernel";
+// (before the first decode: which kernel it will be, without the template arguments its launch records in `info`)
+const char *CsrState::kernel_name() const {
+    if (info.name[0]) return info.name;
+    return (dtype == LDPC_F32 && d_ell_b && want_batched && batched_shape(*this)) ? "fused_csr_batched_kernel" : "fused_csr_kernel";
 }
-void fused_csr_set_round16(CsrState *s, int on) { if (s) s->round16 = on; }
 
 template <typename CT, int VARIANT, int DMAX, int RPT, int CPT, int THREADS = kCsrThreads>
 static int launch_csr(CsrState &s, hipStream_t st, CsrArgs &a) {
@@ -1067,20 +1067,20 @@ static int csr_run(CsrState &s, hipStream_t st, CsrArgs &a) {
     return s.variant == LDPC_MINSUM ? dispatch_dmax<float, LDPC_V_MINSUM>(s, st, a) : dispatch_dmax<float, LDPC_V_TANH>(s, st, a);
 }
 
-int fused_csr_decode(CsrState &s, hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits,
-                     int32_t *d_iters, uint8_t *d_conv, double *d_final, double *d_trace) {
+int CsrState::decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                     uint8_t *d_conv, double *d_final, double *d_trace) {
     CsrArgs a{};
-    a.llr = d_llr; a.llr_fmt = llr_fmt; a.llr_round16 = s.round16; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final; a.trace = d_trace;
+    a.llr = d_llr; a.llr_fmt = llr_fmt; a.llr_round16 = round16; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final; a.trace = d_trace;
     a.batch = batch; a.max_iters = max_iters;
-    return csr_run(s, st, a);
+    return csr_run(*this, st, a);
 }
 
-int fused_csr_step(CsrState &s, hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne,
-                   double *d_ne_out, double *d_lam_out, uint8_t *d_syn) {
+int CsrState::step(hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne, double *d_ne_out,
+                   double *d_lam_out, uint8_t *d_syn) {
     CsrArgs a{};
     a.llr = d_orig; a.llr_fmt = LLR_F64; a.llr_round16 = 0; a.batch = batch; a.max_iters = 1; a.step_mode = 1;
     a.st_lam = d_lam; a.st_ne_in = d_ne; a.st_ne_out = d_ne_out; a.final_lam = d_lam_out; a.st_syn = d_syn;
-    return csr_run(s, st, a);
+    return csr_run(*this, st, a);
 }
 
 }  // namespace ldpc

@@ -81,30 +81,6 @@ struct LaunchInfo {
     int frames_per_wg = 0;   // frames one workgroup decodes (0: not a frame-per-workgroup kernel)
 };
 
-struct FloodState {
-    FloodDev dev;
-    int variant, dtype;
-    KernelTimer *timer = nullptr;
-    bool has_wide_rows = false;   // some check row has weight 9..32 (not 18): second CN kernel instance, flood.hip
-    void *msg = nullptr, *scratch = nullptr, *lam = nullptr, *orig = nullptr;
-    // row-layered schedule (extension; flood.hip layered_kernel): layers as row ranges, device copy owned by the context
-    bool layered = false;
-    int n_layers = 0, max_row_deg = 0;
-    int32_t *d_layer_ptr = nullptr;
-    // The turn loop (2 launches per turn, no host decision inside: finished frames are frozen on the device)
-    // touches only this context's buffers, so it is captured once per max_iters into a hipGraph and
-    // replayed: one graph launch instead of 2*max_iters + 2 kernel launches.  flood_graph_release() frees it.
-    hipGraphExec_t turn_graph = nullptr;
-    int graph_iters = -1;
-};
-void flood_graph_release(FloodState &s);
-
-int flood_decode(FloodState &s, hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt,
-                 uint8_t *d_bits, double *d_final, double *d_trace);
-int flood_step(FloodState &s, hipStream_t st, int batch, const double *d_orig, const double *d_lam,
-               const double *d_ne, double *d_ne_out, double *d_lam_out, uint8_t *d_syn);
-size_t flood_elem_size(int dtype);
-
 }  // namespace ldpc
 
 // host-side graph (immutable after creation, except for the lazily created per-device copies of its tables)

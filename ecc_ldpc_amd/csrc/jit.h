@@ -32,6 +32,8 @@ enum JitKind {
     JIT_LAYERED = 2,        // fused_layered_body.h layered, f32 (min-sum)
     JIT_LAYERED_PK16 = 3,   // fused_layered_body.h layered, packed fp16 (min-sum)
 };
+// the kind a context of this dtype and schedule specialises (select.cc)
+int jit_kind_of(int dtype, int schedule);
 // Why the run-time specialised kernel cannot be built for this code/variant/dtype (nullptr = it can).  dtype: LDPC_F32, or
 // LDPC_F16PK for the packed-fp16 kinds.
 const char *jit_split_why_not(const ldpc_code &c, int variant, int dtype, int kind = JIT_SPLIT);

@@ -448,7 +448,7 @@ __global__ __launch_bounds__(lds_max_threads(DCLASS, P)) void layered_lds_kernel
 }
 
 // ------------------------------------------------------------------ host side
-struct LayeredLdsState {
+struct LayeredLdsState : Backend {
     int max_batch = 0, max_row_deg = 0, threads = 0, nbr = 0, grid = 0, prefetch = 0;   // threads: of ONE block row (tl)
     int ng = 0, gsz = 1, nslot = 0, rw = 1;        // groups of block rows run together (pipelined instances); rw: block rows of a group per sub
     size_t lds = 0;
@@ -456,8 +456,16 @@ struct LayeredLdsState {
     int32_t *d_tab = nullptr, *d_lbeg = nullptr, *d_ltab = nullptr;
     int *d_counter = nullptr;
     LdsRec *rec = nullptr;
-    KernelTimer *timer = nullptr;
-    LaunchInfo info;
+
+    ~LayeredLdsState() override {
+        (void)hipFree(d_tab); (void)hipFree(d_lbeg); (void)hipFree(d_ltab); (void)hipFree(d_counter); (void)hipFree(rec);
+    }
+    int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+               uint8_t *d_conv, double *d_final, double *d_trace) override;
+    int step(hipStream_t, int, const double *, const double *, const double *, double *, double *, uint8_t *) override {
+        return set_error(LDPC_EUNSUPPORTED, "no teacher-forced step with fp16 lam storage (the record kernels keep no per-edge messages)");
+    }
+    bool reads_llr_once(int) const override { return true; }
 };
 
 static size_t lds_bytes_for(const ldpc_code &c) { return (((size_t)c.N * 2 + 15) & ~(size_t)15) + 32; }
@@ -468,17 +476,10 @@ const char *layered_lds_why_not(const ldpc_code &c, int variant, int dtype) {
     if (dtype != LDPC_F16 || variant != LDPC_MINSUM) return "the lam-in-LDS layered kernel is min-sum with fp16 lam storage";
     if (c.max_row_deg > 27) return "check rows above weight 27";
     if (lds_bytes_for(c) > 160 * 1024) return "a frame's fp16 LLRs exceed the 160 KB of LDS";
-    if ((int)c.layer_ptr.size() != c.block_rows + 1) return "layers were replaced: not the block rows";
-    for (int br = 0; br <= c.block_rows; br++) if (c.layer_ptr[br] != br * c.sz) return "layers were replaced: not the block rows";
+    if (const char *l = layers_why_not(c)) return l;
     const char *e = getenv("LDPC_LAYERED_LDS");
     if (e && !strcmp(e, "0")) return "disabled (LDPC_LAYERED_LDS=0)";
     return nullptr;
-}
-
-void layered_lds_destroy(LayeredLdsState *s) {
-    if (!s) return;
-    (void)hipFree(s->d_tab); (void)hipFree(s->d_lbeg); (void)hipFree(s->d_ltab); (void)hipFree(s->d_counter); (void)hipFree(s->rec);
-    delete s;
 }
 
 template <int DCLASS, int P, int RW> static const void *kernel_ptr() { return (const void *)layered_lds_kernel<DCLASS, P, RW>; }
@@ -488,12 +489,11 @@ static const void *pick_kernel(int dclass, int p, int rw) {
     return dclass == 8 ? kernel_ptr<8, 4, 1>() : dclass == 20 ? kernel_ptr<20, 4, 1>() : kernel_ptr<32, 4, 1>();
 }
 
-LayeredLdsState *layered_lds_create(const ldpc_code &c, int variant, int dtype, int max_batch) {
-    const char *why = layered_lds_why_not(c, variant, dtype);
-    if (why) { set_error(LDPC_EUNSUPPORTED, "%s", why); return nullptr; }
+Backend *layered_lds_create(const ldpc_code &c, int max_batch) {
     LayeredLdsState *s = new (std::nothrow) LayeredLdsState();
     if (!s) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
     try {
+        s->path = LDPC_PATH_FLOOD;
         s->max_batch = max_batch; s->max_row_deg = c.max_row_deg; s->nbr = c.block_rows;
         std::vector<int32_t> tab, lbeg(1, 0);
         for (int br = 0; br < c.block_rows; br++) {
@@ -566,7 +566,7 @@ LayeredLdsState *layered_lds_create(const ldpc_code &c, int variant, int dtype, 
         if (e == hipSuccess) e = hipGetDevice(&dev);
         if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
         if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, s->threads * subs, s->lds);
-        if (e == hipSuccess && per_cu <= 0) { set_error(LDPC_EHIP, "layered_lds: no workgroup of %d threads and %zu B of LDS is resident", s->threads * subs, s->lds); layered_lds_destroy(s); return nullptr; }
+        if (e == hipSuccess && per_cu <= 0) { set_error(LDPC_EHIP, "layered_lds: no workgroup of %d threads and %zu B of LDS is resident", s->threads * subs, s->lds); delete s; return nullptr; }
         if (e == hipSuccess) s->grid = std::min(max_batch, per_cu * prop.multiProcessorCount);
         if (e == hipSuccess) e = hipMalloc((void **)&s->d_tab, sizeof(int32_t) * std::max<size_t>(tab.size(), 2));
         if (e == hipSuccess) e = hipMalloc((void **)&s->d_lbeg, sizeof(int32_t) * lbeg.size());
@@ -579,21 +579,19 @@ LayeredLdsState *layered_lds_create(const ldpc_code &c, int variant, int dtype, 
         if (e != hipSuccess) {
             set_error(e == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "layered_lds_create (%d workgroups x %zu bytes of records): %s", s->grid,
                       sizeof(LdsRec) * (size_t)c.block_rows * s->threads, hipGetErrorString(e));
-            layered_lds_destroy(s);
+            delete s;
             return nullptr;
         }
         s->g.tab = s->d_tab; s->g.lbeg = s->d_lbeg; s->g.gtab = s->d_ltab;
         snprintf(s->info.name, sizeof(s->info.name), "ldpc::layered_lds_kernel<%d, %d, %d>", dclass, s->prefetch, s->rw);
         s->info.threads = s->threads * subs; s->info.frames_per_wg = 1;
         return s;
-    } catch (...) { layered_lds_destroy(s); set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    } catch (...) { delete s; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
 }
 
-void layered_lds_set_timer(LayeredLdsState *s, KernelTimer *t) { if (s) s->timer = t; }
-const LaunchInfo &layered_lds_launch_info(const LayeredLdsState &s) { return s.info; }
-
-int layered_lds_decode(LayeredLdsState &s, hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
-                       uint8_t *d_conv, double *d_final, double *d_trace) {
+int LayeredLdsState::decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                            uint8_t *d_conv, double *d_final, double *d_trace) {
+    LayeredLdsState &s = *this;
     LdsArgs a{};
     a.llr = d_llr; a.llr_fmt = llr_fmt; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final; a.trace = d_trace;
     a.batch = batch; a.max_iters = max_iters; a.work_counter = s.d_counter;

@@ -443,7 +443,7 @@ __global__ __launch_bounds__(1024) void flood_qc_kernel(QcLayerDev g, CT *lam_al
 }
 
 // ------------------------------------------------------------------ host side
-struct LayeredQcState {
+struct LayeredQcState : Backend {
     int variant = 0, dtype = 0, max_batch = 0, max_row_deg = 0, threads = 0;
     QcLayerDev g{};
     bool flooding = false;
@@ -451,9 +451,17 @@ struct LayeredQcState {
     int32_t *d_tab = nullptr;
     int32_t *d_lbeg = nullptr, *d_ctab = nullptr, *d_cbeg = nullptr;
     void *lam = nullptr, *msg = nullptr;
-    LayeredLdsState *lds = nullptr;   // fp16 lam storage and the frame fits LDS: lam on-chip, records streamed (layered_lds.hip); then lam / msg above stay null
-    KernelTimer *timer = nullptr;
-    LaunchInfo info;
+
+    ~LayeredQcState() override {
+        (void)hipFree(d_tab); (void)hipFree(d_lbeg); (void)hipFree(d_ctab); (void)hipFree(d_cbeg); (void)hipFree(lam); (void)hipFree(msg);
+    }
+    int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+               uint8_t *d_conv, double *d_final, double *d_trace) override;
+    int step(hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne, double *d_ne_out,
+             double *d_lam_out, uint8_t *d_syn) override;
+    // (the layered kernel reads the LLRs once into lam; flood_qc_kernel re-reads them in every variable-node pass, N values per frame
+    //  and turn, which over PCIe would be ~70 GB for 65 536 jpl.4096 frames)
+    bool reads_llr_once(int) const override { return !flooding; }
 };
 
 const char *layered_qc_why_not(const ldpc_code &c, int variant, int dtype, int flooding) {
@@ -466,35 +474,18 @@ const char *layered_qc_why_not(const ldpc_code &c, int variant, int dtype, int f
     } else if (dtype != LDPC_F32 && dtype != LDPC_F64) return "the frame-per-workgroup HBM kernels exist for f32, f64 and (layered min-sum) fp16 lam storage";
     if (variant != LDPC_TANH && variant != LDPC_MINSUM) return "tanh and min-sum rules only";
     if (c.max_row_deg > 32) return "check rows above weight 32";
-    if (!flooding) {
-        if ((int)c.layer_ptr.size() != c.block_rows + 1) return "layers were replaced: not the block rows";
-        for (int br = 0; br <= c.block_rows; br++) if (c.layer_ptr[br] != br * c.sz) return "layers were replaced: not the block rows";
-    }
+    if (const char *l = flooding ? nullptr : layers_why_not(c)) return l;
     const char *e = getenv(flooding ? "LDPC_FLOOD_QC" : "LDPC_LAYERED_QC");
     if (e && !strcmp(e, "0")) return flooding ? "disabled (LDPC_FLOOD_QC=0)" : "disabled (LDPC_LAYERED_QC=0)";
     return nullptr;
 }
 
-void layered_qc_destroy(LayeredQcState *s) {
-    if (!s) return;
-    (void)hipFree(s->d_tab); (void)hipFree(s->d_lbeg); (void)hipFree(s->d_ctab); (void)hipFree(s->d_cbeg); (void)hipFree(s->lam); (void)hipFree(s->msg);
-    layered_lds_destroy(s->lds);
-    delete s;
-}
-
-LayeredQcState *layered_qc_create(const ldpc_code &c, int variant, int dtype, int max_batch, int flooding) {
-    const char *why = layered_qc_why_not(c, variant, dtype, flooding);
-    if (why) { set_error(LDPC_EUNSUPPORTED, "%s", why); return nullptr; }
+Backend *layered_qc_create(const ldpc_code &c, int variant, int dtype, int max_batch, int flooding) {
     LayeredQcState *s = new (std::nothrow) LayeredQcState();
     if (!s) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
     try {
+        s->path = LDPC_PATH_FLOOD;
         s->variant = variant; s->dtype = dtype; s->max_batch = max_batch; s->max_row_deg = c.max_row_deg; s->flooding = flooding != 0;
-        if (!flooding && layered_lds_why_not(c, variant, dtype) == nullptr) {
-            s->lds = layered_lds_create(c, variant, dtype, max_batch);
-            if (!s->lds) { layered_qc_destroy(s); return nullptr; }
-            s->info = layered_lds_launch_info(*s->lds);
-            return s;
-        }
         std::vector<int32_t> tab;
         std::vector<int32_t> lbeg(1, 0);
         std::vector<std::vector<std::pair<int, int>>> cols((size_t)c.block_cols);   // per block column: (circulant index, rotation), ascending block row
@@ -531,7 +522,7 @@ LayeredQcState *layered_qc_create(const ldpc_code &c, int variant, int dtype, in
         if (e != hipSuccess) {
             set_error(e == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "layered_qc_create (%d frames x %zu bytes of state): %s", max_batch,
                       ((size_t)c.N + c.E) * es, hipGetErrorString(e));
-            layered_qc_destroy(s);
+            delete s;
             return nullptr;
         }
         s->g.tab = s->d_tab; s->g.lbeg = s->d_lbeg; s->g.ctab = s->d_ctab; s->g.cbeg = s->d_cbeg;
@@ -540,11 +531,8 @@ LayeredQcState *layered_qc_create(const ldpc_code &c, int variant, int dtype, in
                  flooding ? "" : (s->records ? ", true" : ", false"), dtype == LDPC_F16 ? ", __half" : "");
         s->info.threads = s->threads; s->info.frames_per_wg = 1;
         return s;
-    } catch (...) { layered_qc_destroy(s); set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    } catch (...) { delete s; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
 }
-
-void layered_qc_set_timer(LayeredQcState *s, KernelTimer *t) { if (s) { s->timer = t; layered_lds_set_timer(s->lds, t); } }
-const LaunchInfo &layered_qc_launch_info(const LayeredQcState &s) { return s.info; }
 
 template <typename CT, int VARIANT>
 static int launch(LayeredQcState &s, hipStream_t st, QcLayerArgs &a) {
@@ -588,22 +576,20 @@ static int run(LayeredQcState &s, hipStream_t st, QcLayerArgs &a) {
     return s.variant == LDPC_MINSUM ? launch<float, LDPC_V_MINSUM>(s, st, a) : launch<float, LDPC_V_TANH>(s, st, a);
 }
 
-int layered_qc_decode(LayeredQcState &s, hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
-                      uint8_t *d_conv, double *d_final, double *d_trace) {
+int LayeredQcState::decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                           uint8_t *d_conv, double *d_final, double *d_trace) {
     QcLayerArgs a{};
     a.llr = d_llr; a.llr_fmt = llr_fmt; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final; a.trace = d_trace;
     a.batch = batch; a.max_iters = max_iters;
-    if (s.lds) return layered_lds_decode(*s.lds, st, max_iters, batch, d_llr, llr_fmt, d_bits, d_iters, d_conv, d_final, d_trace);
-    return run(s, st, a);
+    return run(*this, st, a);
 }
 
-int layered_qc_step(LayeredQcState &s, hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne, double *d_ne_out,
-                    double *d_lam_out, uint8_t *d_syn) {
+int LayeredQcState::step(hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne, double *d_ne_out,
+                         double *d_lam_out, uint8_t *d_syn) {
     QcLayerArgs a{};
     a.llr = d_orig; a.llr_fmt = LLR_F64; a.batch = batch; a.max_iters = 1; a.step_mode = 1;
     a.st_lam = d_lam; a.st_ne_in = d_ne; a.st_ne_out = d_ne_out; a.st_lam_out = d_lam_out; a.st_syn = d_syn;
-    if (s.lds) return set_error(LDPC_EUNSUPPORTED, "no teacher-forced step with fp16 lam storage (the record kernels keep no per-edge messages)");
-    return run(s, st, a);
+    return run(*this, st, a);
 }
 
 }  // namespace ldpc
