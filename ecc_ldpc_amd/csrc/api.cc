@@ -50,13 +50,15 @@ struct ldpc_ctx {
     hipStream_t stream = nullptr;
     ldpc::Backend *backend = nullptr;   // the context's decoder (select.cc make_backend)
     // staging of the host-pointer entry points, allocated on first use.  kSlots slots, each with its own stream
-    // running H2D -> decode -> D2H for one chunk, so that the copies of one chunk overlap the decode of another
-    // (fused paths are stateless on the device; the flood path keeps per-context BP state and uses slot 0 with
-    // the whole batch).  Measured on MI355X: a third slot changes nothing (65 536 jpl.4096 frames, pinned fp16
+    // running H2D -> decode -> D2H for one chunk, so that the copies of one chunk overlap the decode of another.
+    // The decodes themselves never overlap: each waits for `decoded`, recorded after the previous chunk's decode
+    // (backend.h: a backend's decode may keep device state across launches; the flood path uses slot 0 with the
+    // whole batch).  Measured on MI355X: a third slot changes nothing (65 536 jpl.4096 frames, pinned fp16
     // LLRs: 44.7 ms with 2 and with 3) -- the copies of both directions together run at ~25-32 GB/s, which is the
     // bound, not the pipeline depth.
     static constexpr int kSlots = 2;
     hipStream_t pstream[kSlots] = {};   // [0] aliases `stream`
+    hipEvent_t decoded = nullptr;       // (slots > 1) recorded after each chunk's decode; the next chunk's decode waits for it
     int slots = 0, chunk = 0;
     void *d_in[kSlots] = {};            // [chunk][N] float, double or half
     uint8_t *d_bits[kSlots] = {};       // [chunk][N]
@@ -377,6 +379,7 @@ void ldpc_ctx_destroy(ldpc_ctx *ctx) {
     for (int i = 1; i < ldpc_ctx::kSlots; i++) if (ctx->pstream[i]) hipStreamSynchronize(ctx->pstream[i]);
     for (int i = 0; i < ldpc_ctx::kSlots; i++) { hipFree(ctx->d_in[i]); hipFree(ctx->d_bits[i]); hipFree(ctx->d_iters[i]); hipFree(ctx->d_conv[i]); hipFree(ctx->d_final[i]); }
     for (int i = 1; i < ldpc_ctx::kSlots; i++) if (ctx->pstream[i]) hipStreamDestroy(ctx->pstream[i]);
+    if (ctx->decoded) (void)hipEventDestroy(ctx->decoded);
     if (ctx->h_small_in) (void)hipHostFree(ctx->h_small_in);
     if (ctx->h_small_out) (void)hipHostFree(ctx->h_small_out);
     (void)hipFree(ctx->d_small_out); (void)hipFree(ctx->d_small_in);
@@ -509,6 +512,7 @@ static int ensure_staging(ldpc_ctx *ctx, bool want_final) {
         ctx->pstream[0] = ctx->stream;
         hipError_t e = hipSuccess;
         for (int i = 1; i < ctx->slots && e == hipSuccess; i++) e = hipStreamCreateWithFlags(&ctx->pstream[i], hipStreamNonBlocking);
+        if (ctx->slots > 1 && e == hipSuccess) e = hipEventCreateWithFlags(&ctx->decoded, hipEventDisableTiming);
         for (int i = 0; i < ctx->slots && e == hipSuccess; i++) {
             const size_t c = (size_t)ctx->chunk;
             e = hipMalloc(&ctx->d_in[i], c * N * sizeof(double));
@@ -522,6 +526,7 @@ static int ensure_staging(ldpc_ctx *ctx, bool want_final) {
                 ctx->d_in[i] = nullptr; ctx->d_bits[i] = nullptr; ctx->d_iters[i] = nullptr; ctx->d_conv[i] = nullptr;
                 if (i > 0 && ctx->pstream[i]) { (void)hipStreamDestroy(ctx->pstream[i]); ctx->pstream[i] = nullptr; }
             }
+            if (ctx->decoded) { (void)hipEventDestroy(ctx->decoded); ctx->decoded = nullptr; }
             ctx->slots = 0;
             return set_error(LDPC_ENOMEM, "staging buffers for %d frames: %s", ctx->chunk, hipGetErrorString(e));
         }
@@ -539,6 +544,22 @@ static void *pinned_device_ptr(const void *p) {
     if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
     return at.devicePointer;
+}
+
+// one chunk's decode on slot stream `st`, enqueued after its H2D copy: it starts when the previous chunk's decode (on the other
+// slot's stream) has ended, so one context's decodes never run at once while copies still overlap them
+static int decode_chunk(ldpc_ctx *ctx, hipStream_t st, int max_iters, int batch, const void *d_llr, int fmt, uint8_t *d_bits,
+                        int32_t *d_iters, uint8_t *d_conv, double *d_final, double *d_trace) {
+    if (ctx->decoded) {
+        hipError_t e = hipStreamWaitEvent(st, ctx->decoded, 0);
+        if (e != hipSuccess) return set_error(LDPC_EHIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
+    }
+    int rc = decode_dev(ctx, st, max_iters, batch, d_llr, fmt, d_bits, d_iters, d_conv, d_final, d_trace);
+    if (rc == LDPC_OK && ctx->decoded) {
+        hipError_t e = hipEventRecord(ctx->decoded, st);
+        if (e != hipSuccess) return set_error(LDPC_EHIP, "hipEventRecord: %s", hipGetErrorString(e));
+    }
+    return rc;
 }
 
 static int decode_host(ldpc_ctx *ctx, int max_iters, int batch, const void *llr, int fmt, uint8_t *bits,
@@ -630,8 +651,8 @@ static int decode_host(ldpc_ctx *ctx, int max_iters, int batch, const void *llr,
         // stream order protects the slot: this copy is queued behind the slot's previous D2H
         e = hipMemcpyAsync(ctx->d_in[slot], (const char *)llr + (size_t)f0 * N * es, (size_t)nb * N * es, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) break;
-        rc = decode_dev(ctx, st, max_iters, nb, ctx->d_in[slot], fmt, ctx->d_bits[slot], ctx->d_iters[slot], ctx->d_conv[slot],
-                        final_lam ? ctx->d_final[slot] : nullptr, d_trace ? d_trace + (size_t)f0 * turns * N : nullptr);
+        rc = decode_chunk(ctx, st, max_iters, nb, ctx->d_in[slot], fmt, ctx->d_bits[slot], ctx->d_iters[slot], ctx->d_conv[slot],
+                          final_lam ? ctx->d_final[slot] : nullptr, d_trace ? d_trace + (size_t)f0 * turns * N : nullptr);
         if (rc != LDPC_OK) break;
         e = hipMemcpyAsync(bits + (size_t)f0 * N, ctx->d_bits[slot], (size_t)nb * N, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && iters) e = hipMemcpyAsync(iters + f0, ctx->d_iters[slot], sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, st);
@@ -729,7 +750,7 @@ int ldpc_decode_batch_packed(ldpc_ctx *ctx, int max_iters, int batch, const void
         hipStream_t st = ctx->pstream[slot];
         e = hipMemcpyAsync(ctx->d_in[slot], (const char *)llr + (size_t)f0 * N * es, (size_t)nb * N * es, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) break;
-        rc = decode_dev(ctx, st, max_iters, nb, ctx->d_in[slot], llr_f16 ? ldpc::LLR_F16 : ldpc::LLR_F32, ctx->d_bits[slot], ctx->d_iters[slot], ctx->d_conv[slot], nullptr, nullptr);
+        rc = decode_chunk(ctx, st, max_iters, nb, ctx->d_in[slot], llr_f16 ? ldpc::LLR_F16 : ldpc::LLR_F32, ctx->d_bits[slot], ctx->d_iters[slot], ctx->d_conv[slot], nullptr, nullptr);
         if (rc == LDPC_OK) rc = ldpc::pack_bits(st, ctx->d_bits[slot], ctx->d_packed + (size_t)f0 * PB, nb, (int)N);
         if (rc != LDPC_OK) break;
         e = hipMemcpyAsync(packed + (size_t)f0 * PB, ctx->d_packed + (size_t)f0 * PB, (size_t)nb * PB, hipMemcpyDeviceToHost, st);

@@ -1,5 +1,10 @@
 // backend.h -- the one decoder a context owns (host side).  Every kernel family implements this interface in its own
 // translation unit and owns its own buffers; make_backend (select.cc) decides which family and instance a context gets.
+//
+// One backend's decode never runs twice at once on the device: the host-pointer entry points (api.cc decode_host) start each
+// chunk's decode after the previous chunk's has ended, whichever slot stream it is on, and device-pointer callers order their
+// streams (include/ldpc_hip.h).  So a backend may keep mutable device state across launches: fused_csr.hip's and
+// layered_lds.hip's work counters, the HBM state of flood.hip and layered_qc.hip.
 #pragma once
 #include "internal.h"
 

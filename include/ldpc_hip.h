@@ -196,7 +196,8 @@ int ldpc_decode_batch_f64(ldpc_ctx *ctx, int max_iters, int batch, const double 
  * float32; d_bits [batch][N] bytes; d_iters, d_converged may be NULL.  Work is enqueued on
  * `stream` (a hipStream_t) and NOT synchronised.  NULL = the context's OWN stream, which is
  * non-blocking: it does not order against the default (null) stream, so a caller that produces
- * d_llr on another stream must pass that stream here (or synchronise first). */
+ * d_llr on another stream must pass that stream here (or synchronise first).  A context decodes one
+ * batch at a time: two calls on one context with different streams must be ordered by the caller. */
 int ldpc_decode_batch_dev(ldpc_ctx *ctx, int max_iters, int batch, const float *d_llr,
                           uint8_t *d_bits, int32_t *d_iters, uint8_t *d_converged, void *stream);
 /* fp16 channel LLRs (IEEE binary16 bit patterns; BASELINE.json configs[3] "min-sum fp16 LLRs"): the same two
