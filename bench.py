@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decoded information Mbit/s of the LDPC BP decode path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   N > 1, either way: `python bench.py --gpus N ...` starts its own N child ranks (ecc_ldpc_amd/launch.py; the parent never
   touches the GPU), or `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`
 
@@ -10,7 +10,10 @@ that are already resident in HBM.  Workload at every N: BASELINE.json's metric c
 codes/jpl.4096.4.5, rate 4/5 puncturing, min-sum, 50 iterations, Eb/N0 = 2 dB -- with a fixed
 per-GPU batch (weak scaling: frames are independent, each rank generates its own frame-id range
 from the counter-based RNG; the only exchange is one RCCL all-reduce of the error tallies).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline figure needs: set up, warm up, time the
+steps, write --dump-outputs, print.  --full adds, after the timed steps, everything else the benchmark measures or checks:
+the roofline objects (untimed passes, rocprofv3 child runs), proof_of_work, cpu_baseline, and the other precisions,
+schedules and BASELINE configurations as labelled measurements.
 """
 from __future__ import annotations
 
@@ -44,6 +47,9 @@ def main():
     ap.add_argument("--batch", type=int, default=65536, help="frames per GPU per step")
     ap.add_argument("--path", default="auto", choices=["auto", "flood", "fused"])
     ap.add_argument("--schedule", default="flooding", choices=["flooding", "layered"], help="layered: extension (BASELINE configs[4])")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check what the headline figure does not need "
+                    "(roofline, roofline_hbm_model, proof_of_work, cpu_baseline, fp16_packed, layered_extension, long_code_layered, configs*); "
+                    "--cpu-seconds, --fp16-leg, --live-traffic and --proof trim such a run and do nothing without it")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the cpu_baseline sample (0 = skip)")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EEDC0DE)
     ap.add_argument("--fp16-leg", type=int, default=1, help="0: skip the extra, separately labelled measurements of the same workload (packed-fp16 decoder; layered schedule f32 / packed fp16) "
@@ -169,15 +175,20 @@ def main():
     frames_total = world * args.steps * B
     value = frames_total * k / elapsed / 1e6
 
-    # ---- iterations the timed steps really ran (early exit): one untimed pass per distinct input buffer
-    sum_iters_buf = []
-    for i in range(nbuf):
-        step(i)
-        torch.cuda.synchronize()
-        sum_iters_buf.append(int(iters_t.sum().item()))
-    turns_timed = sum(sum_iters_buf[(args.warmup + i) % nbuf] for i in range(args.steps))   # frame-turns of this rank
-    roofline, roofline_hbm = rooflines(args, dec, B, Eg, N, n_tx, k, s_bytes, launches, kernel_ms, turns_timed, live=(rank == 0))
-    pow_obj = proof_of_work(args, E, ecc, dec, sim, llr[0], msg[0], bits, iters_t, conv_t, sp, f16) if (rank == 0 and args.proof) else None
+    full = {}       # what --full adds to the line, in the line's order
+    if args.full:
+        # ---- iterations the timed steps really ran (early exit): one untimed pass per distinct input buffer
+        sum_iters_buf = []
+        for i in range(nbuf):
+            step(i)
+            torch.cuda.synchronize()
+            sum_iters_buf.append(int(iters_t.sum().item()))
+        turns_timed = sum(sum_iters_buf[(args.warmup + i) % nbuf] for i in range(args.steps))   # frame-turns of this rank
+        roofline, roofline_hbm = rooflines(args, dec, B, Eg, N, n_tx, k, s_bytes, launches, kernel_ms, turns_timed, live=(rank == 0))
+        full["roofline"] = roofline
+        if roofline_hbm:
+            full["roofline_hbm_model"] = roofline_hbm
+        full["proof_of_work"] = proof_of_work(args, E, ecc, dec, sim, llr[0], msg[0], bits, iters_t, conv_t, sp, f16) if (rank == 0 and args.proof) else None
 
     out = None
     if rank == 0:
@@ -194,16 +205,14 @@ def main():
             "ranks_seen": int(ones.item()), "per_rank_ms_per_step": [round(s / args.steps * 1e3, 3) for s in rank_seconds],
             "launcher": os.environ.get("LDPC_BENCH_LAUNCHER", "external" if "WORLD_SIZE" in os.environ else "none"),
             "collective_backend": (dist.get_backend() if dist is not None else None),
-            "roofline": roofline,
-            **({"roofline_hbm_model": roofline_hbm} if roofline_hbm else {}),
-            "proof_of_work": pow_obj,
+            **full,
             "hbm_roofline_mbit_s": round(HBM_PEAK_GBS * 1e9 / B_cw * k / 1e6, 1),
             "frac_of_hbm_roofline_throughput": round(value / world / (HBM_PEAK_GBS * 1e9 / B_cw * k / 1e6), 4),
             "ber": t[2] / max(t[0] * k, 1), "fer": t[1] / max(t[0], 1), "mean_iters": t[3] / max(t[0], 1),
         }
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(args, ecc, llr[0], value)
-        if world == 1 and args.dtype == "f32" and args.variant == "minsum" and args.schedule == "flooding" and args.path == "auto" and args.fp16_leg:
+        if args.full and world == 1 and args.dtype == "f32" and args.variant == "minsum" and args.schedule == "flooding" and args.path == "auto" and args.fp16_leg:
             out["fp16_packed"] = fp16_packed_leg(args, E, torch, dev, sp, B)
             # the row-layered schedule (an extension: the reference has flooding only) on the same code, on-chip, f32 and packed fp16,
             # at the headline Eb/N0 and in the waterfall -- labelled measurements next to `value`, never instead of it
@@ -564,7 +573,7 @@ def live_counters(args, dec, B):
         return None                # this process is being profiled itself: no profiler inside a profiler
     child = [sys.executable or "python3", os.path.abspath(__file__), "--gpus", "1", "--steps", "2", "--warmup", "1", "--code", args.code, "--rate", args.rate,
              "--variant", args.variant, "--dtype", args.dtype, "--iters", str(args.iters), "--ebn0", str(args.ebn0), "--batch", str(B), "--path", args.path,
-             "--schedule", args.schedule, "--cpu-seconds", "0", "--seed", hex(args.seed), "--fp16-leg", "0", "--proof", "0", "--live-traffic", "0"]
+             "--schedule", args.schedule, "--full", "--cpu-seconds", "0", "--seed", hex(args.seed), "--fp16-leg", "0", "--proof", "0", "--live-traffic", "0"]
     env = dict(os.environ, LDPC_BENCH_CHILD="1", TMPDIR="/tmp")
     for k in list(env):              # a child is a plain one-process run, whatever launched this one
         if k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "GROUP_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "ROLE_RANK",

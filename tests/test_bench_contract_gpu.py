@@ -1,5 +1,5 @@
-"""GPU: bench.py's output contract -- ONE JSON line with the driver's keys, the roofline and cpu_baseline objects,
-for the headline workload at a small batch and for two ranks sharing the GPU in rehearsal mode."""
+"""GPU: bench.py's output contract -- ONE JSON line with the driver's keys; with --full also the roofline and cpu_baseline
+objects; for the headline workload at a small batch and for two ranks sharing the GPU in rehearsal mode."""
 import json
 import os
 import subprocess
@@ -12,7 +12,9 @@ from tests.helpers import ROOT
 pytestmark = pytest.mark.gpu
 
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-        "dtype", "data", "config", "roofline"}
+        "dtype", "data", "config"}
+FULL_ONLY = {"roofline", "roofline_hbm_model", "proof_of_work", "cpu_baseline", "fp16_packed", "layered_extension", "long_code_layered",
+             "configs0_moon_tanh", "configs1_jpl1024_minsum", "configs2_mackay_tanh_sweep"}
 
 
 def _run(cmd, env=None, only_line=True, timeout=300):
@@ -29,8 +31,8 @@ def _run(cmd, env=None, only_line=True, timeout=300):
 
 
 def test_one_json_line_with_roofline_and_cpu_baseline():
-    d = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "2048", "--cpu-seconds", "1"])
-    assert KEYS <= set(d) and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    d = _run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--batch", "2048", "--cpu-seconds", "1"])
+    assert KEYS | FULL_ONLY <= set(d) and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
     assert d["unit"] == "Mbit/s" and d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert d["dtype"] == "f32" and d["data"] == "synthetic" and "workload" in d["config"] and "model" not in d["config"]
     # on-chip kernel: VALU-issue roofline from the build's own assembly x the iterations really run, 0 < frac <= 1
@@ -79,12 +81,12 @@ def test_two_ranks_rehearsal_aggregates_over_ranks():
 
 def test_bench_starts_its_own_ranks():
     """The driver's command shape for N > 1 WITHOUT a launcher: `python3 bench.py --gpus 2 --steps 2 --warmup 1` (the headline
-    workload at its full batch).  The parent never touches the GPU; two child ranks share this box's one GPU (rehearsal:
-    gloo instead of RCCL, which refuses two ranks on one device).  One JSON line, both ranks took part in the collectives."""
+    workload at its full batch), with --full so that rank 0's proof_of_work runs too.  The parent never touches the GPU; two child
+    ranks share this box's one GPU (rehearsal: gloo instead of RCCL, which refuses two ranks on one device).  One JSON line, both ranks took part in the collectives."""
     env = {"LDPC_BENCH_REHEARSE": "1"}
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         os.environ.pop(k, None)
-    d = _run(["python3", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1"], env=env, only_line=False, timeout=900)
+    d = _run(["python3", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], env=env, only_line=False, timeout=900)
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and len(d["per_rank_ms_per_step"]) == 2 and d["launcher"] == "self"
     assert d["steps"] == 2 and d["warmup"] == 1 and d["config"]["batch_per_gpu"] == 65536 and "cpu_baseline" not in d
     assert max(d["per_rank_ms_per_step"]) == d["ms_per_step"]
@@ -133,7 +135,7 @@ def test_bench_starts_its_own_ranks_on_a_fresh_jit_cache(tmp_path):
 
 def test_early_exit_is_priced_by_the_iterations_run():
     """4 dB: frames converge after a few turns; both roofline objects must price what ran, not max_iters."""
-    d = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "2048", "--cpu-seconds", "0", "--ebn0", "4"])
+    d = _run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--batch", "2048", "--cpu-seconds", "0", "--ebn0", "4"])
     r, h = d["roofline"], d["roofline_hbm_model"]
     assert d["metric"].endswith("Eb/N0=4 dB") and d["mean_iters"] < 10
     assert r["frame_turns_timed"] < 2 * 2048 * 10 and 0 < r["frac"] <= 1.0
@@ -141,11 +143,11 @@ def test_early_exit_is_priced_by_the_iterations_run():
 
 
 def test_flood_path_reports_an_hbm_roofline():
-    d = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "2048", "--cpu-seconds", "0", "--path", "flood"])
+    d = _run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--batch", "2048", "--cpu-seconds", "0", "--path", "flood"])
     r = d["roofline"]
     # QC code: the frame-per-workgroup flooding kernel (one launch per batch); LDPC_FLOOD_QC=0 gives the batch-major pair
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and "flood_qc_kernel" in r["kernel"] and 0 < r["frac"] <= 1.0 and d["proof_of_work"]["ok"]
-    d2 = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "2048", "--cpu-seconds", "0", "--path", "flood"],
+    d2 = _run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--batch", "2048", "--cpu-seconds", "0", "--path", "flood"],
               env={"LDPC_FLOOD_QC": "0"})
     assert "flood_cn" in d2["roofline"]["kernel"] and 0 < d2["roofline"]["frac"] <= 1.0 and d2["proof_of_work"]["ok"]
 
@@ -154,7 +156,7 @@ def test_rccl_collectives_run_with_one_rank():
     """The N > 1 path's process-group setup and its two collectives (all-reduce of the tallies, max of the elapsed time) over
     the real RCCL backend, with a single rank on this 1-GPU box: next to the library's own HIP client in the process."""
     d = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-              "--master-port", "29534", "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2048", "--cpu-seconds", "0"],
+              "--master-port", "29534", "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2048", "--cpu-seconds", "0", "--full"],
              env={"LDPC_BENCH_FORCE_DIST": "1"}, only_line=False)
     assert d["n_gpus"] == 1 and "rehearsal" not in d and d["proof_of_work"]["ok"]
     assert abs(d["value"] - 2 * 2048 * 4096 / (d["ms_per_step"] * 2e-3) / 1e6) / d["value"] < 0.02
@@ -162,20 +164,25 @@ def test_rccl_collectives_run_with_one_rank():
 
 def test_dump_outputs_are_the_last_timed_step_and_repeat_exactly(tmp_path):
     """--dump-outputs DIR: the last timed step's hard bits, iterations and converged flags as float32 .npy files (2 048 frames fit
-    in the 64 MB bound whole), identical in a second run with the same arguments; --steps sets the timed launches.  4 dB: most
-    frames converge, after differing numbers of turns."""
+    in the 64 MB bound whole), identical in a second run with the same arguments plus --full; a plain run's line holds none of what
+    --full adds; --steps sets the timed launches.  4 dB: most frames converge, after differing numbers of turns."""
     import numpy as np
     from tests.helpers import load
-    args = ["--steps", "3", "--warmup", "1", "--batch", "2048", "--ebn0", "4", "--cpu-seconds", "0", "--fp16-leg", "0", "--proof", "0", "--live-traffic", "0"]
+    args = ["--steps", "3", "--warmup", "1", "--batch", "2048", "--ebn0", "4"]
     runs = []
-    for name in ("a", "b"):
-        d = _run([sys.executable, "bench.py", "--dump-outputs", str(tmp_path / name)] + args)
-        assert d["steps"] == 3 and d["roofline"]["launches"] == 3 and d["ms_per_step"] > 0
+    for name, more in (("a", []), ("b", ["--full", "--cpu-seconds", "0", "--fp16-leg", "0", "--proof", "0", "--live-traffic", "0"])):
+        d = _run([sys.executable, "bench.py", "--dump-outputs", str(tmp_path / name)] + args + more)
+        assert KEYS <= set(d) and d["steps"] == 3 and d["ms_per_step"] > 0
+        if more:
+            assert d["roofline"]["launches"] == 3
+        else:
+            assert not FULL_ONLY & set(d), FULL_ONLY & set(d)
         files = sorted(os.listdir(tmp_path / name))
         assert files == ["bits.npy", "bits_frames.npy", "converged.npy", "iters.npy"]
         assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64_000_000
         runs.append((d, {f[:-4]: np.load(tmp_path / name / f) for f in files}))
-    (d, a), (_, b) = runs
+    (d, a), (d_b, b) = runs
+    assert (d["ber"], d["fer"], d["mean_iters"]) == (d_b["ber"], d_b["fer"], d_b["mean_iters"])
     for k in a:
         assert a[k].dtype == (np.float64 if k == "bits_frames" else np.float32) and np.array_equal(a[k], b[k]), k
     H = load("jpl.4096.4.5").H.astype(np.float32)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs bench.py over the BASELINE.json configurations that fit one GPU; one JSON line each -> gpurun_out/bench_matrix.jsonl
 mkdir -p gpurun_out; out=gpurun_out/bench_matrix.jsonl; : > $out
-run() { echo "# $*" >&2; python bench.py --cpu-seconds 0 --fp16-leg 0 "$@" 2>/dev/null | tail -1 >> $out; }
+run() { echo "# $*" >&2; python bench.py --full --cpu-seconds 0 --fp16-leg 0 "$@" 2>/dev/null | tail -1 >> $out; }
 run --steps 6 --warmup 2                                              # headline: jpl.4096 min-sum f32 (fused)
 LDPC_HIP_PATH=flood run --steps 3 --warmup 1 --batch 16384            # same on the generic flood path
 run --steps 6 --warmup 2 --dtype f16pk                                # configs[3]: fp16 LLRs AND arithmetic, two frames per lane (LDPC_F16PK)
