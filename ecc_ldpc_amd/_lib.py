@@ -29,7 +29,7 @@ class CtxConfig(C.Structure):   # ldpc_ctx_config
 ABI_SYMBOLS = [
     "ldpc_init", "ldpc_shutdown", "ldpc_current_device", "ldpc_ctx_create_on", "ldpc_sim_create_on", "ldpc_ctx_create_cfg", "ldpc_ctx_schedule", "ldpc_ctx_code", "ldpc_ctx_max_batch", "ldpc_ctx_device",
     "ldpc_batcher_create", "ldpc_batcher_destroy", "ldpc_batcher_decode_one", "ldpc_batcher_stats",
-    "ldpc_ecc_create_replicas", "ldpc_ecc_replicas", "ldpc_ecc_ctx_at", "ldpc_ecc_sim_at", "ldpc_ecc_decode_on", "ldpc_ecc_set_coalescing", "ldpc_ecc_coalescing_stats", "ldpc_code_set_layers", "ldpc_code_layers", "ldpc_qc_layer_order", "ldpc_last_error", "ldpc_last_error_code", "ldpc_abi_version", "ldpc_device_count",
+    "ldpc_ecc_create_replicas", "ldpc_ecc_replicas", "ldpc_ecc_ctx_at", "ldpc_ecc_sim_at", "ldpc_ecc_decode_on", "ldpc_ecc_set_coalescing", "ldpc_ecc_coalescing_stats", "ldpc_code_set_layers", "ldpc_code_layers", "ldpc_qc_layer_order", "ldpc_csr_layer_order", "ldpc_last_error", "ldpc_last_error_code", "ldpc_abi_version", "ldpc_device_count",
     "ldpc_code_create_qc", "ldpc_code_create_csr", "ldpc_code_destroy", "ldpc_code_dims", "ldpc_code_csr",
     "ldpc_ctx_create", "ldpc_ctx_create_ex", "ldpc_ctx_destroy", "ldpc_ctx_path", "ldpc_ctx_synchronize",
     "ldpc_decode_one", "ldpc_decode_batch", "ldpc_decode_batch_f64", "ldpc_decode_batch_dev",
@@ -163,6 +163,7 @@ def lib():
     L.ldpc_ctx_schedule.argtypes = [vp]
     L.ldpc_code_set_layers.argtypes = [vp, C.c_int, i32p]
     L.ldpc_qc_layer_order.argtypes = [C.c_int, C.c_int, i32p, C.c_int, i32p]
+    L.ldpc_csr_layer_order.argtypes = [C.c_int, C.c_int, i32p, i32p, C.c_int, i32p, i32p]
     L.ldpc_code_layers.argtypes = [vp, ip, i32p]
     L.ldpc_sim_create_on.restype = vp
     L.ldpc_sim_create_on.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_int]
@@ -342,6 +343,31 @@ class Code:
         if n < 0:
             raise LdpcError(lib().ldpc_last_error_code(), last_error())
         return perm, n
+
+    @staticmethod
+    def csr_layer_order(row_ptr, col_idx, N, max_rows=0):
+        """-> (perm, layer_ptr): an order of the rows of any H in which consecutive rows form few column-disjoint layers
+        (ldpc_csr_layer_order; the rows perm of H are the matrix to hand to from_csr, layer_ptr what its set_layers takes)"""
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        ci = np.ascontiguousarray(col_idx, dtype=np.int32)
+        M = max(len(rp) - 1, 0)
+        perm = np.zeros(max(M, 1), np.int32)
+        lp = np.zeros(M + 1, np.int32)
+        n = lib().ldpc_csr_layer_order(M, int(N), ptr(rp, C.c_int32), ptr(ci, C.c_int32), int(max_rows), ptr(perm, C.c_int32), ptr(lp, C.c_int32))
+        if n < 0:
+            raise LdpcError(lib().ldpc_last_error_code(), last_error())
+        return perm[:M], lp[: n + 1]
+
+    @staticmethod
+    def permute_rows(row_ptr, col_idx, perm):
+        """-> (row_ptr, col_idx) of H with its rows in the order perm (perm[i] = the row put at place i)"""
+        rp = np.asarray(row_ptr, np.int64)
+        ci = np.asarray(col_idx, np.int32)
+        deg = np.diff(rp)[perm]
+        nrp = np.zeros(len(perm) + 1, np.int32)
+        nrp[1:] = np.cumsum(deg)
+        nci = np.concatenate([ci[rp[m]:rp[m + 1]] for m in perm]).astype(np.int32) if len(perm) else ci[:0]
+        return nrp, nci
 
     @classmethod
     def from_csr(cls, row_ptr, col_idx, N):

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <mutex>
 #include <new>
+#include <set>
 
 #include "backend.h"
 #include "jit.h"
@@ -309,6 +310,39 @@ int ldpc_qc_layer_order(int block_rows, int block_cols, const int32_t *offsets, 
         int n = 0, full = 0;
         for (auto &r : runs) { if ((int)r.size() == run) full++; for (int br : r) perm[n++] = br; }
         return full;
+    } catch (...) { return set_error(LDPC_ENOMEM, "out of host memory"); }
+}
+
+int ldpc_csr_layer_order(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int max_rows, int32_t *perm, int32_t *layer_ptr) {
+    if (M <= 0 || N <= 0 || !row_ptr || !col_idx || max_rows < 0 || !perm || !layer_ptr || row_ptr[0] != 0)
+        return set_error(LDPC_EINVAL, "ldpc_csr_layer_order: bad arguments (M=%d N=%d max_rows=%d)", M, N, max_rows);
+    for (int m = 0; m < M; m++) {
+        if (row_ptr[m + 1] < row_ptr[m]) return set_error(LDPC_EINVAL, "ldpc_csr_layer_order: row_ptr decreases at row %d", m);
+        for (int q = row_ptr[m]; q < row_ptr[m + 1]; q++)
+            if (col_idx[q] < 0 || col_idx[q] >= N || (q > row_ptr[m] && col_idx[q] <= col_idx[q - 1]))
+                return set_error(LDPC_EINVAL, "ldpc_csr_layer_order: row %d: columns not strictly ascending inside [0, %d)", m, N);
+    }
+    try {
+        // first fit in file order: each row joins the lowest layer that holds none of its columns and has room
+        std::vector<std::vector<int32_t>> col_layers((size_t)N);   // per column: the layers that already hold it
+        std::vector<int32_t> layer_of((size_t)M), size, stamp;
+        std::set<int> open;                                       // layers with room (all of them when max_rows = 0)
+        for (int m = 0; m < M; m++) {
+            for (int q = row_ptr[m]; q < row_ptr[m + 1]; q++)
+                for (int l : col_layers[col_idx[q]]) stamp[l] = m;
+            int l = (int)size.size();
+            for (int o : open) if (stamp[o] != m) { l = o; break; }
+            if (l == (int)size.size()) { size.push_back(0); stamp.push_back(-1); open.insert(l); }
+            layer_of[m] = l;
+            if (++size[l] == max_rows) open.erase(l);
+            for (int q = row_ptr[m]; q < row_ptr[m + 1]; q++) col_layers[col_idx[q]].push_back(l);
+        }
+        const int n = (int)size.size();
+        layer_ptr[0] = 0;
+        for (int l = 0; l < n; l++) layer_ptr[l + 1] = layer_ptr[l] + size[l];
+        std::vector<int32_t> at(layer_ptr, layer_ptr + n);
+        for (int m = 0; m < M; m++) perm[at[layer_of[m]]++] = m;   // rows of a layer in file order
+        return n;
     } catch (...) { return set_error(LDPC_ENOMEM, "out of host memory"); }
 }
 

@@ -1,0 +1,441 @@
+// layered_csr.hip -- row-layered min-sum for ANY parity-check matrix: lam ON-CHIP as fp16, row records streamed from HBM.
+//
+// layered_lds.hip carried over from quasi-cyclic codes to CSR graphs.  Same arithmetic, same roundings (f32 arithmetic and records,
+// every lam write saturated and rounded to binary16 -- specification oracle/emulate_f16.py decode_minsum_f16_layered, rows in
+// ascending order, reproduced bit for bit), same row records {3/4 min1, 3/4 min2, signs | arg-min} in a per-workgroup scratch area,
+// same persistent workgroups taking frames from a counter.  What differs is where a row's edges come from:
+//   * a code-constant COLUMN TABLE in device memory, shared by all workgroups (L2-resident), 16-bit column indices laid out
+//     [slab][edge k][thread]: a wave's k-th gather addresses are one contiguous 128-byte load;
+//   * STEPS instead of block rows: each maximal run of consecutive layers (ldpc_code_set_layers; default one row per layer) that are
+//     pairwise column-disjoint is one barrier step -- its rows touch distinct lam cells, so running them together gives what running
+//     them one after the other gives.  A step's rows are sorted by weight (heaviest first) and cut into SLABS of T rows, thread t
+//     taking row t of every slab of the step; rows lighter than their wave's heaviest are padded with neutral edges (index 0xFFFF:
+//     no lam read or write, no part in min, sign, parity or flip).
+// LDS: the frame's lam (2 N bytes) + 32 bytes of control words; the short codes get several workgroups per CU.
+// Algorithmic HBM bytes per frame: sweeps * 24 M (the first sweep writes only) + the LLRs in + the bits out; the column table
+// (2 bytes per padded edge) is read by every workgroup every sweep and stays in L2.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <numeric>
+#include <vector>
+
+#include "layered_qc.h"
+#include "ldpc_math.h"
+
+namespace ldpc {
+
+typedef const __attribute__((address_space(4))) int32_t *ctab_t;   // graph tables: scalar loads (never written by the kernel)
+
+struct CsrRec { float c1, c2; uint32_t meta; };   // meta: bit (deg-1-k) = sign bit of the message on edge k; bits 27..31 = an arg-min edge
+
+constexpr uint16_t kNoEdge = 0xFFFF;
+
+struct CsrLayDev {
+    int N, T, nstep;
+    const uint16_t *cols;       // per slab, [edge k < slab weight][thread]: column index, kNoEdge past the row's weight
+    const int32_t *slab;        // [nslab][2]: {first entry in cols, slab weight (its heaviest row)}
+    const int32_t *wdeg;        // [nslab][T / 64]: the heaviest row of each wave of the slab, | 0x100 when all 64 rows of the wave have that weight
+    const int32_t *step_ptr;    // [nstep + 1]: the slabs of each barrier step
+};
+
+struct CsrLayArgs {
+    const void *llr; int llr_fmt;   // [batch][N]
+    uint8_t *bits; int32_t *iters; uint8_t *conv;
+    double *final_lam;              // may be null
+    int batch, max_iters;
+    int *work_counter;              // next frame to take = gridDim.x + atomicAdd(work_counter, 1)
+};
+
+namespace {   // (the device helpers below are layered_lds.hip's, kept local to this file)
+
+__device__ __forceinline__ void lds_barrier() {     // LDS traffic only: global loads / stores stay in flight across it
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+__device__ __forceinline__ _Float16 sat16(float v) { return (_Float16)__builtin_amdgcn_fmed3f(v, -65504.f, 65504.f); }
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+template <int FMT> __device__ __forceinline__ void load_llr8(const void *base, size_t i, half8 &h) {
+    if constexpr (FMT == LLR_F64) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) h[k] = sat16((float)reinterpret_cast<const double *>(base)[i + k]);
+    } else if constexpr (FMT == LLR_F16) {
+        const half8 v = *reinterpret_cast<const half8 *>(reinterpret_cast<const _Float16 *>(base) + i);
+#pragma unroll
+        for (int k = 0; k < 8; k++) h[k] = sat16((float)v[k]);
+    } else {
+        const float4 a = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + i);
+        const float4 b = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + i + 4);
+        h[0] = sat16(a.x); h[1] = sat16(a.y); h[2] = sat16(a.z); h[3] = sat16(a.w);
+        h[4] = sat16(b.x); h[5] = sat16(b.y); h[6] = sat16(b.z); h[7] = sat16(b.w);
+    }
+}
+
+typedef __attribute__((address_space(3))) _Float16 *lds_half_t;
+__device__ __forceinline__ lds_half_t lds_cell(uint32_t byte_addr) { return (lds_half_t)(uintptr_t)byte_addr; }
+
+// one check row: layered_lds.hip lds_row with the row's weight per LANE (deg <= D; EXACT: every lane's row has weight D).  cp: this
+// lane's entry of edge 0 in the column table, edge k at cp[k T]; wd: the heaviest row of the wave (entries past it are not read).
+template <int D, bool EXACT, bool FIRST>
+__device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint32_t lam0, const CsrRec &in, CsrRec &out, bool &odd, bool &flip) {
+    uint32_t ad[D];
+    float l[D], t[D];
+    int deg = EXACT ? D : 0;
+#pragma unroll
+    for (int k = 0; k < D; k++) {
+        const uint32_t c = (EXACT || k < wd) ? (uint32_t)cp[(size_t)k * T] : (uint32_t)kNoEdge;
+        const bool v = EXACT || c != kNoEdge;       // (the neutral entries are the last ones of a row)
+        if constexpr (!EXACT) deg += v ? 1 : 0;
+        ad[k] = lam0 + 2u * (v ? c : 0u);
+    }
+#pragma unroll
+    for (int k = 0; k < D; k++) l[k] = (float)*lds_cell(ad[k]);
+    bool par = false;
+    uint32_t X = 0;
+    float m1 = INFINITY, m2 = INFINITY;
+    const uint32_t oidx = in.meta >> 27;
+#pragma unroll
+    for (int k = 0; k < D; k++) {
+        if (EXACT || k < deg) {
+            par ^= hard(l[k]);
+            float old = 0.f;
+            if constexpr (!FIRST) {
+                const uint32_t mag = __float_as_uint(((uint32_t)k == oidx) ? in.c2 : in.c1);
+                old = __uint_as_float(mag | ((in.meta << (32 - deg + k)) & 0x80000000u));
+            }
+            t[k] = l[k] - old;
+            X ^= __float_as_uint(t[k]);
+            const float a = fabsf(t[k]);
+            m2 = __builtin_amdgcn_fmed3f(m1, m2, a);
+            m1 = fminf(m1, a);
+        } else t[k] = INFINITY;
+    }
+    odd |= par;
+    const float n1 = 0.75f * m1, n2 = 0.75f * m2;      // |(-3/4) * acc|: the one rounding of Min.hs:78
+    // sign bit of message k = (deg odd) ^ (xor of all sign bits of t) ^ (sign bit of t_k)   (cn_update_padded)
+    const uint32_t fl = (X ^ ((deg & 1) ? 0x80000000u : 0u)) & 0x80000000u;
+    uint32_t c1 = __float_as_uint(n1) ^ fl, c2 = __float_as_uint(n2) ^ fl;
+    uint32_t tsig = 0, nidx = 0;                        // tsig: the sign bits of t, edge k at bit deg - 1 - k
+#pragma unroll
+    for (int k = 0; k < D; k++) {
+        if (EXACT || k < deg) {
+            const bool ismin = fabsf(t[k]) == m1;           // ties: n2 == n1, either answer gives the same message
+            const uint32_t nmb = __builtin_amdgcn_bitop3_b32(ismin ? c2 : c1, __float_as_uint(t[k]), 0x80000000u, 0x78);   // a ^ (b & c)
+            nidx = ismin ? (uint32_t)k : nidx;
+            tsig = __builtin_amdgcn_alignbit(tsig, __float_as_uint(t[k]), 31);
+            const _Float16 nw = sat16(t[k] + __uint_as_float(nmb));
+            flip |= (nw > (_Float16)0) != hard(l[k]);
+            *lds_cell(ad[k]) = nw;
+        }
+    }
+    const uint32_t nsig = tsig ^ (fl ? ((1u << deg) - 1u) : 0u);
+    out.c1 = n1; out.c2 = n2; out.meta = nsig | (nidx << 27);
+}
+
+// the instance for a wave: wd = its heaviest row, uni = all its rows have that weight
+template <int DCLASS, bool FIRST>
+__device__ __forceinline__ void csr_row_at(const uint16_t *cp, int T, int wd, bool uni, uint32_t lam0, const CsrRec &in, CsrRec &out, bool &odd, bool &flip) {
+    if (uni) {
+        switch (wd) {
+            case 2: csr_row<2, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 3: csr_row<3, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 4: csr_row<4, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 5: csr_row<5, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 6: csr_row<6, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 7: csr_row<7, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 8: csr_row<8, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            default: break;
+        }
+    }
+    if (wd <= 0) { out = in; return; }                  // (a wave of idle lanes or empty rows)
+    if (wd <= 4) { csr_row<4, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
+    if (wd <= 8) { csr_row<8, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
+    if constexpr (DCLASS >= 20) {
+        if (wd <= 12) { csr_row<12, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
+        if (wd <= 20) { csr_row<20, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
+    }
+    if constexpr (DCLASS >= 32) csr_row<27, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip);
+}
+
+}  // namespace
+
+// block = T threads (a multiple of 64, at most csr_max_threads); grid = resident workgroups (persistent).  Rows above weight 20 keep
+// up to 27 addresses, LLRs and differences per lane: that instance is built for 512 threads (256 registers per lane, no spill).
+constexpr int csr_max_threads(int dclass) { return dclass > 20 ? 512 : 1024; }
+template <int DCLASS>
+__global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(CsrLayDev g, CsrRec *rec_all, CsrLayArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    _Float16 *lam = reinterpret_cast<_Float16 *>(smem);
+    // [0] next frame; [1..3] "sweep n moved" at 1 + n % 3 (cleared by thread 0 two sweeps before its use); [4] "the channel's hard
+    // decisions are not a codeword"
+    int *ctl = reinterpret_cast<int *>(smem + (((size_t)g.N * 2 + 15) & ~(size_t)15));
+    const int T = g.T, tid = threadIdx.x;
+    const int W = T >> 6, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nslab = ((ctab_t)g.step_ptr)[g.nstep];
+    const uint32_t lam0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem;   // LDS byte address of lam
+    CsrRec *const rec = rec_all + (size_t)blockIdx.x * nslab * T + tid;     // this thread's record of slab s: rec[s T]
+    int frame = blockIdx.x;
+    while (frame < A.batch) {
+        const size_t fN = (size_t)frame * g.N;
+        // ---- lam <- channel LLRs, as stored: saturated, rounded to fp16 (eight per lane and request when the frame is 16-byte aligned)
+        const bool wide = (g.N & 7) == 0 && A.llr_fmt != LLR_F64 && !A.final_lam &&
+                          (((uintptr_t)A.llr + fN * (A.llr_fmt == LLR_F16 ? 2 : 4)) & 15) == 0 && (((uintptr_t)A.bits + fN) & 7) == 0;   // (uniform)
+        if (wide) {
+            with_llr_format(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 4
+                for (int i = tid * 8; i < g.N; i += T * 8) {
+                    half8 h;
+                    load_llr8<decltype(fmt)::value>(A.llr, fN + i, h);
+                    *reinterpret_cast<half8 *>(lam + i) = h;
+                }
+            });
+        } else {
+            with_llr_format(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 8
+                for (int i = tid; i < g.N; i += T) lam[i] = sat16(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
+            });
+        }
+        if (tid == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; ctl[4] = 0; }
+        lds_barrier();
+        bool conv = false;
+        int n = 0;
+        {   // syndrome of the hard decisions before the first sweep (reads only: no barrier between steps)
+            bool odd = false;
+            for (int s = 0; s < nslab; s++) {
+                const int c0 = ((ctab_t)g.slab)[2 * s], wd = ((ctab_t)g.wdeg)[s * W + wave] & 0xFF;
+                const uint16_t *cp = g.cols + c0 + tid;
+                bool par = false;
+                for (int k = 0; k < wd; k++) {
+                    const uint32_t c = cp[(size_t)k * T];
+                    if (c != kNoEdge) par ^= *lds_cell(lam0 + 2u * c) > (_Float16)0;
+                }
+                odd |= par;
+            }
+            if (__builtin_amdgcn_ballot_w64(odd) != 0 && (tid & 63) == 0) ctl[4] = 1;
+            lds_barrier();
+            conv = ctl[4] == 0;
+        }
+        if (!conv) {
+            for (n = 1; n <= A.max_iters; n++) {
+                bool odd = false, flip = false;
+                if (tid == 0) ctl[1 + (n + 1) % 3] = 0;                 // the flag of the NEXT sweep (last read two sweeps ago)
+                for (int st = 0; st < g.nstep; st++) {
+                    const int s0 = ((ctab_t)g.step_ptr)[st], s1 = ((ctab_t)g.step_ptr)[st + 1];
+                    for (int s = s0; s < s1; s++) {
+                        const int c0 = ((ctab_t)g.slab)[2 * s], wv = ((ctab_t)g.wdeg)[s * W + wave];
+                        const uint16_t *cp = g.cols + c0 + tid;
+                        CsrRec out;
+                        if (n == 1) {
+                            const CsrRec none{0.f, 0.f, 0u};
+                            csr_row_at<DCLASS, true>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, none, out, odd, flip);
+                        } else {
+                            const CsrRec in = rec[(size_t)s * T];
+                            csr_row_at<DCLASS, false>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, in, out, odd, flip);
+                        }
+                        rec[(size_t)s * T] = out;
+                    }
+                    if (st == g.nstep - 1 && __builtin_amdgcn_ballot_w64(odd || flip) != 0 && (tid & 63) == 0) ctl[1 + n % 3] = 1;
+                    lds_barrier();
+                }
+                if (ctl[1 + n % 3] == 0) { conv = true; break; }
+            }
+            if (n > A.max_iters) n = A.max_iters;
+        }
+        // ---- result: hard(lam) of a frame that stopped by the rule, the channel's decisions (as stored: fp16) otherwise (Orig.hs:69-70)
+        if (wide) {
+            auto put = [&](int i, const half8 &h) {
+                uint32_t lo = 0, hi = 0;
+#pragma unroll
+                for (int k = 0; k < 4; k++) { lo |= (h[k] > (_Float16)0 ? 1u : 0u) << (8 * k); hi |= (h[k + 4] > (_Float16)0 ? 1u : 0u) << (8 * k); }
+                *reinterpret_cast<uint2 *>(A.bits + fN + i) = make_uint2(lo, hi);
+            };
+            if (conv) {
+#pragma unroll 4
+                for (int i = tid * 8; i < g.N; i += T * 8) put(i, *reinterpret_cast<const half8 *>(lam + i));
+            } else {
+                with_llr_format(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 4
+                    for (int i = tid * 8; i < g.N; i += T * 8) {
+                        half8 h;
+                        load_llr8<decltype(fmt)::value>(A.llr, fN + i, h);
+                        put(i, h);
+                    }
+                });
+            }
+        } else {
+            with_llr_format(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 4
+                for (int i = tid; i < g.N; i += T) {
+                    const float v = conv ? (float)lam[i] : (float)sat16(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
+                    A.bits[fN + i] = v > 0.f ? 1 : 0;
+                    if (A.final_lam) A.final_lam[fN + i] = (double)v;
+                }
+            });
+        }
+        if (tid == 0) {
+            if (A.iters) A.iters[frame] = conv ? n : A.max_iters;
+            if (A.conv) A.conv[frame] = conv ? 1 : 0;
+            ctl[0] = (int)gridDim.x + atomicAdd(A.work_counter, 1);
+        }
+        lds_barrier();   // also: every lam read of this frame is done before the next frame's LLRs are written over it
+        frame = ctl[0];
+        lds_barrier();   // (nobody still reads ctl[0] when thread 0 of a fast wave writes the next one)
+    }
+}
+
+namespace {
+
+int dclass_of(int max_row_deg) { return max_row_deg <= 8 ? 8 : (max_row_deg <= 20 ? 20 : 32); }
+size_t lds_bytes_for(const ldpc_code &c) { return (((size_t)c.N * 2 + 15) & ~(size_t)15) + 32; }
+const void *pick_kernel(int dclass) {
+    return dclass == 8 ? (const void *)layered_csr_kernel<8> : dclass == 20 ? (const void *)layered_csr_kernel<20> : (const void *)layered_csr_kernel<32>;
+}
+
+// ------------------------------------------------------------------ host side
+struct LayeredCsrState : Backend {
+    int max_batch = 0, dclass = 8, grid = 0, nslab = 0;
+    size_t lds = 0;
+    CsrLayDev g{};
+    uint16_t *d_cols = nullptr;
+    int32_t *d_slab = nullptr, *d_wdeg = nullptr, *d_step = nullptr;
+    int *d_counter = nullptr;
+    CsrRec *rec = nullptr;
+
+    ~LayeredCsrState() override {
+        (void)hipFree(d_cols); (void)hipFree(d_slab); (void)hipFree(d_wdeg); (void)hipFree(d_step); (void)hipFree(d_counter); (void)hipFree(rec);
+    }
+    int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+               uint8_t *d_conv, double *d_final, double *d_trace) override;
+    int step(hipStream_t, int, const double *, const double *, const double *, double *, double *, uint8_t *) override {
+        return set_error(LDPC_EUNSUPPORTED, "no teacher-forced step with fp16 lam storage (the record kernels keep no per-edge messages)");
+    }
+    bool reads_llr_once(int) const override { return true; }
+};
+
+}  // namespace
+
+const char *layered_csr_why_not(const ldpc_code &c, int variant, int dtype) {
+    if (variant != LDPC_MINSUM) return "the on-chip layered kernel for any H implements min-sum";
+    if (dtype != LDPC_F16) return "the on-chip layered kernel for any H stores lam in fp16 (LDPC_F16)";
+    if (c.max_row_deg > 27) return "check rows above weight 27 (a row record holds 27 sign bits)";
+    if (lds_bytes_for(c) > 160 * 1024) return "a frame's fp16 LLRs exceed the 160 KB of LDS";
+    if (c.N > 65535) return "more than 65 535 columns (16-bit column table)";
+    const char *e = getenv("LDPC_LAYERED_CSR");
+    if (e && !strcmp(e, "0")) return "disabled (LDPC_LAYERED_CSR=0)";
+    return nullptr;
+}
+
+Backend *layered_csr_create(const ldpc_code &c, int max_batch) {
+    LayeredCsrState *s = new (std::nothrow) LayeredCsrState();
+    if (!s) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    try {
+        // lam stays on-chip for the whole decode in one launch (only the row records travel to HBM): reported as the on-chip path
+        s->path = LDPC_PATH_FUSED;
+        s->max_batch = max_batch; s->dclass = dclass_of(c.max_row_deg);
+        // barrier steps: maximal runs of consecutive layers that share no column
+        std::vector<std::vector<int>> steps;
+        {
+            std::vector<int32_t> stamp((size_t)c.N, -1);
+            const int nl = (int)c.layer_ptr.size() - 1;
+            for (int l = 0; l < nl; l++) {
+                bool clash = steps.empty();
+                for (int m = c.layer_ptr[l]; m < c.layer_ptr[l + 1] && !clash; m++)
+                    for (int q = c.row_ptr[m]; q < c.row_ptr[m + 1] && !clash; q++) clash = stamp[c.col_idx[q]] == (int)steps.size() - 1;
+                if (clash) steps.emplace_back();
+                for (int m = c.layer_ptr[l]; m < c.layer_ptr[l + 1]; m++) {
+                    steps.back().push_back(m);
+                    for (int q = c.row_ptr[m]; q < c.row_ptr[m + 1]; q++) stamp[c.col_idx[q]] = (int)steps.size() - 1;
+                }
+            }
+        }
+        auto deg = [&](int m) { return c.row_ptr[m + 1] - c.row_ptr[m]; };
+        size_t rmax = 1;
+        for (auto &st : steps) {
+            std::stable_sort(st.begin(), st.end(), [&](int a, int b) { return deg(a) > deg(b); });   // heaviest first: uniform waves
+            rmax = std::max(rmax, st.size());
+        }
+        const int T = (int)std::min<size_t>(csr_max_threads(s->dclass), (rmax + 63) / 64 * 64), W = T / 64;
+        std::vector<uint16_t> cols;
+        std::vector<int32_t> slab, wdeg, step_ptr(1, 0);
+        for (auto &st : steps) {
+            for (size_t r0 = 0; r0 < st.size(); r0 += T) {
+                const int nr = (int)std::min<size_t>(T, st.size() - r0), D = deg(st[r0]);
+                slab.push_back((int32_t)cols.size()); slab.push_back(D);
+                const size_t base = cols.size();
+                cols.resize(base + (size_t)D * T, kNoEdge);
+                for (int i = 0; i < nr; i++) {
+                    const int m = st[r0 + i];
+                    for (int k = 0; k < deg(m); k++) cols[base + (size_t)k * T + i] = (uint16_t)c.col_idx[c.row_ptr[m] + k];
+                }
+                for (int w = 0; w < W; w++) {
+                    int wd = 0; bool uni = true;
+                    for (int i = 64 * w; i < 64 * w + 64; i++) {
+                        const int d = i < nr ? deg(st[r0 + i]) : 0;
+                        if (i == 64 * w) wd = d; else uni = uni && d == wd;
+                        wd = std::max(wd, d);
+                    }
+                    wdeg.push_back(wd | (uni ? 0x100 : 0));
+                }
+            }
+            step_ptr.push_back((int32_t)(slab.size() / 2));
+        }
+        s->nslab = (int)(slab.size() / 2);
+        s->g.N = c.N; s->g.T = T; s->g.nstep = (int)steps.size();
+        s->lds = lds_bytes_for(c);
+        const void *kern = pick_kernel(s->dclass);
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds);
+        int per_cu = 0, dev = 0;
+        hipDeviceProp_t prop;
+        if (e == hipSuccess) e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, T, s->lds);
+        if (e == hipSuccess && per_cu <= 0) { set_error(LDPC_EHIP, "layered_csr: no workgroup of %d threads and %zu B of LDS is resident", T, s->lds); delete s; return nullptr; }
+        if (e == hipSuccess) s->grid = std::min(max_batch, per_cu * prop.multiProcessorCount);
+        if (e == hipSuccess) e = hipMalloc((void **)&s->d_cols, sizeof(uint16_t) * std::max<size_t>(cols.size(), 1));
+        if (e == hipSuccess) e = hipMalloc((void **)&s->d_slab, sizeof(int32_t) * std::max<size_t>(slab.size(), 2));
+        if (e == hipSuccess) e = hipMalloc((void **)&s->d_wdeg, sizeof(int32_t) * std::max<size_t>(wdeg.size(), 1));
+        if (e == hipSuccess) e = hipMalloc((void **)&s->d_step, sizeof(int32_t) * step_ptr.size());
+        if (e == hipSuccess) e = hipMalloc((void **)&s->d_counter, sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void **)&s->rec, sizeof(CsrRec) * (size_t)s->grid * std::max(s->nslab, 1) * T);
+        if (e == hipSuccess && !cols.empty()) e = hipMemcpy(s->d_cols, cols.data(), sizeof(uint16_t) * cols.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !slab.empty()) e = hipMemcpy(s->d_slab, slab.data(), sizeof(int32_t) * slab.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !wdeg.empty()) e = hipMemcpy(s->d_wdeg, wdeg.data(), sizeof(int32_t) * wdeg.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(s->d_step, step_ptr.data(), sizeof(int32_t) * step_ptr.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            set_error(e == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "layered_csr_create (%d workgroups x %zu bytes of records): %s", s->grid,
+                      sizeof(CsrRec) * (size_t)s->nslab * T, hipGetErrorString(e));
+            delete s;
+            return nullptr;
+        }
+        s->g.cols = s->d_cols; s->g.slab = s->d_slab; s->g.wdeg = s->d_wdeg; s->g.step_ptr = s->d_step;
+        snprintf(s->info.name, sizeof(s->info.name), "ldpc::layered_csr_kernel<%d>", s->dclass);
+        s->info.threads = T; s->info.frames_per_wg = 1;
+        return s;
+    } catch (...) { delete s; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+}
+
+int LayeredCsrState::decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                            uint8_t *d_conv, double *d_final, double *d_trace) {
+    if (d_trace) return set_error(LDPC_EUNSUPPORTED, "layered_csr: no per-sweep trace (decode without one)");
+    CsrLayArgs a{};
+    a.llr = d_llr; a.llr_fmt = llr_fmt; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final;
+    a.batch = batch; a.max_iters = max_iters; a.work_counter = d_counter;
+    hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(int), st);
+    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
+    const dim3 grid(std::min(batch, this->grid)), block(g.T);
+    if (timer) timer->begin(st);
+    if (dclass == 8) hipLaunchKernelGGL(layered_csr_kernel<8>, grid, block, lds, st, g, rec, a);
+    else if (dclass == 20) hipLaunchKernelGGL(layered_csr_kernel<20>, grid, block, lds, st, g, rec, a);
+    else hipLaunchKernelGGL(layered_csr_kernel<32>, grid, block, lds, st, g, rec, a);
+    if (timer) timer->end(st);
+    e = hipGetLastError();
+    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr launch: %s", hipGetErrorString(e));
+    return LDPC_OK;
+}
+
+}  // namespace ldpc

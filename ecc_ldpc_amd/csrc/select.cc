@@ -14,6 +14,8 @@
 //   (5) layered_lds.hip   layered min-sum with fp16 lam storage whose frame fits LDS: lam on-chip, row records streamed
 //   (6) layered_qc.hip    QC codes, either schedule: one workgroup per frame
 //   (7) flood.hip         any H, batch-major (lane = frame): flooding and layered schedules, fp16 storage, the parity modes
+// Layered min-sum with fp16 lam storage where none of the above serves it (LDPC_PATH_AUTO or LDPC_PATH_FUSED; reported as FUSED):
+//   (8) layered_csr.hip   any H whose frame fits LDS in fp16: lam on-chip, row records streamed, layers merged into barrier steps
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -178,16 +180,28 @@ Backend *make_backend(const ldpc_code &c, const ldpc_code_dev &tabs, int variant
     const bool parity = variant == LDPC_TANH_CM || variant == LDPC_TANH_CUDA32 || sum_order != LDPC_SUM_REFERENCE;
     // why no on-chip kernel serves this context (null: one does)
     const char *onchip_why = layered ? fused_layered_why_not(c, variant, dtype) : parity ? "parity mode" : fused_why_not(c, variant, dtype);
+    const char *csr_why = "";   // why the on-chip layered kernel for any H does not serve this context ("" = not considered)
     if (layered) {
+        // (8) layered_csr.hip: fp16 lam storage on-chip for ANY H -- only where no kernel above serves the request: no on-chip QC kernel,
+        // and under LDPC_PATH_AUTO no HBM kernel of a QC code either (an explicit LDPC_PATH_FLOOD keeps the state in HBM and is refused)
+        if (dtype == LDPC_F16 && onchip_why && path != LDPC_PATH_FLOOD && (path == LDPC_PATH_FUSED || layered_qc_why_not(c, variant, dtype, 0) != nullptr)) {
+            csr_why = layered_csr_why_not(c, variant, dtype);
+            if (!csr_why) return layered_csr_create(c, max_batch);
+        }
         if (dtype == LDPC_F16 && (onchip_why || path == LDPC_PATH_FLOOD)) {
             // from HBM: lam stored in fp16 for the frame-per-workgroup min-sum record kernel of QC codes (r03); nothing else
             const char *why = layered_qc_why_not(c, variant, dtype, 0);
-            if (why) { set_error(LDPC_EUNSUPPORTED, "the layered schedule from HBM with fp16 storage: %s", why); return nullptr; }
+            if (why) {
+                if (*csr_why) set_error(LDPC_EUNSUPPORTED, "the layered schedule with fp16 storage: from HBM: %s; on-chip kernel for any H: %s", why, csr_why);
+                else set_error(LDPC_EUNSUPPORTED, "the layered schedule from HBM with fp16 storage: %s", why);
+                return nullptr;
+            }
         }
         if (c.max_row_deg > 32) { set_error(LDPC_EUNSUPPORTED, "layered schedule: check rows above weight 32 (this code has %d)", c.max_row_deg); return nullptr; }
     }
     if ((path == LDPC_PATH_FUSED || dtype == LDPC_F16PK) && onchip_why) {
-        if (layered) set_error(LDPC_EUNSUPPORTED, "no on-chip kernel for the layered schedule on this code / rule / type (%s); LDPC_PATH_FLOOD keeps the state in HBM", onchip_why);
+        if (layered && *csr_why) set_error(LDPC_EUNSUPPORTED, "no on-chip kernel for the layered schedule on this code / rule / type (%s; on-chip kernel for any H: %s); LDPC_PATH_FLOOD keeps the state in HBM", onchip_why, csr_why);
+        else if (layered) set_error(LDPC_EUNSUPPORTED, "no on-chip kernel for the layered schedule on this code / rule / type (%s); LDPC_PATH_FLOOD keeps the state in HBM", onchip_why);
         else set_error(LDPC_EUNSUPPORTED, "no fused kernel for this code/variant/dtype (%s)", onchip_why);
         return nullptr;
     }

@@ -66,7 +66,9 @@ typedef enum { LDPC_TANH = 0, LDPC_MINSUM = 1, LDPC_TANH_CM = 2, LDPC_TANH_CUDA3
  *      the flood path also keeps lam and the messages in fp16 between its kernels, the fused paths keep them
  *      on-chip in f32 -- so for F16 the two paths are two different (documented) decoders, each with its own
  *      emulation in oracle/emulate_f16.py, whereas for F32/F64 they agree bit for bit.  With LDPC_SCHED_LAYERED from HBM
- *      (quasi-cyclic codes, min-sum): lam stored in fp16, f32 row records (emulation decode_minsum_f16_layered). */
+ *      (quasi-cyclic codes, min-sum): lam stored in fp16, f32 row records (emulation decode_minsum_f16_layered).  With
+ *      LDPC_SCHED_LAYERED, min-sum, on any other H whose frame fits the LDS in fp16 (csrc/layered_csr.hip): lam STORED in fp16
+ *      on-chip -- the arithmetic of that from-HBM F16 layered decoder (same emulation), not "the f32 decoder fed fp16-rounded LLRs". */
 /* F16PK (extension, BASELINE.json configs[3] "min-sum fp16 LLRs"): ARITHMETIC in IEEE binary16, two frames per lane in
  *      packed instructions (csrc/fused_pk16_body.h holds the specification: the loop of Min.hs:54-104 on fp16 values, the 3/4
  *      applied inside fused multiply-adds; channel LLRs saturate at +-16384 and message magnitudes at 2048, so that no sum
@@ -99,7 +101,12 @@ typedef enum {
     LDPC_PATH_FLOOD = 1, /* state in HBM, any H: quasi-cyclic codes one workgroup per frame and ONE launch per batch (either
                             schedule), any other H batch-major with two kernels per iteration                              */
     LDPC_PATH_FUSED = 2  /* whole decode in one launch, state in LDS/registers: QC codes (built-in or run-time specialised
-                            instances) and any H whose frame fits in 160 KB of LDS; flooding schedule                      */
+                            instances) and any H whose frame fits in 160 KB of LDS; flooding schedule.  Layered schedule:
+                            QC codes on-chip; and LDPC_F16 min-sum on any H no QC kernel takes (csrc/layered_csr.hip: lam
+                            STORED in fp16 in LDS for the whole decode, row records streamed through an HBM scratch area) --
+                            reported as FUSED because lam never leaves the chip, unlike the QC long-code kernel
+                            layered_lds.hip, which also keeps lam in LDS but reports FLOOD; an explicit LDPC_PATH_FLOOD
+                            still refuses LDPC_F16 layered on such a code                                                  */
 } ldpc_path;
 
 /* ---- library life-cycle -------------------------------------------------------------------
@@ -148,6 +155,15 @@ int ldpc_code_set_layers(ldpc_code *code, int n_layers, const int32_t *layer_ptr
  * tools/gen_dvbs2_like.py applies to codes/dvbs2like.64800.1.2).  Pure host code, needs no GPU.  Returns the number of full runs,
  * < 0 on error.  No counterpart in the reference (flooding only). */
 int ldpc_qc_layer_order(int block_rows, int block_cols, const int32_t *offsets, int run, int32_t *perm /* block_rows */);
+/* The same for any H, given as CSR the way ldpc_code_create_csr takes it: an order of the rows in which consecutive rows form few
+ * column-disjoint layers -- perm[i] = the row to put at place i, layer_ptr[0..n] = the layers of the permuted matrix (what
+ * ldpc_code_set_layers takes for the code built from the permuted rows); max_rows > 0 caps the rows of a layer, 0 leaves them
+ * uncapped.  First fit in file order (each row joins the lowest layer that holds none of its columns), the rows of a layer in file
+ * order: deterministic.  Like ldpc_qc_layer_order it only PROPOSES an order; the on-chip layered kernel for any H
+ * (csrc/layered_csr.hip) does one barrier step per run of consecutive column-disjoint layers, so the fewer layers, the faster.
+ * Pure host code, needs no GPU.  Returns n (the number of layers), < 0 on error.  No counterpart in the reference. */
+int ldpc_csr_layer_order(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int max_rows,
+                         int32_t *perm /* M */, int32_t *layer_ptr /* M + 1 */);
 int ldpc_code_layers(const ldpc_code *code, int *n_layers, int32_t *layer_ptr /* may be NULL; n_layers+1 entries */);
 
 /* ---- decoder replica -------------------------------------------------------------------------
