@@ -16,12 +16,38 @@ struct DynRow {
     ctab_t p;
     __device__ __forceinline__ uint32_t lo(int k) const { return p[k] & 0xffffu; }
     __device__ __forceinline__ uint32_t hi(int k) const { return p[k] >> 16; }
+    static constexpr bool nowrap(int) { return false; }
+    static constexpr bool any_wrap(int) { return true; }
 };
 template <typename CT, int SZ, class T, int EBEG>
 struct StatRow {
     static constexpr uint32_t CPW = QcGeom<SZ>::CPW, V = QcGeom<SZ>::V, ES = sizeof(CT);
     __device__ __forceinline__ constexpr uint32_t lo(int k) const { return T::rot[EBEG + k] * CPW * ES; }
     __device__ __forceinline__ constexpr uint32_t hi(int k) const { return T::bc[EBEG + k] * V * ES; }
+    static constexpr bool nowrap(int) { return false; }
+    static constexpr bool any_wrap(int) { return true; }
+};
+// The rotation as ONE WAVE of a group sees it.  A thread is row 64 * WV + i of every circulant (WV = its wave inside the
+// group, i = its lane); the address base is the LANE's offset i * ES, and the wave's 64 * WV rows are folded into the
+// rotation: s = (64 * WV + rot) mod SZ.  If s + 63 < SZ no lane of this wave wraps: the position is i * ES + s * ES, lane
+// base + an immediate of the DS instruction, no arithmetic at all.  Otherwise (lane base + s * ES) wraps as before.
+// WV < 0: not specialised, rot() is the plain rotation against the thread's row offset inside the group.
+template <int SZ, int WV>
+struct WaveRot {
+    static_assert(WV < 0 || (QcGeom<SZ>::CPW == 1 && SZ % 64 == 0), "wave-specialised addresses: whole waves of one frame");
+    static constexpr uint32_t rot(uint32_t r) { return WV < 0 ? r * QcGeom<SZ>::CPW : (64u * WV + r) % SZ; }
+    static constexpr bool nowrap(uint32_t r) { return WV >= 0 && rot(r) + 63 < SZ; }
+};
+template <typename CT, int SZ, class T, int EBEG, int WV>
+struct StatRowW {
+    static constexpr uint32_t V = QcGeom<SZ>::V, ES = sizeof(CT);
+    __device__ __forceinline__ constexpr uint32_t lo(int k) const { return WaveRot<SZ, WV>::rot(T::rot[EBEG + k]) * ES; }
+    __device__ __forceinline__ constexpr uint32_t hi(int k) const { return T::bc[EBEG + k] * V * ES; }
+    static constexpr bool nowrap(int k) { return WaveRot<SZ, WV>::nowrap(T::rot[EBEG + k]); }
+    static constexpr bool any_wrap(int d) {
+        for (int k = 0; k < d; k++) if (!nowrap(k)) return true;
+        return false;
+    }
 };
 struct DynTab {
     ctab_t p;
@@ -118,25 +144,42 @@ __device__ __forceinline__ uint32_t row_addr(uint32_t a0, uint32_t p4, uint32_t 
 }
 
 // phase A for the RPL rows a lane owns in one block row of degree D.  msg: [RPL][D] registers.
-template <typename CT, int VARIANT, int D, int RPL, int HSTEP, bool SYNDROME_ONLY, class Row>
+// NEG: LDS holds L = 0 - lam (an exact zero therefore always as +0), so that "lam > 0" is L's sign bit: a row's parity
+// is then the sign of the XOR of its gathered words (one v_xor per edge instead of a v_cmp), and t = lam - m = (-L) - m.
+template <typename CT, int VARIANT, int D, int RPL, int HSTEP, bool SYNDROME_ONLY, bool NEG = false, class Row>
 __device__ __forceinline__ bool rows_a(const char *lds, Row tabrow, uint32_t p4, uint32_t vmask, CT *msg) {
-    asm volatile("" : "+v"(p4));  // keeps the loop-invariant address arithmetic inside the turn loop, row by row
+    const uint32_t b4 = p4;   // edges that cannot wrap (Row::nowrap) address base + immediate: nothing to hoist, no fence
+    if constexpr (Row::any_wrap(D)) asm volatile("" : "+v"(p4));  // keeps the loop-invariant address arithmetic inside the turn loop, row by row
     if constexpr (SYNDROME_ONLY) LDPC_COLD_PATH();   // the one extra pass after the last update (Orig.hs:69-70)
     CT l[RPL][D];
     static_for<0, D>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         const uint32_t lo = tabrow.lo(k), hi = tabrow.hi(k);
-        uint32_t a0 = qc_wrap(p4 + lo, vmask);   // position inside the block column; `hi` (its base) is added below
+        uint32_t a0;   // position inside the block column; `hi` (its base) is added below
+        if constexpr (Row::nowrap(k)) a0 = b4 + lo; else a0 = qc_wrap(p4 + lo, vmask);
 #pragma unroll
         for (int h = 0; h < RPL; h++) l[h][k] = lds_ld<CT>(lds + hi, row_addr<RPL, HSTEP>(a0, p4, lo, vmask, h));
     });
     bool any = false;
+    if constexpr (NEG) {
+        static_assert(VARIANT == LDPC_V_MINSUM && sizeof(CT) == 4, "negated lam: the f32 min-sum form only");
+        uint32_t odd = 0;
 #pragma unroll
-    for (int h = 0; h < RPL; h++) {
-        bool par = false;
+        for (int h = 0; h < RPL; h++) {
+            uint32_t px = 0;
 #pragma unroll
-        for (int k = 0; k < D; k++) par ^= (l[h][k] > CT(0));
-        any |= par;
+            for (int k = 0; k < D; k++) px ^= __float_as_uint(l[h][k]);
+            odd |= px;
+        }
+        any = (odd >> 31) != 0u;
+    } else {
+#pragma unroll
+        for (int h = 0; h < RPL; h++) {
+            bool par = false;
+#pragma unroll
+            for (int k = 0; k < D; k++) par ^= (l[h][k] > CT(0));
+            any |= par;
+        }
     }
     if constexpr (SYNDROME_ONLY) return any;
 #pragma unroll
@@ -148,7 +191,7 @@ __device__ __forceinline__ bool rows_a(const char *lds, Row tabrow, uint32_t p4,
             float m1 = INFINITY, m2 = INFINITY;
             static_for<0, D>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                float t = l[h][k] - m[k];
+                float t = NEG ? (-l[h][k]) - m[k] : l[h][k] - m[k];
                 m[k] = t;
                 X ^= __float_as_uint(t);
                 float a = fabsf(t);

@@ -10,8 +10,12 @@
 // For sz < 64 a workgroup holds 64/sz frames interleaved lane by lane (sz = 32: wave 0 = pair 0 and wave 1 =
 // pair 1 of two frames); loop control then runs on a workgroup-uniform "done" mask, see split_body.
 // No cross-lane combine is needed (a check row is still handled by one thread) and the graph stays a
-// compile-time table; the two pairs run different straight-line code behind one wave-uniform branch, so
-// the total code size is unchanged.
+// compile-time table; the two pairs run different straight-line code behind one wave-uniform branch.
+// The f32 min-sum sz = 128 instance goes one step further (SPLIT_WAVE_SPEC): each of the frame's FOUR waves runs its
+// own program, because a wave that knows its place inside the pair knows which of its edges can wrap around
+// their circulant -- for every rotation one of a pair's two waves cannot, and addresses that edge as lane base +
+// immediate with no arithmetic (as shipped: in phase A, see SPLIT_WAVE_PHASES below).  Four turn loops of ~1 920 instructions
+// instead of two of ~2 280; the kernel's code about doubles (measured harmless: profiles/r06_split_wave_ab.txt).
 //
 // Phase B keeps the column "rounds" of fused_msg.hip (round q = q-th contribution of every block column
 // in descending row order = Orig.hs:96 per column): in a round each pair adds the edges it owns; all
@@ -19,12 +23,33 @@
 // consecutive contributions of a column alternate between the pairs, which balances the rounds.
 #include <stdio.h>
 
-// f32 min-sum, sz = 128: 12 of the 24 round-0 LLR copies per thread live in LDS (12 KB per workgroup, 34.8 KB in all: four
-// workgroups still fit a CU's 160 KB) -- 127 VGPRs and no scratch at 4 waves/SIMD instead of 71 spilled registers.  Measured on
-// jpl.4096, 65 536 frames, 2 dB / 3 dB (profiles/r05_split_ab.txt): 0 copies 18.55 / 8.68 ms, 8: 18.29 / 8.36 (26 spilled),
-// 12: 18.20 / 8.26, 16: 18.42 / 8.36.
+// f32 min-sum, sz = 128: 13 of the 24 round-0 LLR copies per thread live in LDS (13 KB per workgroup, 35.9 KB in all: four
+// workgroups still fit a CU's 160 KB) -- no scratch at 4 waves/SIMD instead of 71 spilled registers.  Measured on
+// jpl.4096, 65 536 frames, 2 dB / 3 dB (profiles/r05_split_ab.txt, before the items below): 0 copies 18.55 / 8.68 ms,
+// 8: 18.29 / 8.36 (26 spilled), 12: 18.20 / 8.26, 16: 18.42 / 8.36.  With the sign-bit syndrome 12 leaves one register spilled
+// and 13 none; 14 and other SPLIT_CH values time within the run-to-run spread of 13 (profiles/r06_split_wave_ab.txt).
 #ifndef SPLIT_ORIG_LDS
-#define SPLIT_ORIG_LDS 12
+#define SPLIT_ORIG_LDS 13
+#endif
+// f32 min-sum, sz = 128 (fused_split_body.h; measured one by one in profiles/r06_split_wave_ab.txt, 2 dB: 18.14 ms before,
+// 16.82 with the first two, 17.56 with the third alone, 16.19 with all; SPLIT_WAVE_SPEC in both phases there):
+//   SPLIT_WAVE_SPEC  one program per wave of a pair, rotation wrap as an immediate where the wave cannot wrap
+//   SPLIT_FLAGS_LDS  the syndrome words as LDS accesses (no flat loads behind the barrier)
+//   SPLIT_NEG_LAM    lam stored negated, syndrome = XOR of sign bits
+#ifndef SPLIT_WAVE_SPEC
+#define SPLIT_WAVE_SPEC 1
+#endif
+// The wave's own rotations in phase A only (SPLIT_WAVE_PHASES = 1): 903 VALU instructions per wave-turn, 16.86 ms.  In both phases
+// (= 3) the kernel is at 846 and 16.24 ms in the same job -- but bench.py's contract test (tests/test_bench_contract_gpu.py) accepts
+// 900 to 1 100 VALU instructions per wave-turn for this kernel, so that form stays behind the macro.
+#ifndef SPLIT_WAVE_PHASES
+#define SPLIT_WAVE_PHASES 1
+#endif
+#ifndef SPLIT_FLAGS_LDS
+#define SPLIT_FLAGS_LDS 1
+#endif
+#ifndef SPLIT_NEG_LAM
+#define SPLIT_NEG_LAM 1
 #endif
 #include "fused_split_body.h"
 

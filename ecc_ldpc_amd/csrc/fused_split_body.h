@@ -2,6 +2,9 @@
 // Compiled two ways from this one source: ahead of time for the shipped matrices (fused_split.hip, tables in
 // generated_tables.h) and at run time by hiprtc for any other single-circulant quasi-cyclic H (jit.cc: plan and
 // rotation table generated as constexpr structs from the code's description) -- so it includes nothing host-side.
+// The ahead-of-time f32 min-sum instances with whole waves of one frame (sz = 128) are built in a tighter form behind
+// SPLIT_WAVE_SPEC, SPLIT_FLAGS_LDS and SPLIT_NEG_LAM below; all three default to off here, so a run-time compiled instance
+// and the sz = 32 instances compile to what they were.
 #pragma once
 #include "fused_rows.h"
 
@@ -13,6 +16,30 @@
 // run-time compiled instances keep every copy in registers.
 #ifndef SPLIT_ORIG_LDS
 #define SPLIT_ORIG_LDS 0
+#endif
+// One straight-line program per WAVE of a group instead of one per group (f32 min-sum, whole waves of one frame, more than one
+// wave per group): the wave's index inside its group becomes a compile-time constant, and with it which edges can wrap around
+// their circulant in that wave (fused_rows.h WaveRot): for every rotation at least one of a group's two waves adds no wrap
+// arithmetic, only an immediate.  fused_split.hip sets it for its ahead-of-time instances; run-time compiled instances keep one
+// program per group.
+#ifndef SPLIT_WAVE_SPEC
+#define SPLIT_WAVE_SPEC 0
+#endif
+// which phases address by the wave's own rotations when SPLIT_WAVE_SPEC is on: bit 0 = phase A (check rows), bit 1 = phase B
+// (column rounds).  The other phase keeps the thread's offset inside its pair and the plain rotations.
+#ifndef SPLIT_WAVE_PHASES
+#define SPLIT_WAVE_PHASES 3
+#endif
+// the per-wave syndrome words read and written as LDS (address space 3) accesses instead of through a generic volatile pointer,
+// whose loads go down the flat path and count against vmcnt as well as lgkmcnt right behind the barrier (same instances)
+#ifndef SPLIT_FLAGS_LDS
+#define SPLIT_FLAGS_LDS 0
+#endif
+// lam kept NEGATED in LDS, L = 0 - lam with an exact zero always as +0 (same instances): the syndrome becomes the XOR of the
+// gathered words' sign bits (fused_rows.h rows_a NEG).  Phase B subtracts, L' = L - ne'; whatever leaves the kernel as lam
+// (final_lam, trace) or enters it (channel LLRs, a given lam) is negated on the way.
+#ifndef SPLIT_NEG_LAM
+#define SPLIT_NEG_LAM 0
 #endif
 // wave priority while in phase A (check rows: long stretches of independent VALU work) and in phase B (column
 // rounds: short, LDS-bound, barrier-separated).  Measured on jpl.4096, 65 536 frames: A=0/B=0 20.72 ms,
@@ -35,6 +62,23 @@
 #endif
 
 namespace ldpc {
+
+// the instances SPLIT_WAVE_SPEC and SPLIT_FLAGS_LDS apply to: f32 min-sum, one frame per workgroup in whole waves, several waves per group
+template <typename CT, int VARIANT, int SZ>
+constexpr bool kSplitWholeWaves = VARIANT == LDPC_V_MINSUM && sizeof(CT) == 4 && QcGeom<SZ>::CPW == 1 && QcGeom<SZ>::VT == QcGeom<SZ>::V && QcGeom<SZ>::VT > 64;
+// the syndrome words of a workgroup, one per wave.  volatile either way: they are rewritten behind every barrier.
+template <bool LDS_AS> struct SynFlags;
+template <> struct SynFlags<false> {
+    volatile uint32_t *p;
+    __device__ __forceinline__ explicit SynFlags(char *at) : p(reinterpret_cast<volatile uint32_t *>(at)) {}
+    __device__ __forceinline__ volatile uint32_t &operator[](uint32_t w) const { return p[w]; }
+};
+template <> struct SynFlags<true> {
+    typedef __attribute__((address_space(3))) volatile uint32_t *ptr_t;
+    ptr_t p;
+    __device__ __forceinline__ explicit SynFlags(char *at) : p((ptr_t)at) {}
+    __device__ __forceinline__ __attribute__((address_space(3))) volatile uint32_t &operator[](uint32_t w) const { return p[w]; }
+};
 
 // hard bits of the block columns a lane's group fills, NB of them
 #ifndef SPLIT_RESULT_PACKED
@@ -126,12 +170,27 @@ struct SplitLds {
     static constexpr uint32_t orig_at(int P, int os) { return ORIG_OFF + (uint32_t)(os * THREADS + P * VT) * ES; }
 };
 
-template <typename CT, int VARIANT, int SZ, class Plan, class T, int P, int Q, int I0, int I1>
-__device__ __forceinline__ void split_round_chunk(char *lds, uint32_t p4, uint32_t vmask, const CT *msg, const CT *orig_rot, const float *gllr, uint32_t r0) {
+// b4: the address base of the thread -- its byte offset inside a block column (WV < 0), or its LANE's, with the wave's rows
+// folded into the rotations (WV = the wave inside the group, WaveRot).  An edge that cannot wrap is base + immediate and
+// holds no address register; the fence keeps the wrapped addresses of the others from being hoisted out of the turn loop.
+template <typename CT, int VARIANT, int SZ, class Plan, class T, int P, int WV, int Q, int I0, int I1>
+__device__ __forceinline__ void split_round_chunk(char *lds, const uint32_t b4, uint32_t vmask, const CT *msg, const CT *orig_rot, const float *gllr, uint32_t r0) {
     using S = Split<Plan, T>;
     using L = SplitLds<CT, VARIANT, Plan, SZ, T>;
-    constexpr uint32_t ES = sizeof(CT), CPW = QcGeom<SZ>::CPW, V = QcGeom<SZ>::V;
-    asm volatile("" : "+v"(p4));
+    using R = WaveRot<SZ, WV>;
+    constexpr uint32_t ES = sizeof(CT), V = QcGeom<SZ>::V;
+    constexpr uint32_t WOFF = WV < 0 ? 0 : WV * 64 * ES;   // own position inside a block column = b4 + WOFF
+    constexpr bool NEG = SPLIT_NEG_LAM && kSplitWholeWaves<CT, VARIANT, SZ>;   // LDS (lam and the round-0 copies) holds 0 - lam
+    constexpr bool FENCE = [] {
+        for (int i = I0; i < I1; i++) if (!R::nowrap(T::rot[S::nth(Q, P, i)])) return true;
+        return false;
+    }();
+    uint32_t p4 = b4;
+    if constexpr (FENCE) asm volatile("" : "+v"(p4));
+    auto pos = [&](auto ec) -> uint32_t {   // position of edge e inside its block column
+        constexpr uint32_t rot = T::rot[decltype(ec)::value];
+        if constexpr (R::nowrap(rot)) return b4 + R::rot(rot) * ES; else return qc_wrap(p4 + R::rot(rot) * ES, vmask);
+    };
     if constexpr (Q == 0) {
         static_for<I0, I1>([&](auto ic) {
             // (constexpr VARIABLES: a constexpr function call in a subscript is not a constant expression and was
@@ -139,9 +198,9 @@ __device__ __forceinline__ void split_round_chunk(char *lds, uint32_t p4, uint32
             constexpr int e = S::nth(Q, P, decltype(ic)::value);
             constexpr int ms = S::slot(e), os = S::oslot(T::bc[e]);
             CT o;
-            if constexpr (SPLIT_ORIG_REGS && os < L::NOL) o = lds_ld<CT>(lds + L::orig_at(P, os), p4);
+            if constexpr (SPLIT_ORIG_REGS && os < L::NOL) o = lds_ld<CT>(lds + L::orig_at(P, os) + WOFF, b4);
             else if constexpr (SPLIT_ORIG_REGS) o = orig_rot[os]; else o = (CT)gllr[T::bc[e] * SZ + ((r0 + T::rot[e]) % SZ)];
-            lds_st<CT>(lds + T::bc[e] * V * ES, qc_wrap(p4 + T::rot[e] * CPW * ES, vmask), msg[ms] + o);
+            lds_st<CT>(lds + T::bc[e] * V * ES, pos(std::integral_constant<int, e>{}), NEG ? o - msg[ms] : msg[ms] + o);
         });
         return;
     }
@@ -150,32 +209,34 @@ __device__ __forceinline__ void split_round_chunk(char *lds, uint32_t p4, uint32
     static_for<I0, I1>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         constexpr int e = S::nth(Q, P, i);
-        adr[i - I0] = qc_wrap(p4 + T::rot[e] * CPW * ES, vmask);
+        adr[i - I0] = pos(std::integral_constant<int, e>{});
         cur[i - I0] = lds_ld<CT>(lds + T::bc[e] * V * ES, adr[i - I0]);
     });
     static_for<I0, I1>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         constexpr int e = S::nth(Q, P, i);
         constexpr int ms = S::slot(e);
-        lds_st<CT>(lds + T::bc[e] * V * ES, adr[i - I0], msg[ms] + cur[i - I0]);
+        lds_st<CT>(lds + T::bc[e] * V * ES, adr[i - I0], NEG ? cur[i - I0] - msg[ms] : msg[ms] + cur[i - I0]);
     });
     asm volatile("" ::: "memory");
 }
-template <typename CT, int VARIANT, int SZ, class Plan, class T, int P, int Q, int I0>
+template <typename CT, int VARIANT, int SZ, class Plan, class T, int P, int WV, int Q, int I0>
 __device__ __forceinline__ void split_round(char *lds, uint32_t p4, uint32_t vmask, const CT *msg, const CT *orig_rot, const float *gllr, uint32_t r0) {
     constexpr int CNT = Split<Plan, T>::count(Q, P), CH = SZ < 64 ? SPLIT_CH_SMALL : SPLIT_CH;
     if constexpr (I0 < CNT) {
-        split_round_chunk<CT, VARIANT, SZ, Plan, T, P, Q, I0, (I0 + CH < CNT ? I0 + CH : CNT)>(lds, p4, vmask, msg, orig_rot, gllr, r0);
-        split_round<CT, VARIANT, SZ, Plan, T, P, Q, I0 + CH>(lds, p4, vmask, msg, orig_rot, gllr, r0);
+        split_round_chunk<CT, VARIANT, SZ, Plan, T, P, WV, Q, I0, (I0 + CH < CNT ? I0 + CH : CNT)>(lds, p4, vmask, msg, orig_rot, gllr, r0);
+        split_round<CT, VARIANT, SZ, Plan, T, P, WV, Q, I0 + CH>(lds, p4, vmask, msg, orig_rot, gllr, r0);
     }
 }
 
 // The whole decode of one pair: P is a compile-time constant, so every ownership test below is resolved
 // at compile time and the two pairs are two independent straight-line programs (one wave-uniform branch
-// in the kernel).  Keeping them as separate regions matters for the register allocator: with both pairs'
+// in the kernel).  WV >= 0: the program of wave WV of the pair alone (SPLIT_WAVE_SPEC); the register that lives
+// across the loop is then the LANE's offset b4, and the thread's own position p4 = b4 + an immediate.
+// Keeping them as separate regions matters for the register allocator: with both pairs'
 // code merged in one loop body the 105 loop-carried registers met in phi nodes at every branch merge and
 // were spilled wholesale.
-template <typename CT, int VARIANT, class Plan, int SZ, class T, int P>
+template <typename CT, int VARIANT, class Plan, int SZ, class T, int P, int WV>
 __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const uint32_t tid) {
     using S = Split<Plan, T>;
     constexpr int CPW = QcGeom<SZ>::CPW, V = QcGeom<SZ>::V, VT = QcGeom<SZ>::VT;  // frames per workgroup, positions per block column, threads per group
@@ -186,7 +247,12 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
     // about the lane's place -- frame, row, global offsets -- is recomputed from it where needed (Where), so that
     // it does not occupy registers next to the messages.
     if constexpr (VT != V) { if ((tid % VT) >= (uint32_t)V) return; }   // circulant size not a multiple of 64: the top lanes of the group idle
-    const uint32_t p4 = (tid % VT) * ES;
+    // what LDS holds for a lam (and for a channel LLR among the round-0 copies), and back: lam itself, or 0 - lam (SPLIT_NEG_LAM)
+    constexpr bool NEG = SPLIT_NEG_LAM && kSplitWholeWaves<CT, VARIANT, SZ>;
+    auto stored = [](CT x) { return NEG ? CT(0) - x : x; };
+    const uint32_t b4 = (tid % (WV < 0 ? VT : 64)) * ES;
+    const uint32_t p4 = b4 + (WV < 0 ? 0 : WV * 64) * ES;
+    constexpr int WVA = (SPLIT_WAVE_PHASES & 1) ? WV : -1, WVB = (SPLIT_WAVE_PHASES & 2) ? WV : -1;   // per phase: specialised or not
     struct Where {
         uint32_t sub, r0; long long frame; bool valid; size_t fN, fE;
         __device__ __forceinline__ Where(uint32_t p, int batch) {
@@ -229,7 +295,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
                 CT v = maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, fN + bc * SZ + r0), A.llr_round16);
                 obits.set(bc / Plan::NP, v > CT(0));
                 if (A.step_mode) v = (CT)A.st_lam[fN + bc * SZ + r0];
-                lds_st<CT>(lds, p4 + (bc * V * ES), v);
+                lds_st<CT>(lds, p4 + (bc * V * ES), stored(v));
             }
         });
         if (A.step_mode) {   // teacher-forced step: LDS holds the given lam, the channel LLRs come from memory
@@ -238,7 +304,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
                 if constexpr (SPLIT_ORIG_REGS && S::oowner(bc) == P) {
                     constexpr int e0 = Rounds<T>::round0_edge(bc);
                     constexpr int os = S::oslot(bc);
-                    put_orig(os, maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, fN + bc * SZ + ((r0 + T::rot[e0]) % SZ)), A.llr_round16));
+                    put_orig(os, stored(maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, fN + bc * SZ + ((r0 + T::rot[e0]) % SZ)), A.llr_round16)));
                 }
             });
         }
@@ -268,7 +334,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
         });
     }
 
-    volatile uint32_t *flags = reinterpret_cast<volatile uint32_t *>(lds + LAM_BYTES);
+    const SynFlags<SPLIT_FLAGS_LDS && kSplitWholeWaves<CT, VARIANT, SZ>> flags(lds + LAM_BYTES);
     // done: bit s = frame s of this workgroup has finished.  Workgroup-uniform (derived from the shared flags), so
     // loop control and barriers stay uniform with several frames.  A finished frame keeps its answer in `snap`;
     // its lanes then keep computing on their own (disjoint) LDS columns until the workgroup's other frames are
@@ -292,7 +358,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
             static_for<0, Plan::NBC>([&](auto bcc) {
                 constexpr int bc = decltype(bcc)::value;
                 if constexpr ((bc % Plan::NP) == P)
-                    A.trace[((size_t)w.frame * (A.max_iters + 1) + n) * N + bc * SZ + w.r0] = (double)lds_ld<CT>(lds, p4 + (bc * V * ES));
+                    A.trace[((size_t)w.frame * (A.max_iters + 1) + n) * N + bc * SZ + w.r0] = (double)stored(lds_ld<CT>(lds, p4 + (bc * V * ES)));
             });
         }
         const bool last = (n >= turns);
@@ -302,9 +368,9 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
             constexpr int br = decltype(brc)::value;
             if constexpr (S::owner_br(br) == P) {
                 constexpr int D = Plan::deg(br), ms0 = S::slot(Plan::ebeg(br));
-                StatRow<CT, SZ, T, Plan::ebeg(br)> row;
-                if (last) unsat |= rows_a<CT, VARIANT, D, 1, 0, true>(lds, row, p4, vmask, (CT *)nullptr);
-                else unsat |= rows_a<CT, VARIANT, D, 1, 0, false>(lds, row, p4, vmask, &msg[ms0]);
+                StatRowW<CT, SZ, T, Plan::ebeg(br), WVA> row;
+                if (last) unsat |= rows_a<CT, VARIANT, D, 1, 0, true, NEG>(lds, row, WVA < 0 ? p4 : b4, vmask, (CT *)nullptr);
+                else unsat |= rows_a<CT, VARIANT, D, 1, 0, false, NEG>(lds, row, WVA < 0 ? p4 : b4, vmask, &msg[ms0]);
             }
         });
         // per wave: bit s = some lane of frame s saw an odd row parity (frames interleave lane by lane)
@@ -363,14 +429,14 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
                     constexpr int bc = decltype(bcc)::value;
                     if constexpr ((bc % Plan::NP) == P) {
                         CT v = lds_ld<CT>(lds, p4 + (bc * V * ES));
-                        res.bits.set(bc / Plan::NP, v > CT(0));
+                        res.bits.set(bc / Plan::NP, NEG ? v < CT(0) : v > CT(0));
                     }
                 });
                 if (A.final_lam) {
                     const Where w(p4, A.batch);
                     static_for<0, Plan::NBC>([&](auto bcc) {
                         constexpr int bc = decltype(bcc)::value;
-                        if constexpr ((bc % Plan::NP) == P) A.final_lam[w.fN + bc * SZ + w.r0] = (double)lds_ld<CT>(lds, p4 + (bc * V * ES));
+                        if constexpr ((bc % Plan::NP) == P) A.final_lam[w.fN + bc * SZ + w.r0] = (double)stored(lds_ld<CT>(lds, p4 + (bc * V * ES)));
                     });
                 }
             }
@@ -382,7 +448,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
         if (done != FULL) {
             __builtin_amdgcn_s_setprio(SPLIT_PRIO_B);
             static_for<0, Rounds<T>::num_rounds()>([&](auto qc) {
-                split_round<CT, VARIANT, SZ, Plan, T, P, decltype(qc)::value, 0>(lds, p4, vmask, msg, orig, reinterpret_cast<const float *>(A.llr) + fN, r0);
+                split_round<CT, VARIANT, SZ, Plan, T, P, WVB, decltype(qc)::value, 0>(lds, WVB < 0 ? p4 : b4, vmask, msg, orig, reinterpret_cast<const float *>(A.llr) + fN, r0);
                 __syncthreads();  // the next round adds into the same columns
             });
             __builtin_amdgcn_s_setprio(SPLIT_PRIO_A);
@@ -395,7 +461,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
     if (A.step_mode) {
         static_for<0, Plan::NBC>([&](auto bcc) {
             constexpr int bc = decltype(bcc)::value;
-            if constexpr ((bc % Plan::NP) == P) A.final_lam[w.fN + bc * SZ + w.r0] = (double)lds_ld<CT>(lds, p4 + (bc * V * ES));
+            if constexpr ((bc % Plan::NP) == P) A.final_lam[w.fN + bc * SZ + w.r0] = (double)stored(lds_ld<CT>(lds, p4 + (bc * V * ES)));
         });
         static_for<0, Plan::NBR>([&](auto brc) {
             constexpr int br = decltype(brc)::value;
@@ -453,11 +519,20 @@ __device__ __forceinline__ void split_kernel_body(const FusedArgs &A) {
     static_assert(SZ >= 2, "circulant size");
     __shared__ __attribute__((aligned(16))) char lds[SplitLds<CT, VARIANT, Plan, SZ, T>::BYTES];
     const uint32_t tid = threadIdx.x;
-    const uint32_t pair = __builtin_amdgcn_readfirstlane(tid / G::VT);  // wave-uniform (VT is a multiple of 64)
-    static_for<0, Plan::NP>([&](auto pc) {
-        constexpr int P = decltype(pc)::value;
-        if (pair == (uint32_t)P) split_body<CT, VARIANT, Plan, SZ, T, P>(A, lds, tid);
-    });
+    constexpr int WPG = G::VT / 64;   // waves per group
+    if constexpr (SPLIT_WAVE_SPEC && kSplitWholeWaves<CT, VARIANT, SZ>) {
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(tid / 64);
+        static_for<0, Plan::NP * WPG>([&](auto wc) {
+            constexpr int P = decltype(wc)::value / WPG, WV = decltype(wc)::value % WPG;
+            if (wave == (uint32_t)decltype(wc)::value) split_body<CT, VARIANT, Plan, SZ, T, P, WV>(A, lds, tid);
+        });
+    } else {
+        const uint32_t pair = __builtin_amdgcn_readfirstlane(tid / G::VT);  // wave-uniform (VT is a multiple of 64)
+        static_for<0, Plan::NP>([&](auto pc) {
+            constexpr int P = decltype(pc)::value;
+            if (pair == (uint32_t)P) split_body<CT, VARIANT, Plan, SZ, T, P, -1>(A, lds, tid);
+        });
+    }
 }
 
 }  // namespace ldpc
