@@ -1,4 +1,4 @@
-// layered_csr.hip -- row-layered min-sum for ANY parity-check matrix: lam ON-CHIP as fp16, row records streamed from HBM.
+// layered_csr.hip -- row-layered min-sum for ANY parity-check matrix: lam ON-CHIP (as fp16 or as f32), row records streamed from HBM.
 //
 // layered_lds.hip carried over from quasi-cyclic codes to CSR graphs.  Same arithmetic, same roundings (f32 arithmetic and records,
 // every lam write saturated and rounded to binary16 -- specification oracle/emulate_f16.py decode_minsum_f16_layered, rows in
@@ -11,7 +11,14 @@
 //     them one after the other gives.  A step's rows are sorted by weight (heaviest first) and cut into SLABS of T rows, thread t
 //     taking row t of every slab of the step; rows lighter than their wave's heaviest are padded with neutral edges (index 0xFFFF:
 //     no lam read or write, no part in min, sign, parity or flip).
-// LDS: the frame's lam (2 N bytes) + 32 bytes of control words; the short codes get several workgroups per CU.
+// LDS: the frame's lam (sizeof(LT) N bytes, LT the type of a lam cell) + 32 bytes of control words; the short codes get several
+// workgroups per CU.
+// The lam cell's type LT is the kernel's second template parameter.  _Float16 (LDPC_F16) is everything said above.  float (LDPC_F32)
+// keeps the cell as the arithmetic produced it -- nothing rounded, nothing saturated, N <= 40 952 -- and is,
+// bit for bit, flood.hip's layered_kernel<float, min-sum> on the same code and layers (tests/test_layered_csr_f32_gpu.py).  Without
+// saturation a frame that diverges reaches +-inf, then NaN, whose hard decisions are an all-zero "codeword": that instance carries the
+// non-finite veto of ldpc_math.h kVetoesNonFinite -- when a frame's stop rule fires the workgroup scans its lam once, and any cell
+// that is not finite turns "converged" into "failed" (flag 0, the sweep limit as its count, the channel's decisions and LLRs).
 // Algorithmic HBM bytes per frame: sweeps * 24 M (the first sweep writes only) + the LLRs in + the bits out; the column table
 // (2 bytes per padded edge) is read by every workgroup every sweep and stays in L2.
 #include <stdio.h>
@@ -60,28 +67,55 @@ __device__ __forceinline__ void lds_barrier() {     // LDS traffic only: global 
 __device__ __forceinline__ _Float16 sat16(float v) { return (_Float16)__builtin_amdgcn_fmed3f(v, -65504.f, 65504.f); }
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-template <int FMT> __device__ __forceinline__ void load_llr8(const void *base, size_t i, half8 &h) {
+typedef float float8 __attribute__((ext_vector_type(8)));
+
+// a lam cell of type LT: what a float becomes when it is stored (fp16: saturated and rounded; f32: itself), eight cells at once
+template <typename LT> struct Cell;
+template <> struct Cell<_Float16> {
+    typedef half8 vec8;
+    static __device__ __forceinline__ _Float16 of(float v) { return sat16(v); }
+    static __device__ __forceinline__ void st8(_Float16 *p, const half8 &h) { *reinterpret_cast<half8 *>(p) = h; }
+    static __device__ __forceinline__ half8 ld8(const _Float16 *p) { return *reinterpret_cast<const half8 *>(p); }
+};
+template <> struct Cell<float> {
+    typedef float8 vec8;
+    static __device__ __forceinline__ float of(float v) { return v; }
+    static __device__ __forceinline__ void st8(float *p, const float8 &h) {      // two 16-byte LDS stores
+        *reinterpret_cast<float4 *>(p) = make_float4(h[0], h[1], h[2], h[3]);
+        *reinterpret_cast<float4 *>(p + 4) = make_float4(h[4], h[5], h[6], h[7]);
+    }
+    static __device__ __forceinline__ float8 ld8(const float *p) {
+        const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
+        float8 h;
+        h[0] = a.x; h[1] = a.y; h[2] = a.z; h[3] = a.w; h[4] = b.x; h[5] = b.y; h[6] = b.z; h[7] = b.w;
+        return h;
+    }
+};
+
+// eight channel LLRs as lam cells (16-byte requests)
+template <typename LT, int FMT> __device__ __forceinline__ void load_llr8(const void *base, size_t i, typename Cell<LT>::vec8 &h) {
     if constexpr (FMT == LLR_F64) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) h[k] = sat16((float)reinterpret_cast<const double *>(base)[i + k]);
+        for (int k = 0; k < 8; k++) h[k] = Cell<LT>::of((float)reinterpret_cast<const double *>(base)[i + k]);
     } else if constexpr (FMT == LLR_F16) {
         const half8 v = *reinterpret_cast<const half8 *>(reinterpret_cast<const _Float16 *>(base) + i);
 #pragma unroll
-        for (int k = 0; k < 8; k++) h[k] = sat16((float)v[k]);
+        for (int k = 0; k < 8; k++) h[k] = Cell<LT>::of((float)v[k]);
     } else {
         const float4 a = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + i);
         const float4 b = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + i + 4);
-        h[0] = sat16(a.x); h[1] = sat16(a.y); h[2] = sat16(a.z); h[3] = sat16(a.w);
-        h[4] = sat16(b.x); h[5] = sat16(b.y); h[6] = sat16(b.z); h[7] = sat16(b.w);
+        h[0] = Cell<LT>::of(a.x); h[1] = Cell<LT>::of(a.y); h[2] = Cell<LT>::of(a.z); h[3] = Cell<LT>::of(a.w);
+        h[4] = Cell<LT>::of(b.x); h[5] = Cell<LT>::of(b.y); h[6] = Cell<LT>::of(b.z); h[7] = Cell<LT>::of(b.w);
     }
 }
 
-typedef __attribute__((address_space(3))) _Float16 *lds_half_t;
-__device__ __forceinline__ lds_half_t lds_cell(uint32_t byte_addr) { return (lds_half_t)(uintptr_t)byte_addr; }
+template <typename LT> __device__ __forceinline__ __attribute__((address_space(3))) LT *lds_cell(uint32_t byte_addr) {
+    return (__attribute__((address_space(3))) LT *)(uintptr_t)byte_addr;
+}
 
 // one check row: layered_lds.hip lds_row with the row's weight per LANE (deg <= D; EXACT: every lane's row has weight D).  cp: this
 // lane's entry of edge 0 in the column table, edge k at cp[k T]; wd: the heaviest row of the wave (entries past it are not read).
-template <int D, bool EXACT, bool FIRST>
+template <typename LT, int D, bool EXACT, bool FIRST>
 __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint32_t lam0, const CsrRec &in, CsrRec &out, bool &odd, bool &flip) {
     uint32_t ad[D];
     float l[D], t[D];
@@ -91,10 +125,10 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
         const uint32_t c = (EXACT || k < wd) ? (uint32_t)cp[(size_t)k * T] : (uint32_t)kNoEdge;
         const bool v = EXACT || c != kNoEdge;       // (the neutral entries are the last ones of a row)
         if constexpr (!EXACT) deg += v ? 1 : 0;
-        ad[k] = lam0 + 2u * (v ? c : 0u);
+        ad[k] = lam0 + (uint32_t)sizeof(LT) * (v ? c : 0u);
     }
 #pragma unroll
-    for (int k = 0; k < D; k++) l[k] = (float)*lds_cell(ad[k]);
+    for (int k = 0; k < D; k++) l[k] = (float)*lds_cell<LT>(ad[k]);
     bool par = false;
     uint32_t X = 0;
     float m1 = INFINITY, m2 = INFINITY;
@@ -128,9 +162,9 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
             const uint32_t nmb = __builtin_amdgcn_bitop3_b32(ismin ? c2 : c1, __float_as_uint(t[k]), 0x80000000u, 0x78);   // a ^ (b & c)
             nidx = ismin ? (uint32_t)k : nidx;
             tsig = __builtin_amdgcn_alignbit(tsig, __float_as_uint(t[k]), 31);
-            const _Float16 nw = sat16(t[k] + __uint_as_float(nmb));
-            flip |= (nw > (_Float16)0) != hard(l[k]);
-            *lds_cell(ad[k]) = nw;
+            const LT nw = Cell<LT>::of(t[k] + __uint_as_float(nmb));
+            flip |= (nw > (LT)0) != hard(l[k]);
+            *lds_cell<LT>(ad[k]) = nw;
         }
     }
     const uint32_t nsig = tsig ^ (fl ? ((1u << deg) - 1u) : 0u);
@@ -138,28 +172,28 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
 }
 
 // the instance for a wave: wd = its heaviest row, uni = all its rows have that weight
-template <int DCLASS, bool FIRST>
+template <typename LT, int DCLASS, bool FIRST>
 __device__ __forceinline__ void csr_row_at(const uint16_t *cp, int T, int wd, bool uni, uint32_t lam0, const CsrRec &in, CsrRec &out, bool &odd, bool &flip) {
     if (uni) {
         switch (wd) {
-            case 2: csr_row<2, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 3: csr_row<3, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 4: csr_row<4, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 5: csr_row<5, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 6: csr_row<6, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 7: csr_row<7, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 8: csr_row<8, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 2: csr_row<LT, 2, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 3: csr_row<LT, 3, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 4: csr_row<LT, 4, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 5: csr_row<LT, 5, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 6: csr_row<LT, 6, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 7: csr_row<LT, 7, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 8: csr_row<LT, 8, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
             default: break;
         }
     }
     if (wd <= 0) { out = in; return; }                  // (a wave of idle lanes or empty rows)
-    if (wd <= 4) { csr_row<4, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
-    if (wd <= 8) { csr_row<8, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
+    if (wd <= 4) { csr_row<LT, 4, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
+    if (wd <= 8) { csr_row<LT, 8, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
     if constexpr (DCLASS >= 20) {
-        if (wd <= 12) { csr_row<12, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
-        if (wd <= 20) { csr_row<20, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
+        if (wd <= 12) { csr_row<LT, 12, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
+        if (wd <= 20) { csr_row<LT, 20, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
     }
-    if constexpr (DCLASS >= 32) csr_row<27, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip);
+    if constexpr (DCLASS >= 32) csr_row<LT, 27, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip);
 }
 
 }  // namespace
@@ -167,13 +201,15 @@ __device__ __forceinline__ void csr_row_at(const uint16_t *cp, int T, int wd, bo
 // block = T threads (a multiple of 64, at most csr_max_threads); grid = resident workgroups (persistent).  Rows above weight 20 keep
 // up to 27 addresses, LLRs and differences per lane: that instance is built for 512 threads (256 registers per lane, no spill).
 constexpr int csr_max_threads(int dclass) { return dclass > 20 ? 512 : 1024; }
-template <int DCLASS>
+template <int DCLASS, typename LT = _Float16>
 __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(CsrLayDev g, CsrRec *rec_all, CsrLayArgs A) {
+    typedef typename Cell<LT>::vec8 cell8;
+    constexpr bool kVeto = kVetoesNonFinite<float, LDPC_V_MINSUM> && sizeof(LT) == 4;    // (fp16 lam saturates by its own rule)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    _Float16 *lam = reinterpret_cast<_Float16 *>(smem);
+    LT *lam = reinterpret_cast<LT *>(smem);
     // [0] next frame; [1..3] "sweep n moved" at 1 + n % 3 (cleared by thread 0 two sweeps before its use); [4] "the channel's hard
-    // decisions are not a codeword"
-    int *ctl = reinterpret_cast<int *>(smem + (((size_t)g.N * 2 + 15) & ~(size_t)15));
+    // decisions are not a codeword"; [5] (f32 lam) "some LLR of the frame that just stopped is not finite"
+    int *ctl = reinterpret_cast<int *>(smem + (((size_t)g.N * sizeof(LT) + 15) & ~(size_t)15));
     const int T = g.T, tid = threadIdx.x;
     const int W = T >> 6, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nslab = ((ctab_t)g.step_ptr)[g.nstep];
@@ -182,25 +218,25 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
     int frame = blockIdx.x;
     while (frame < A.batch) {
         const size_t fN = (size_t)frame * g.N;
-        // ---- lam <- channel LLRs, as stored: saturated, rounded to fp16 (eight per lane and request when the frame is 16-byte aligned)
+        // ---- lam <- channel LLRs, as stored: saturated, rounded to fp16 / the float (eight per lane and request when the frame is 16-byte aligned)
         const bool wide = (g.N & 7) == 0 && A.llr_fmt != LLR_F64 && !A.final_lam &&
                           (((uintptr_t)A.llr + fN * (A.llr_fmt == LLR_F16 ? 2 : 4)) & 15) == 0 && (((uintptr_t)A.bits + fN) & 7) == 0;   // (uniform)
         if (wide) {
             with_llr_format(A.llr_fmt, [&](auto fmt) {
 #pragma unroll 4
                 for (int i = tid * 8; i < g.N; i += T * 8) {
-                    half8 h;
-                    load_llr8<decltype(fmt)::value>(A.llr, fN + i, h);
-                    *reinterpret_cast<half8 *>(lam + i) = h;
+                    cell8 h;
+                    load_llr8<LT, decltype(fmt)::value>(A.llr, fN + i, h);
+                    Cell<LT>::st8(lam + i, h);
                 }
             });
         } else {
             with_llr_format(A.llr_fmt, [&](auto fmt) {
 #pragma unroll 8
-                for (int i = tid; i < g.N; i += T) lam[i] = sat16(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
+                for (int i = tid; i < g.N; i += T) lam[i] = Cell<LT>::of(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
             });
         }
-        if (tid == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; ctl[4] = 0; }
+        if (tid == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; ctl[4] = 0; if constexpr (kVeto) ctl[5] = 0; }
         lds_barrier();
         bool conv = false;
         int n = 0;
@@ -212,7 +248,7 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
                 bool par = false;
                 for (int k = 0; k < wd; k++) {
                     const uint32_t c = cp[(size_t)k * T];
-                    if (c != kNoEdge) par ^= *lds_cell(lam0 + 2u * c) > (_Float16)0;
+                    if (c != kNoEdge) par ^= *lds_cell<LT>(lam0 + (uint32_t)sizeof(LT) * c) > (LT)0;
                 }
                 odd |= par;
             }
@@ -232,10 +268,10 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
                         CsrRec out;
                         if (n == 1) {
                             const CsrRec none{0.f, 0.f, 0u};
-                            csr_row_at<DCLASS, true>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, none, out, odd, flip);
+                            csr_row_at<LT, DCLASS, true>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, none, out, odd, flip);
                         } else {
                             const CsrRec in = rec[(size_t)s * T];
-                            csr_row_at<DCLASS, false>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, in, out, odd, flip);
+                            csr_row_at<LT, DCLASS, false>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, in, out, odd, flip);
                         }
                         rec[(size_t)s * T] = out;
                     }
@@ -245,24 +281,35 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
                 if (ctl[1 + n % 3] == 0) { conv = true; break; }
             }
             if (n > A.max_iters) n = A.max_iters;
+            if constexpr (kVeto) {
+                // LLRs that left the float range: failed, not "converged" (ldpc_math.h).  Once per frame; `conv` comes from a control
+                // word every thread read after a barrier, so it is workgroup-uniform and every wave reaches the barrier below
+                if (conv) {
+                    bool bad = false;
+                    for (int i = tid; i < g.N; i += T) bad |= not_finite(lam[i]);
+                    if (__builtin_amdgcn_ballot_w64(bad) != 0 && (tid & 63) == 0) ctl[5] = 1;
+                    lds_barrier();
+                    conv = ctl[5] == 0;
+                }
+            }
         }
-        // ---- result: hard(lam) of a frame that stopped by the rule, the channel's decisions (as stored: fp16) otherwise (Orig.hs:69-70)
+        // ---- result: hard(lam) of a frame that stopped by the rule, the channel's decisions (as stored) otherwise (Orig.hs:69-70)
         if (wide) {
-            auto put = [&](int i, const half8 &h) {
+            auto put = [&](int i, const cell8 &h) {
                 uint32_t lo = 0, hi = 0;
 #pragma unroll
-                for (int k = 0; k < 4; k++) { lo |= (h[k] > (_Float16)0 ? 1u : 0u) << (8 * k); hi |= (h[k + 4] > (_Float16)0 ? 1u : 0u) << (8 * k); }
+                for (int k = 0; k < 4; k++) { lo |= (h[k] > (LT)0 ? 1u : 0u) << (8 * k); hi |= (h[k + 4] > (LT)0 ? 1u : 0u) << (8 * k); }
                 *reinterpret_cast<uint2 *>(A.bits + fN + i) = make_uint2(lo, hi);
             };
             if (conv) {
 #pragma unroll 4
-                for (int i = tid * 8; i < g.N; i += T * 8) put(i, *reinterpret_cast<const half8 *>(lam + i));
+                for (int i = tid * 8; i < g.N; i += T * 8) put(i, Cell<LT>::ld8(lam + i));
             } else {
                 with_llr_format(A.llr_fmt, [&](auto fmt) {
 #pragma unroll 4
                     for (int i = tid * 8; i < g.N; i += T * 8) {
-                        half8 h;
-                        load_llr8<decltype(fmt)::value>(A.llr, fN + i, h);
+                        cell8 h;
+                        load_llr8<LT, decltype(fmt)::value>(A.llr, fN + i, h);
                         put(i, h);
                     }
                 });
@@ -271,7 +318,7 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
             with_llr_format(A.llr_fmt, [&](auto fmt) {
 #pragma unroll 4
                 for (int i = tid; i < g.N; i += T) {
-                    const float v = conv ? (float)lam[i] : (float)sat16(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
+                    const float v = conv ? (float)lam[i] : (float)Cell<LT>::of(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
                     A.bits[fN + i] = v > 0.f ? 1 : 0;
                     if (A.final_lam) A.final_lam[fN + i] = (double)v;
                 }
@@ -291,14 +338,17 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
 namespace {
 
 int dclass_of(int max_row_deg) { return max_row_deg <= 8 ? 8 : (max_row_deg <= 20 ? 20 : 32); }
-size_t lds_bytes_for(const ldpc_code &c) { return (((size_t)c.N * 2 + 15) & ~(size_t)15) + 32; }
-const void *pick_kernel(int dclass) {
-    return dclass == 8 ? (const void *)layered_csr_kernel<8> : dclass == 20 ? (const void *)layered_csr_kernel<20> : (const void *)layered_csr_kernel<32>;
+size_t lds_bytes_for(const ldpc_code &c, int dtype) { return (((size_t)c.N * (dtype == LDPC_F32 ? 4 : 2) + 15) & ~(size_t)15) + 32; }
+typedef void (*csr_kernel_t)(CsrLayDev, CsrRec *, CsrLayArgs);
+template <typename LT> csr_kernel_t kernel_for(int dclass) {
+    return dclass == 8 ? layered_csr_kernel<8, LT> : dclass == 20 ? layered_csr_kernel<20, LT> : layered_csr_kernel<32, LT>;
 }
+csr_kernel_t pick_kernel(int dclass, bool f32) { return f32 ? kernel_for<float>(dclass) : kernel_for<_Float16>(dclass); }
 
 // ------------------------------------------------------------------ host side
 struct LayeredCsrState : Backend {
     int max_batch = 0, dclass = 8, grid = 0, nslab = 0;
+    bool f32 = false;           // lam cells are floats (LDPC_F32), not fp16
     size_t lds = 0;
     CsrLayDev g{};
     uint16_t *d_cols = nullptr;
@@ -312,7 +362,8 @@ struct LayeredCsrState : Backend {
     int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                uint8_t *d_conv, double *d_final, double *d_trace) override;
     int step(hipStream_t, int, const double *, const double *, const double *, double *, double *, uint8_t *) override {
-        return set_error(LDPC_EUNSUPPORTED, "no teacher-forced step with fp16 lam storage (the record kernels keep no per-edge messages)");
+        return set_error(LDPC_EUNSUPPORTED, f32 ? "no teacher-forced step on the on-chip layered kernel for any H (the record kernels keep no per-edge messages)"
+                                                : "no teacher-forced step with fp16 lam storage (the record kernels keep no per-edge messages)");
     }
     bool reads_llr_once(int) const override { return true; }
 };
@@ -321,22 +372,22 @@ struct LayeredCsrState : Backend {
 
 const char *layered_csr_why_not(const ldpc_code &c, int variant, int dtype) {
     if (variant != LDPC_MINSUM) return "the on-chip layered kernel for any H implements min-sum";
-    if (dtype != LDPC_F16) return "the on-chip layered kernel for any H stores lam in fp16 (LDPC_F16)";
+    if (dtype != LDPC_F16 && dtype != LDPC_F32) return "the on-chip layered kernel for any H stores lam in fp16 (LDPC_F16) or in f32 (LDPC_F32)";
     if (c.max_row_deg > 27) return "check rows above weight 27 (a row record holds 27 sign bits)";
-    if (lds_bytes_for(c) > 160 * 1024) return "a frame's fp16 LLRs exceed the 160 KB of LDS";
+    if (lds_bytes_for(c, dtype) > 160 * 1024) return dtype == LDPC_F32 ? "a frame's f32 LLRs exceed the 160 KB of LDS" : "a frame's fp16 LLRs exceed the 160 KB of LDS";
     if (c.N > 65535) return "more than 65 535 columns (16-bit column table)";
     const char *e = getenv("LDPC_LAYERED_CSR");
     if (e && !strcmp(e, "0")) return "disabled (LDPC_LAYERED_CSR=0)";
     return nullptr;
 }
 
-Backend *layered_csr_create(const ldpc_code &c, int max_batch) {
+Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch) {
     LayeredCsrState *s = new (std::nothrow) LayeredCsrState();
     if (!s) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
     try {
         // lam stays on-chip for the whole decode in one launch (only the row records travel to HBM): reported as the on-chip path
         s->path = LDPC_PATH_FUSED;
-        s->max_batch = max_batch; s->dclass = dclass_of(c.max_row_deg);
+        s->max_batch = max_batch; s->dclass = dclass_of(c.max_row_deg); s->f32 = dtype == LDPC_F32;
         // barrier steps: maximal runs of consecutive layers that share no column
         std::vector<std::vector<int>> steps;
         {
@@ -386,8 +437,8 @@ Backend *layered_csr_create(const ldpc_code &c, int max_batch) {
         }
         s->nslab = (int)(slab.size() / 2);
         s->g.N = c.N; s->g.T = T; s->g.nstep = (int)steps.size();
-        s->lds = lds_bytes_for(c);
-        const void *kern = pick_kernel(s->dclass);
+        s->lds = lds_bytes_for(c, dtype);
+        const void *kern = (const void *)pick_kernel(s->dclass, s->f32);
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds);
         int per_cu = 0, dev = 0;
         hipDeviceProp_t prop;
@@ -413,7 +464,7 @@ Backend *layered_csr_create(const ldpc_code &c, int max_batch) {
             return nullptr;
         }
         s->g.cols = s->d_cols; s->g.slab = s->d_slab; s->g.wdeg = s->d_wdeg; s->g.step_ptr = s->d_step;
-        snprintf(s->info.name, sizeof(s->info.name), "ldpc::layered_csr_kernel<%d>", s->dclass);
+        snprintf(s->info.name, sizeof(s->info.name), s->f32 ? "ldpc::layered_csr_kernel<%d, float>" : "ldpc::layered_csr_kernel<%d>", s->dclass);
         s->info.threads = T; s->info.frames_per_wg = 1;
         return s;
     } catch (...) { delete s; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
@@ -429,9 +480,7 @@ int LayeredCsrState::decode(hipStream_t st, int max_iters, int batch, const void
     if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
     const dim3 grid(std::min(batch, this->grid)), block(g.T);
     if (timer) timer->begin(st);
-    if (dclass == 8) hipLaunchKernelGGL(layered_csr_kernel<8>, grid, block, lds, st, g, rec, a);
-    else if (dclass == 20) hipLaunchKernelGGL(layered_csr_kernel<20>, grid, block, lds, st, g, rec, a);
-    else hipLaunchKernelGGL(layered_csr_kernel<32>, grid, block, lds, st, g, rec, a);
+    hipLaunchKernelGGL(pick_kernel(dclass, f32), grid, block, lds, st, g, rec, a);
     if (timer) timer->end(st);
     e = hipGetLastError();
     if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr launch: %s", hipGetErrorString(e));

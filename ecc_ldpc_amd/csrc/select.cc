@@ -14,8 +14,12 @@
 //   (5) layered_lds.hip   layered min-sum with fp16 lam storage whose frame fits LDS: lam on-chip, row records streamed
 //   (6) layered_qc.hip    QC codes, either schedule: one workgroup per frame
 //   (7) flood.hip         any H, batch-major (lane = frame): flooding and layered schedules, fp16 storage, the parity modes
-// Layered min-sum with fp16 lam storage where none of the above serves it (LDPC_PATH_AUTO or LDPC_PATH_FUSED; reported as FUSED):
-//   (8) layered_csr.hip   any H whose frame fits LDS in fp16: lam on-chip, row records streamed, layers merged into barrier steps
+// Layered min-sum where none of the above serves it (reported as FUSED):
+//   (8) layered_csr.hip   any H whose frame fits LDS: lam on-chip, row records streamed, layers merged into barrier steps
+//                         - lam as fp16 (LDPC_F16, N <= 65 535): LDPC_PATH_AUTO or LDPC_PATH_FUSED
+//                         - lam as f32 (LDPC_F32, N <= 40 952): LDPC_PATH_FUSED only.  LDPC_PATH_AUTO keeps such a context on (7): that
+//                           routing follows a measurement of this instance against flood.hip's layered kernel on the same frames and
+//                           layers (tools/layered_csr_rate.py --lam f32), it does not precede it
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -182,11 +186,17 @@ Backend *make_backend(const ldpc_code &c, const ldpc_code_dev &tabs, int variant
     const char *onchip_why = layered ? fused_layered_why_not(c, variant, dtype) : parity ? "parity mode" : fused_why_not(c, variant, dtype);
     const char *csr_why = "";   // why the on-chip layered kernel for any H does not serve this context ("" = not considered)
     if (layered) {
-        // (8) layered_csr.hip: fp16 lam storage on-chip for ANY H -- only where no kernel above serves the request: no on-chip QC kernel,
+        // (8) layered_csr.hip, lam on-chip for ANY H; its fp16-lam instances -- only where no kernel above serves the request: no on-chip QC kernel,
         // and under LDPC_PATH_AUTO no HBM kernel of a QC code either (an explicit LDPC_PATH_FLOOD keeps the state in HBM and is refused)
         if (dtype == LDPC_F16 && onchip_why && path != LDPC_PATH_FLOOD && (path == LDPC_PATH_FUSED || layered_qc_why_not(c, variant, dtype, 0) != nullptr)) {
             csr_why = layered_csr_why_not(c, variant, dtype);
-            if (!csr_why) return layered_csr_create(c, max_batch);
+            if (!csr_why) return layered_csr_create(c, dtype, max_batch);
+        }
+        // its f32-lam instances: on an explicit LDPC_PATH_FUSED only, and only where no on-chip QC kernel exists for the request (a QC code
+        // whose on-chip kernel fails to compile still fails under LDPC_PATH_FUSED); LDPC_PATH_AUTO is not re-routed (see the ladder above)
+        if (dtype == LDPC_F32 && onchip_why && path == LDPC_PATH_FUSED) {
+            csr_why = layered_csr_why_not(c, variant, dtype);
+            if (!csr_why) return layered_csr_create(c, dtype, max_batch);
         }
         if (dtype == LDPC_F16 && (onchip_why || path == LDPC_PATH_FLOOD)) {
             // from HBM: lam stored in fp16 for the frame-per-workgroup min-sum record kernel of QC codes (r03); nothing else

@@ -59,7 +59,10 @@ typedef struct ldpc_ctx ldpc_ctx;   /* one decoder replica: device buffers + str
  * Parity mode only: LDPC_F32, flooding schedule, flood path, rows up to weight 32 (checker: oracle "cuda32"). */
 typedef enum { LDPC_TANH = 0, LDPC_MINSUM = 1, LDPC_TANH_CM = 2, LDPC_TANH_CUDA32 = 3 } ldpc_variant;
 /* arithmetic / storage type of LLRs and messages on the device.
- * F32: the cudabits kernels' `typedef float float_ty` (cudabits/common.h:1).
+ * F32: the cudabits kernels' `typedef float float_ty` (cudabits/common.h:1).  With LDPC_SCHED_LAYERED, min-sum and
+ *      LDPC_PATH_FUSED on an H no quasi-cyclic kernel takes, whose frame fits the LDS as f32 (4 N + 32 B <= 160 KB: N <= 40 952):
+ *      csrc/layered_csr.hip with lam kept as f32 in LDS -- bit for bit the LDPC_PATH_FLOOD decoder of the same context; a frame whose
+ *      LLRs leave the float range is failed, never reported converged (non-finite veto).
  * F64: parity mode, same type as the CPU reference (Double).
  * F16: fp16 storage of whatever the decoder keeps in HBM, fp32 arithmetic (BASELINE.json configs[3]):
  *      every LLR given to an F16 context counts as stored in fp16 (saturating round-to-nearest-even on load);
@@ -106,7 +109,9 @@ typedef enum {
                             STORED in fp16 in LDS for the whole decode, row records streamed through an HBM scratch area) --
                             reported as FUSED because lam never leaves the chip, unlike the QC long-code kernel
                             layered_lds.hip, which also keeps lam in LDS but reports FLOOD; an explicit LDPC_PATH_FLOOD
-                            still refuses LDPC_F16 layered on such a code                                                  */
+                            still refuses LDPC_F16 layered on such a code.  The same kernel with lam as f32 (LDPC_F32 min-sum,
+                            N <= 40 952) is taken on an explicit LDPC_PATH_FUSED only: LDPC_PATH_AUTO keeps LDPC_F32 layered
+                            contexts of such codes on the HBM path                                                         */
 } ldpc_path;
 
 /* ---- library life-cycle -------------------------------------------------------------------

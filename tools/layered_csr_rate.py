@@ -5,10 +5,14 @@
   (b) flood.hip, f32 layered (path="flood"), same code, layers and frames;
   (c) layered_lds.hip on codes/dvbs2like.64800.1.2 (the quasi-cyclic reference);
   and layered_csr on codes/1920.1280.3.303 in file order and in helper order (with (b) for it).
+  --lam f32|f16|both: the f32-lam instances (layered_csr_kernel<D, float>, path="fused") next to the fp16-lam ones and flood.hip f32
+  layered, on identical frames and layers, at 1.5 / 2.0 / 2.5 dB: codes/1920.1280.3.303 and the DVB-S2 short-frame structure
+  (tests/dvbs2_short.py), both in helper order.  The legs of one point take turns launch by launch (warm-up launch first).
 Decoded-information Gbit/s = frames x k / kernel time (HIP events around the decode kernel, the median of the timed launches);
 frames: the all-zero codeword + AWGN, f32 LLRs generated on the device.
 
-usage: python tools/layered_csr_rate.py [--frames 16384] [--reps 3] [--quick]"""
+usage: python tools/layered_csr_rate.py [--frames 16384] [--reps 3] [--quick] [--lam f32|f16|both [--lam-only]] [--asm FILE]
+(profiles/r07_layered_csr_f32_rate.txt: --lam both --lam-only --reps 5)"""
 from __future__ import annotations
 
 import argparse
@@ -27,18 +31,19 @@ import torch  # noqa: E402
 
 import ecc_ldpc_amd as E  # noqa: E402
 from oracle import channel, formats  # noqa: E402
-from tests import dvbs2_natural  # noqa: E402
+from tests import dvbs2_natural, dvbs2_short  # noqa: E402
 
 ASM = os.path.join(ROOT, "ecc_ldpc_amd", "build", "layered_csr-hip-amdgcn-amd-amdhsa-gfx950.s")
 
 
-def kernel_resources(dclass):
-    """(vgpr_count, private_segment_fixed_size) of layered_csr_kernel<dclass> from the device assembly the build keeps"""
+def kernel_resources(dclass, lam="f16"):
+    """(vgpr_count, private_segment_fixed_size) of layered_csr_kernel<dclass, lam cell type> from the device assembly the build keeps
+    (the cell type is part of the mangled name: DF16_ = _Float16, f = float)"""
     try:
         text = open(ASM).read()
     except OSError:
         return None, None
-    m = re.search(r"\.name:\s+_ZN4ldpc18layered_csr_kernelILi%dE\S*\n((?:\s+\.[a-z_]+:.*\n)+)" % dclass, text)
+    m = re.search(r"\.name:\s+_ZN4ldpc18layered_csr_kernelILi%dE%sEE\S*\n((?:\s+\.[a-z_]+:.*\n)+)" % (dclass, "f" if lam == "f32" else "DF16_"), text)
     if not m:
         return None, None
     f = dict(re.findall(r"\.([a-z_]+):\s+(\d+)", m.group(1)))
@@ -49,37 +54,96 @@ def device_frames(F, N, k, db, seed):
     s2 = channel.sigma2(db, k, N)
     g = torch.Generator(device="cuda").manual_seed(seed)
     y = -1.0 + torch.randn((F, N), generator=g, device="cuda", dtype=torch.float32) * float(np.sqrt(s2))
-    return (2.0 / s2) * y
+    llr = (2.0 / s2) * y
+    torch.cuda.synchronize()     # the decoders run on their own stream: the frames are complete before the first launch reads them
+    return llr
 
 
 def rate(dec, llr, k, max_iters, reps):
-    F, N = llr.shape
-    bits = torch.empty((F, N), dtype=torch.uint8, device="cuda")
-    iters = torch.empty(F, dtype=torch.int32, device="cuda")
-    conv = torch.empty(F, dtype=torch.uint8, device="cuda")
-    dec.set_timing(True)
-    dec.decode_batch_dev(llr.data_ptr(), bits.data_ptr(), F, max_iters, iters.data_ptr(), conv.data_ptr())   # warm-up
-    dec.synchronize()
-    dec.kernel_time()
-    times = []
-    for _ in range(reps):
-        dec.decode_batch_dev(llr.data_ptr(), bits.data_ptr(), F, max_iters, iters.data_ptr(), conv.data_ptr())
-        dec.synchronize()
-        n, ms = dec.kernel_time()
-        times.append(ms / max(n, 1))
-    ms = statistics.median(times)
-    return {"ms": ms, "gbps": F * k / (ms * 1e-3) / 1e9, "sweeps": float(iters.float().mean()), "conv": float(conv.float().mean()),
-            "bits": bits}
+    return rates_in_turn([dec], llr, k, max_iters, reps)[0]
 
 
 def describe(dec, lds=None):
     t, f = dec.kernel_geometry
     s = f"{dec.kernel_name} path={dec.path} threads/wg={t} frames/wg={f}"
-    m = re.search(r"layered_csr_kernel<(\d+)>", dec.kernel_name)
+    m = re.search(r"layered_csr_kernel<(\d+)(, float)?>", dec.kernel_name)
     if m:
-        v, sc = kernel_resources(int(m.group(1)))
+        v, sc = kernel_resources(int(m.group(1)), "f32" if m.group(2) else "f16")
         s += f" LDS={lds} B VGPRs={v} scratch={sc} B"
     return s
+
+
+def rates_in_turn(decs, llr, k, max_iters, reps):
+    """several contexts on the same frames: a warm-up launch each, then `reps` timed launches each, taking turns (what else runs on the
+    machine then falls on all legs alike).  -> per context: the median kernel time (HIP events) and its spread, the rate, and the mean
+    sweeps, converged share and bits of its last launch"""
+    F, N = llr.shape
+    bits = torch.empty((F, N), dtype=torch.uint8, device="cuda")
+    iters = torch.empty(F, dtype=torch.int32, device="cuda")
+    conv = torch.empty(F, dtype=torch.uint8, device="cuda")
+    times, stats = [[] for _ in decs], []
+    for r in range(reps + 1):                                           # r == 0: warm-up
+        for j, dec in enumerate(decs):
+            dec.set_timing(True)
+            dec.decode_batch_dev(llr.data_ptr(), bits.data_ptr(), F, max_iters, iters.data_ptr(), conv.data_ptr())
+            dec.synchronize()
+            n, ms = dec.kernel_time()
+            if r:
+                times[j].append(ms / max(n, 1))
+            if r == reps:
+                stats.append((float(iters.float().mean()), float(conv.float().mean()), bits.clone()))
+    out = []
+    for j in range(len(decs)):
+        ms = statistics.median(times[j])
+        out.append({"ms": ms, "min": min(times[j]), "max": max(times[j]), "gbps": F * k / (ms * 1e-3) / 1e9, "sweeps": stats[j][0],
+                    "conv": stats[j][1], "bits": stats[j][2]})
+    return out
+
+
+def all_resources(out):
+    """the six instances' registers and scratch, from the assembly the build keeps"""
+    for lam in ("f16", "f32"):
+        for d in (8, 20, 32):
+            v, sc = kernel_resources(d, lam)
+            out(f"#   layered_csr_kernel<{d}{', float' if lam == 'f32' else ''}>: VGPRs={v} scratch={sc} B")
+
+
+def lam_comparison(a, out):
+    """f32 lam / fp16 lam / flood.hip f32 layered on identical frames and layers"""
+    F, MI = a.frames, a.max_iters
+    H = formats.read_alist_mackay(open(os.path.join(ROOT, "codes", "1920.1280.3.303")).read())
+    rp3 = np.concatenate([[0], np.cumsum(H.sum(1))]).astype(np.int32)
+    ci3 = np.nonzero(H)[1].astype(np.int32)
+    rps, cis = dvbs2_short.csr()
+    out(f"# lam cell type comparison (--lam {a.lam}): {F} frames, {MI} sweeps at most, {a.reps} timed launches per leg (median [min..max]), "
+        "legs alternating, f32 LLRs on the device, helper order")
+    all_resources(out)
+    for label, rp, ci, N, k, seed in (("1920.1280.3.303", rp3, ci3, H.shape[1], 640, 23), ("dvbs2-short", rps, cis, dvbs2_short.N, dvbs2_short.K, 29)):
+        perm, lp = E.Code.csr_layer_order(rp, ci, N)
+        prp, pci = E.Code.permute_rows(rp, ci, perm)
+        code = E.Code.from_csr(prp, pci, N)
+        code.set_layers(lp)
+        legs = []
+        if a.lam in ("f32", "both"):
+            legs.append(("f32 lam ", E.Decoder(code, "min", "f32", F, schedule="layered", path="fused"), ((4 * N + 15) // 16) * 16 + 32))
+        if a.lam in ("f16", "both"):
+            legs.append(("fp16 lam", E.Decoder(code, "min", "f16", F, schedule="layered", path="fused"), ((2 * N + 15) // 16) * 16 + 32))
+        legs.append(("flood   ", E.Decoder(code, "min", "f32", F, schedule="layered", path="flood"), None))
+        out(f"{label} N={N} M={len(rp) - 1} E={len(ci)} k={k} layers (helper order)={len(lp) - 1}")
+        for name, dec, lds in legs:
+            out(f"  {name}: {describe(dec, lds)}")
+        for db in (1.5, 2.0, 2.5):
+            llr = device_frames(F, N, k, db, seed)
+            res = rates_in_turn([d for _, d, _ in legs], llr, k, MI, a.reps)
+            for (name, _, _), r in zip(legs, res):
+                out(f"  {db:.1f} dB {name}: {r['gbps']:.2f} Gbit/s  {r['ms']:.2f} ms [{r['min']:.2f}..{r['max']:.2f}]  sweeps {r['sweeps']:.2f}  converged {r['conv']:.4f}")
+            if a.lam in ("f32", "both"):
+                same = bool(torch.equal(res[0]["bits"], res[-1]["bits"]))
+                out(f"  {db:.1f} dB f32 lam / flood: {res[0]['gbps'] / res[-1]['gbps']:.2f}x  (decoded bits identical: {same})")
+            del llr, res
+            torch.cuda.empty_cache()
+        for _, dec, _ in legs:
+            dec.close()
 
 
 def main():
@@ -88,10 +152,21 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--max-iters", type=int, default=50)
     ap.add_argument("--quick", action="store_true", help="(a) at 2 dB only (profiler runs)")
+    ap.add_argument("--lam", choices=("f32", "f16", "both"), help="add the lam cell type comparison with these on-chip legs")
+    ap.add_argument("--lam-only", action="store_true", help="only the --lam comparison")
+    ap.add_argument("--asm", help="the device assembly of layered_csr.hip, where the build directory's copy is not at hand")
     a = ap.parse_args()
+    if a.asm:
+        global ASM
+        ASM = a.asm
     E.init(0)
     F, MI = a.frames, a.max_iters
     out = lambda s: print(s, flush=True)   # noqa: E731
+    if a.lam_only:
+        a.lam = a.lam or "both"
+        lam_comparison(a, out)
+        E.close_all()
+        return
     out(f"# layered_csr rate: {F} frames, {MI} sweeps at most, {a.reps} timed launches (median), f32 LLRs on the device")
 
     # ---- DVB-S2-structured natural-order code, helper order
@@ -161,6 +236,8 @@ def main():
         r = rate(f3, llr, k3, MI, a.reps)
         out(f"  flood.hip f32 layered, {label}: {r['gbps']:.2f} Gbit/s  {r['ms']:.2f} ms  sweeps {r['sweeps']:.2f}  converged {r['conv']:.4f}")
         d3.close(); f3.close()
+    if a.lam:
+        lam_comparison(a, out)
     E.close_all()
 
 
