@@ -99,91 +99,54 @@ template <class Plan, int SZ, class T, int P, bool RS>
 __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32_t tid) {
     using S = Split<Plan, T>;
     using H = Halves<Plan>;
-    constexpr int CPW = QcGeom<SZ>::CPW, V = QcGeom<SZ>::V, VT = QcGeom<SZ>::VT;
-    constexpr int N = Plan::NBC * SZ, THREADS = Plan::NP * VT, NW = THREADS / 64;
-    constexpr uint32_t ES = 4, vmask = V * ES - 1;
-    constexpr int LAM_BYTES = (Plan::NBC * V * (int)ES + 15) / 16 * 16;
-    constexpr int NBCP = (Plan::NBC + Plan::NP - 1) / Plan::NP;
+    using F = Frame<Plan, SZ, P, LamCell<float, false>>;
+    using Where = typename F::W;
+    constexpr int CPW = F::CPW, V = F::V, VT = F::VT, NW = F::NW;
+    constexpr uint32_t ES = 4, vmask = F::vmask, FULL = F::FULL;
     if constexpr (VT != V) { if ((tid % VT) >= (uint32_t)V) return; }
     const uint32_t p4 = (tid % VT) * ES;
-    struct Where {
-        uint32_t sub, r0; long long frame; bool valid; size_t fN;
-        __device__ __forceinline__ Where(uint32_t p, int batch) {
-            asm volatile("" : "+v"(p));
-            const uint32_t lane = p / ES;
-            sub = lane % CPW;
-            r0 = lane / CPW;
-            frame = (long long)blockIdx.x * CPW + sub;
-            valid = frame < batch;
-            fN = (size_t)(valid ? frame : 0) * N;
-        }
-    };
     constexpr int NM = RS ? H::NMSG : S::NMSG;
-    constexpr uint32_t EX0 = LAM_BYTES + 4 * NW + 12;            // RS: exchange area [word 0..2][group][VT] dwords
-    constexpr uint32_t EXW = 2 * VT * ES, EXG = VT * ES;
+    constexpr uint32_t EX0 = F::EX0, EXW = F::EXW, EXG = F::EXG;   // RS: exchange area [word 0..2][group][VT] dwords
     float msg[NM];
 #pragma unroll
     for (int i = 0; i < NM; i++) msg[i] = 0.0f;
     // ---- lam <- channel LLRs: group P fills the block columns bc with bc % NP == P; their hard decisions stay in `obits`
-    typename SplitResult<NBCP>::Bits obits{};
+    typename SplitResult<F::NBCP>::Bits obits{};
     {
         const Where w(p4, A.batch);
         with_llr_format(A.llr_fmt, [&](auto fc) {
             constexpr int FMT = decltype(fc)::value;
-            static_for<0, Plan::NBC>([&](auto bcc) {
+            own_columns<Plan, P>([&](auto bcc) {
                 constexpr int bc = decltype(bcc)::value;
-                if constexpr ((bc % Plan::NP) == P) {
-                    const float v = maybe_round_f16<float>(load_llr_as<float, FMT>(A.llr, w.fN + bc * SZ + w.r0), A.llr_round16);
-                    obits.set(bc / Plan::NP, v > 0.0f);
-                    lds_st<float>(lds, p4 + (bc * V * ES), v);
-                }
+                const float v = maybe_round_f16<float>(load_llr_as<float, FMT>(A.llr, w.fN[0] + bc * SZ + w.r0), A.llr_round16);
+                obits.set(bc / Plan::NP, v > 0.0f);
+                lds_st<float>(lds, p4 + (bc * V * ES), v);
             });
         });
     }
     __syncthreads();
 
-    volatile uint32_t *flags = reinterpret_cast<volatile uint32_t *>(lds + LAM_BYTES);
-    constexpr uint32_t FULL = (1u << CPW) - 1;
+    volatile uint32_t *flags = reinterpret_cast<volatile uint32_t *>(lds + F::LAM_BYTES);
     uint32_t done = 0;     // bit s = frame s of this workgroup has finished (workgroup-uniform)
 #pragma unroll
     for (int s2 = 0; s2 < CPW; s2++) done |= ((long long)blockIdx.x * CPW + s2 < A.batch) ? 0u : (1u << s2);
-    SplitResult<NBCP> res;
+    SplitResult<F::NBCP> res;
     res.bits = obits;
     const uint32_t my_slot = (p4 / ES) % CPW;
 
     // workgroup-wide OR, per frame, of a lane flag; also the barrier between a sweep's last layer and what follows
-    auto frames_with = [&](bool lane_flag) -> uint32_t {
-        const unsigned long long ub = __ballot(lane_flag);
-        uint32_t wbits = 0;
-#pragma unroll
-        for (int s2 = 0; s2 < CPW; s2++) {
-            unsigned long long mk = 0;
-            for (int i = 0; i < 64; i += CPW) mk |= 1ull << i;
-            wbits |= ((ub & (mk << s2)) != 0ull) ? (1u << s2) : 0u;
-        }
-        if ((tid & 63) == 0) flags[tid >> 6] = wbits;
-        __syncthreads();
-        uint32_t f = 0;
-#pragma unroll
-        for (int w = 0; w < NW; w++) f |= flags[w];
-        f = __builtin_amdgcn_readfirstlane(f);
-        __syncthreads();     // (the flags are rewritten by the next call)
-        return f;
-    };
+    auto frames_with = [&](bool lane_flag) -> uint32_t { return ldpc::frames_with<CPW, NW, 1, true>(flags, tid, [&](int) { return lane_flag; }); };
     auto snapshot = [&](int n, uint32_t newly) {   // frames that stop now: hard(lam) of the lane's own columns
         if ((newly >> my_slot) & 1u) {
             LDPC_COLD_PATH();
             res.converge_at(n);
-            static_for<0, Plan::NBC>([&](auto bcc) {
+            own_columns<Plan, P>([&](auto bcc) {   // (F::hard_bits here moves this instance's register allocation)
                 constexpr int bc = decltype(bcc)::value;
-                if constexpr ((bc % Plan::NP) == P) res.bits.set(bc / Plan::NP, lds_ld<float>(lds, p4 + (bc * V * ES)) > 0.0f);
+                res.bits.set(bc / Plan::NP, lds_ld<float>(lds, p4 + (bc * V * ES)) > 0.0f);
             });
             if (A.final_lam) {
                 const Where w(p4, A.batch);
-                static_for<0, Plan::NBC>([&](auto bcc) {
-                    constexpr int bc = decltype(bcc)::value;
-                    if constexpr ((bc % Plan::NP) == P) A.final_lam[w.fN + bc * SZ + w.r0] = (double)lds_ld<float>(lds, p4 + (bc * V * ES));
-                });
+                F::store_lam(A, lds, p4, w, 0);
             }
         }
     };
@@ -191,12 +154,7 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
         if (A.trace) {
             LDPC_COLD_PATH();
             const Where w(p4, A.batch);
-            if (w.valid && !((done >> w.sub) & 1u))
-                static_for<0, Plan::NBC>([&](auto bcc) {
-                    constexpr int bc = decltype(bcc)::value;
-                    if constexpr ((bc % Plan::NP) == P)
-                        A.trace[((size_t)w.frame * (A.max_iters + 1) + n) * N + bc * SZ + w.r0] = (double)lds_ld<float>(lds, p4 + (bc * V * ES));
-                });
+            if (w.valid[0] && !((done >> w.sub) & 1u)) F::trace_frame(A, lds, p4, w, 0, n);
         }
     };
 
@@ -298,9 +256,9 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
             LDPC_COLD_PATH();
             bool nf = false;
             if ((newly >> my_slot) & 1u)
-                static_for<0, Plan::NBC>([&](auto bcc) {
+                own_columns<Plan, P>([&](auto bcc) {
                     constexpr int bc = decltype(bcc)::value;
-                    if constexpr ((bc % Plan::NP) == P) nf |= not_finite(lds_ld<float>(lds, p4 + (bc * V * ES)));
+                    nf |= not_finite(lds_ld<float>(lds, p4 + (bc * V * ES)));
                 });
             const uint32_t veto = frames_with(nf) & newly;
             done |= veto;        // stops here as a failure: `res` keeps the channel's hard decisions and a clear flag
@@ -312,28 +270,16 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
     }
 
     const Where w(p4, A.batch);
-    if (!w.valid) return;
+    if (!w.valid[0]) return;
     const bool converged = res.converged();
-    static_for<0, Plan::NBC>([&](auto bcc) {   // hard(lam) of a frame that stopped by the rule, the channel's decisions otherwise
-        constexpr int bc = decltype(bcc)::value;
-        if constexpr ((bc % Plan::NP) == P) A.bits[w.fN + bc * SZ + w.r0] = res.bits.get(bc / Plan::NP);
-    });
+    F::store_bits(A, w, 0, res);   // hard(lam) of a frame that stopped by the rule, the channel's decisions otherwise
     if (!converged && A.final_lam) {
         LDPC_COLD_PATH();
-        with_llr_format(A.llr_fmt, [&](auto fc) {
-            constexpr int FMT = decltype(fc)::value;
-            static_for<0, Plan::NBC>([&](auto bcc) {
-                constexpr int bc = decltype(bcc)::value;
-                if constexpr ((bc % Plan::NP) == P) {
-                    const size_t gi = w.fN + bc * SZ + w.r0;
-                    A.final_lam[gi] = (double)maybe_round_f16<float>(load_llr_as<float, FMT>(A.llr, gi), A.llr_round16);
-                }
-            });
-        });
+        F::store_channel_lam(A, w, 0);
     }
     if (w.r0 == 0 && P == 0) {
-        if (A.iters) A.iters[w.frame] = converged ? res.turn() : A.max_iters;
-        if (A.conv) A.conv[w.frame] = converged ? 1 : 0;
+        if (A.iters) A.iters[w.frame0] = converged ? res.turn() : A.max_iters;
+        if (A.conv) A.conv[w.frame0] = converged ? 1 : 0;
     }
 }
 
@@ -341,13 +287,9 @@ template <class Plan, int SZ, class T>
 __device__ __forceinline__ void kernel_body(const FusedArgs &A) {
     using G = SplitGeom<Plan, SZ>;
     constexpr bool RS = LAY_ROW_SPLIT && Halves<Plan>::ok();
-    __shared__ __attribute__((aligned(16))) char lds[(Plan::NBC * G::V * 4 + 15) / 16 * 16 + 4 * G::NW + (RS ? 16 + 3 * 2 * G::VT * 4 : 0)];
+    __shared__ __attribute__((aligned(16))) char lds[G::lds_bytes(RS ? 3 : 0)];
     const uint32_t tid = threadIdx.x;
-    const uint32_t group = __builtin_amdgcn_readfirstlane(tid / G::VT);
-    static_for<0, Plan::NP>([&](auto pc) {
-        constexpr int P = decltype(pc)::value;
-        if (group == (uint32_t)P) body<Plan, SZ, T, P, RS>(A, lds, tid);
-    });
+    in_own_group<Plan, G::VT>(tid, [&](auto pc) { body<Plan, SZ, T, decltype(pc)::value, RS>(A, lds, tid); });
 }
 }  // namespace lay
 
@@ -453,90 +395,32 @@ template <class Plan, int SZ, class T, int P, bool RS>
 __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32_t tid) {
     using S = Split<Plan, T>;
     using H = lay::Halves<Plan>;
-    constexpr int CPW = QcGeom<SZ>::CPW, V = QcGeom<SZ>::V, VT = QcGeom<SZ>::VT;
-    constexpr int N = Plan::NBC * SZ, THREADS = Plan::NP * VT, NW = THREADS / 64;
-    constexpr uint32_t ES = 4, vmask = V * ES - 1;
-    constexpr int LAM_BYTES = (Plan::NBC * V * (int)ES + 15) / 16 * 16;
-    constexpr int NBCP = (Plan::NBC + Plan::NP - 1) / Plan::NP;
+    using F = Frame<Plan, SZ, P, LamCellPk16>;
+    using Where = typename F::W;
+    constexpr int CPW = F::CPW, V = F::V, VT = F::VT, NW = F::NW;
+    constexpr uint32_t ES = 4, vmask = F::vmask, FULL = F::FULL;
     static_assert(CPW <= 8, "the done mask holds 2 * CPW frames");
     if constexpr (VT != V) { if ((tid % VT) >= (uint32_t)V) return; }
     const uint32_t p4 = (tid % VT) * ES;
-    struct Where {
-        uint32_t sub, r0; long long frame0; bool valid[2]; size_t fN[2];
-        __device__ __forceinline__ Where(uint32_t p, int batch) {
-            asm volatile("" : "+v"(p));
-            const uint32_t lane = p / ES;
-            sub = lane % CPW;
-            r0 = lane / CPW;
-            frame0 = ((long long)blockIdx.x * CPW + sub) * 2;
-#pragma unroll
-            for (int h = 0; h < 2; h++) { valid[h] = frame0 + h < batch; fN[h] = (size_t)(valid[h] ? frame0 + h : 0) * N; }
-        }
-    };
     constexpr int NU = RS ? H::NMSG : S::NMSG;
-    constexpr uint32_t EX0 = LAM_BYTES + 4 * NW + 12, EXW = 2 * VT * ES, EXG = VT * ES;   // RS: exchange area [word 0..1][group][VT]
+    constexpr uint32_t EX0 = F::EX0, EXW = F::EXW, EXG = F::EXG;   // RS: exchange area [word 0..1][group][VT]
     uint32_t u[NU];
 #pragma unroll
     for (int i = 0; i < NU; i++) u[i] = 0u;
-    typename SplitResult<NBCP>::Bits obits[2];
-    {
-        const Where w(p4, A.batch);
-        with_llr_format(A.llr_fmt, [&](auto fc) {
-            constexpr int FMT = decltype(fc)::value;
-            float x[NBCP][2];
-            static_for<0, Plan::NBC>([&](auto bcc) {
-                constexpr int bc = decltype(bcc)::value;
-                if constexpr ((bc % Plan::NP) == P) {
-#pragma unroll
-                    for (int h = 0; h < 2; h++) x[bc / Plan::NP][h] = load_llr_as<float, FMT>(A.llr, w.fN[h] + bc * SZ + w.r0);
-                }
-            });
-            static_for<0, Plan::NBC>([&](auto bcc) {
-                constexpr int bc = decltype(bcc)::value;
-                if constexpr ((bc % Plan::NP) == P) {
-                    uint32_t packed = 0;
-#pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        const uint32_t b = neg_llr16(x[bc / Plan::NP][h]);
-                        obits[h].set(bc / Plan::NP, (b >> 15) & 1u);
-                        packed |= b << (16 * h);
-                    }
-                    lds_st<uint32_t>(lds, p4 + (bc * V * ES), packed);
-                }
-            });
-        });
-    }
+    typename SplitResult<F::NBCP>::Bits obits[2];
+    load_llrs_pk16<Plan, SZ, P>(A, lds, p4, obits);
     __syncthreads();
 
-    volatile uint32_t *flags = reinterpret_cast<volatile uint32_t *>(lds + LAM_BYTES);
-    constexpr uint32_t FULL = (1u << (2 * CPW)) - 1;
+    volatile uint32_t *flags = reinterpret_cast<volatile uint32_t *>(lds + F::LAM_BYTES);
     uint32_t done = 0;     // bit 2s + h
 #pragma unroll
     for (int s2 = 0; s2 < 2 * CPW; s2++) done |= (((long long)blockIdx.x * CPW + s2 / 2) * 2 + (s2 & 1) < A.batch) ? 0u : (1u << s2);
-    SplitResult<NBCP> res[2];
+    SplitResult<F::NBCP> res[2];
     res[0].bits = obits[0]; res[1].bits = obits[1];
     const uint32_t my_slot = (p4 / ES) % CPW;
 
     auto frames_with = [&](uint32_t word) -> uint32_t {    // bits 15 / 31 of `word` = the lane's flag for its low / high frame
-        uint32_t wbits = 0;
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const unsigned long long ub = __ballot((word >> (15 + 16 * h)) & 1u);
-#pragma unroll
-            for (int s2 = 0; s2 < CPW; s2++) {
-                unsigned long long mk = 0;
-                for (int i = 0; i < 64; i += CPW) mk |= 1ull << i;
-                wbits |= ((ub & (mk << s2)) != 0ull) ? (1u << (2 * s2 + h)) : 0u;
-            }
-        }
-        if ((tid & 63) == 0) flags[tid >> 6] = wbits;
-        __syncthreads();
-        uint32_t f = 0;
-#pragma unroll
-        for (int w = 0; w < NW; w++) f |= flags[w];
-        f = __builtin_amdgcn_readfirstlane(f);
-        __syncthreads();
-        return f;
+        return ldpc::frames_with<CPW, NW, 2, true>(flags, tid, [&](int h) { return (word >> (15 + 16 * h)) & 1u; });
     };
     auto snapshot = [&](int n, uint32_t newly) {
         if ((newly >> (2 * my_slot)) & 3u) {
@@ -545,16 +429,10 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
             for (int h = 0; h < 2; h++)
                 if ((newly >> (2 * my_slot + h)) & 1u) {
                     res[h].converge_at(n);
-                    static_for<0, Plan::NBC>([&](auto bcc) {
-                        constexpr int bc = decltype(bcc)::value;
-                        if constexpr ((bc % Plan::NP) == P) res[h].bits.set(bc / Plan::NP, (lds_ld<uint32_t>(lds, p4 + (bc * V * ES)) >> (15 + 16 * h)) & 1u);
-                    });
+                    F::hard_bits(lds, p4, h, res[h].bits);
                     if (A.final_lam) {
                         const Where w(p4, A.batch);
-                        static_for<0, Plan::NBC>([&](auto bcc) {
-                            constexpr int bc = decltype(bcc)::value;
-                            if constexpr ((bc % Plan::NP) == P) A.final_lam[w.fN[h] + bc * SZ + w.r0] = lam_of(lds_ld<uint32_t>(lds, p4 + (bc * V * ES)), h);
-                        });
+                        F::store_lam(A, lds, p4, w, h);
                     }
                 }
         }
@@ -565,12 +443,7 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
             const Where w(p4, A.batch);
 #pragma unroll
             for (int h = 0; h < 2; h++)
-                if (w.valid[h] && !((done >> (2 * w.sub + h)) & 1u))
-                    static_for<0, Plan::NBC>([&](auto bcc) {
-                        constexpr int bc = decltype(bcc)::value;
-                        if constexpr ((bc % Plan::NP) == P)
-                            A.trace[((size_t)(w.frame0 + h) * (A.max_iters + 1) + n) * N + bc * SZ + w.r0] = lam_of(lds_ld<uint32_t>(lds, p4 + (bc * V * ES)), h);
-                    });
+                if (w.valid[h] && !((done >> (2 * w.sub + h)) & 1u)) F::trace_frame(A, lds, p4, w, h, n);
         }
     };
 
@@ -663,22 +536,10 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
     for (int h = 0; h < 2; h++) {
         if (!w.valid[h]) continue;
         const bool converged = res[h].converged();
-        static_for<0, Plan::NBC>([&](auto bcc) {
-            constexpr int bc = decltype(bcc)::value;
-            if constexpr ((bc % Plan::NP) == P) A.bits[w.fN[h] + bc * SZ + w.r0] = res[h].bits.get(bc / Plan::NP);
-        });
+        F::store_bits(A, w, h, res[h]);
         if (!converged && A.final_lam) {
             LDPC_COLD_PATH();
-            with_llr_format(A.llr_fmt, [&](auto fc) {
-                constexpr int FMT = decltype(fc)::value;
-                static_for<0, Plan::NBC>([&](auto bcc) {
-                    constexpr int bc = decltype(bcc)::value;
-                    if constexpr ((bc % Plan::NP) == P) {
-                        const size_t gi = w.fN[h] + bc * SZ + w.r0;
-                        A.final_lam[gi] = lam_of(neg_llr16(load_llr_as<float, FMT>(A.llr, gi)), 0);
-                    }
-                });
-            });
+            F::store_channel_lam(A, w, h);
         }
         if (w.r0 == 0 && P == 0) {
             if (A.iters) A.iters[w.frame0 + h] = converged ? res[h].turn() : A.max_iters;
@@ -691,13 +552,9 @@ template <class Plan, int SZ, class T>
 __device__ __forceinline__ void kernel_body(const FusedArgs &A) {
     using G = SplitGeom<Plan, SZ>;
     constexpr bool RS = LAY_ROW_SPLIT && lay::Halves<Plan>::ok();
-    __shared__ __attribute__((aligned(16))) char lds[(Plan::NBC * G::V * 4 + 15) / 16 * 16 + 4 * G::NW + (RS ? 16 + 2 * 2 * G::VT * 4 : 0)];
+    __shared__ __attribute__((aligned(16))) char lds[G::lds_bytes(RS ? 2 : 0)];
     const uint32_t tid = threadIdx.x;
-    const uint32_t group = __builtin_amdgcn_readfirstlane(tid / G::VT);
-    static_for<0, Plan::NP>([&](auto pc) {
-        constexpr int P = decltype(pc)::value;
-        if (group == (uint32_t)P) body<Plan, SZ, T, P, RS>(A, lds, tid);
-    });
+    in_own_group<Plan, G::VT>(tid, [&](auto pc) { body<Plan, SZ, T, decltype(pc)::value, RS>(A, lds, tid); });
 }
 }  // namespace laypk
 }  // namespace ldpc

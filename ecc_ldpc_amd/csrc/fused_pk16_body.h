@@ -41,7 +41,6 @@ namespace ldpc {
 namespace pk {
 constexpr uint32_t K75 = 0x3a003a00u, KN75 = 0xba00ba00u, ABS = 0x7fff7fffu, SGN = 0x80008000u, INF2 = 0x7c007c00u;
 constexpr uint32_t UMAX2 = 0x68006800u;    // U16_MAX = 2048 in both halves
-constexpr float LLR16_MAX = 16384.0f;
 constexpr int PK16_MAX_COLUMN_DEGREE = 30;
 // (non-volatile asm: pure functions of their inputs, free to be scheduled; the compiler's own elementwise min/max on half2 adds
 //  a canonicalising v_pk_max_f16 x, x, x per operand)
@@ -189,79 +188,24 @@ __device__ __forceinline__ void round(char *lds, uint32_t p4, uint32_t vmask, co
     }
 }
 
-// -(x) of a channel LLR as fp16 bits, saturated at +-LLR16_MAX, a zero as +0
-__device__ __forceinline__ uint32_t neg_llr16(float x) {
-    const float v = fminf(fmaxf(x, -LLR16_MAX), LLR16_MAX);
-    const _Float16 h = (_Float16)(0.0f - v);          // 0 - (+-0) = +0; the f32 negation is exact, the conversion rounds to nearest even
-    uint16_t b;
-    __builtin_memcpy(&b, &h, 2);
-    return b == 0x8000u ? 0u : (uint32_t)b;           // (a value that underflows to -0 in fp16)
-}
-__device__ __forceinline__ double lam_of(uint32_t packed, int h) {   // lam = -L of half h, as a double
-    const uint16_t b = (uint16_t)(h ? packed >> 16 : packed & 0xffffu);
-    _Float16 v;
-    __builtin_memcpy(&v, &b, 2);
-    return -(double)(float)v;
-}
-
 template <class Plan, int SZ, class T, int P>
 __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32_t tid) {
     using S = Split<Plan, T>;
-    constexpr int CPW = QcGeom<SZ>::CPW, V = QcGeom<SZ>::V, VT = QcGeom<SZ>::VT;
-    constexpr int N = Plan::NBC * SZ, THREADS = Plan::NP * VT, NW = THREADS / 64;
-    constexpr uint32_t ES = 4, vmask = V * ES - 1;
-    constexpr int LAM_BYTES = (Plan::NBC * V * (int)ES + 15) / 16 * 16;
-    constexpr int NBCP = (Plan::NBC + Plan::NP - 1) / Plan::NP;
+    using F = Frame<Plan, SZ, P, LamCellPk16>;
+    constexpr int CPW = F::CPW, V = F::V, VT = F::VT, NW = F::NW;
+    constexpr uint32_t ES = 4, vmask = F::vmask, FULL = F::FULL;
     static_assert(CPW <= 8, "the done mask holds 2 * CPW frames");
     if constexpr (VT != V) { if ((tid % VT) >= (uint32_t)V) return; }
     const uint32_t p4 = (tid % VT) * ES;
-    struct Where {   // recomputed where needed, so that it does not occupy registers next to the messages
-        uint32_t sub, r0; long long frame0; bool valid[2]; size_t fN[2];
-        __device__ __forceinline__ Where(uint32_t p, int batch) {
-            asm volatile("" : "+v"(p));
-            const uint32_t lane = p / ES;
-            sub = lane % CPW;
-            r0 = lane / CPW;
-            frame0 = ((long long)blockIdx.x * CPW + sub) * 2;      // the lane's low-half frame; the high half is frame0 + 1
-#pragma unroll
-            for (int h = 0; h < 2; h++) { valid[h] = frame0 + h < batch; fN[h] = (size_t)(valid[h] ? frame0 + h : 0) * N; }
-        }
-    };
+    using Where = typename F::W;
     uint32_t u[S::NMSG], orig[S::NORIG];
 #pragma unroll
     for (int i = 0; i < S::NMSG; i++) u[i] = 0u;   // Min.hs:60-61: no messages yet
 #pragma unroll
     for (int i = 0; i < S::NORIG; i++) orig[i] = 0u;
-    // ---- L <- -(channel LLRs) of both frames: group P fills the block columns bc with bc % NP == P.  Every LLR is read from
-    // memory once; the hard decisions of the lane's own columns stay in `obits` (the answer of a frame that runs out of turns).
-    typename SplitResult<NBCP>::Bits obits[2];
-    {
-        const Where w(p4, A.batch);   // (a frame past the batch shadows frame 0: every load below is unconditional and in range)
-        with_llr_format(A.llr_fmt, [&](auto fc) {
-            constexpr int FMT = decltype(fc)::value;
-            float x[NBCP][2];          // all of the thread's loads first, back to back: 2 x 22 of them
-            static_for<0, Plan::NBC>([&](auto bcc) {
-                constexpr int bc = decltype(bcc)::value;
-                if constexpr ((bc % Plan::NP) == P) {
-#pragma unroll
-                    for (int h = 0; h < 2; h++) x[bc / Plan::NP][h] = load_llr_as<float, FMT>(A.llr, w.fN[h] + bc * SZ + w.r0);
-                }
-            });
-            static_for<0, Plan::NBC>([&](auto bcc) {
-                constexpr int bc = decltype(bcc)::value;
-                if constexpr ((bc % Plan::NP) == P) {
-                    uint32_t packed = 0;
-#pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        const uint32_t b = neg_llr16(x[bc / Plan::NP][h]);
-                        obits[h].set(bc / Plan::NP, (b >> 15) & 1u);      // hard(llr) = llr > 0 = sign of -llr
-                        packed |= b << (16 * h);
-                    }
-                    lds_st<uint32_t>(lds, p4 + (bc * V * ES), packed);
-                }
-            });
-        });
-    }
+    // ---- L <- -(channel LLRs) of both frames: group P fills the block columns bc with bc % NP == P
+    typename SplitResult<F::NBCP>::Bits obits[2];
+    load_llrs_pk16<Plan, SZ, P>(A, lds, p4, obits);
     __syncthreads();
     static_for<0, Plan::NBC>([&](auto bcc) {   // L == -(channel LLRs) right now: the round-0 (rotated) copies are an LDS gather away
         constexpr int bc = decltype(bcc)::value;
@@ -274,13 +218,12 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
         }
     });
 
-    volatile uint32_t *flags = reinterpret_cast<volatile uint32_t *>(lds + LAM_BYTES);
+    volatile uint32_t *flags = reinterpret_cast<volatile uint32_t *>(lds + F::LAM_BYTES);
     // done: bit 2s + h = frame h of slot s of this workgroup has finished (workgroup-uniform: derived from the shared flags)
-    constexpr uint32_t FULL = (1u << (2 * CPW)) - 1;
     uint32_t done = 0;
 #pragma unroll
     for (int s2 = 0; s2 < 2 * CPW; s2++) done |= (((long long)blockIdx.x * CPW + s2 / 2) * 2 + (s2 & 1) < A.batch) ? 0u : (1u << s2);
-    SplitResult<NBCP> res[2];
+    SplitResult<F::NBCP> res[2];
     res[0].bits = obits[0]; res[1].bits = obits[1];
     const int turns = A.max_iters;
     const uint32_t my_slot = (p4 / ES) % CPW;
@@ -292,12 +235,7 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
             const Where w(p4, A.batch);
 #pragma unroll
             for (int h = 0; h < 2; h++)
-                if (w.valid[h] && !((done >> (2 * w.sub + h)) & 1u))
-                    static_for<0, Plan::NBC>([&](auto bcc) {
-                        constexpr int bc = decltype(bcc)::value;
-                        if constexpr ((bc % Plan::NP) == P)
-                            A.trace[((size_t)(w.frame0 + h) * (A.max_iters + 1) + n) * N + bc * SZ + w.r0] = lam_of(lds_ld<uint32_t>(lds, p4 + (bc * V * ES)), h);
-                    });
+                if (w.valid[h] && !((done >> (2 * w.sub + h)) & 1u)) F::trace_frame(A, lds, p4, w, h, n);
         }
         const bool last = (n >= turns);
         // ---- phase A over the group's block rows
@@ -311,24 +249,8 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
                 else par |= rows_a<D, false>(lds, row, p4, vmask, &u[ms0]);
             }
         });
-        // per wave: bit 2s + h = some lane of slot s saw an odd row parity in frame h
-        uint32_t wbits = 0;
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const unsigned long long ub = __ballot((par >> (15 + 16 * h)) & 1u);
-#pragma unroll
-            for (int s2 = 0; s2 < CPW; s2++) {
-                unsigned long long m = 0;
-                for (int i = 0; i < 64; i += CPW) m |= 1ull << i;
-                wbits |= ((ub & (m << s2)) != 0ull) ? (1u << (2 * s2 + h)) : 0u;
-            }
-        }
-        if ((tid & 63) == 0) flags[tid >> 6] = wbits;
-        __syncthreads();   // syndrome OR over the workgroup's waves; also fences phase A reads from phase B writes
-        uint32_t fbits = 0;
-#pragma unroll
-        for (int w = 0; w < NW; w++) fbits |= flags[w];
-        fbits = __builtin_amdgcn_readfirstlane(fbits);
+        // bit 2s + h = some lane of slot s saw an odd row parity in frame h; the barrier inside also fences phase A reads from phase B writes
+        const uint32_t fbits = frames_with<CPW, NW, 2, false>(flags, tid, [&](int h) { return (par >> (15 + 16 * h)) & 1u; });
         const uint32_t newly = ~fbits & ~done & FULL;   // Min.hs:75: frames whose syndrome is zero now
         if ((newly >> (2 * my_slot)) & 3u) {
             LDPC_COLD_PATH();   // once per frame
@@ -336,16 +258,10 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
             for (int h = 0; h < 2; h++)
                 if ((newly >> (2 * my_slot + h)) & 1u) {
                     res[h].converge_at(n);
-                    static_for<0, Plan::NBC>([&](auto bcc) {
-                        constexpr int bc = decltype(bcc)::value;
-                        if constexpr ((bc % Plan::NP) == P) res[h].bits.set(bc / Plan::NP, (lds_ld<uint32_t>(lds, p4 + (bc * V * ES)) >> (15 + 16 * h)) & 1u);
-                    });
+                    F::hard_bits(lds, p4, h, res[h].bits);
                     if (A.final_lam) {
                         const Where w(p4, A.batch);
-                        static_for<0, Plan::NBC>([&](auto bcc) {
-                            constexpr int bc = decltype(bcc)::value;
-                            if constexpr ((bc % Plan::NP) == P) A.final_lam[w.fN[h] + bc * SZ + w.r0] = lam_of(lds_ld<uint32_t>(lds, p4 + (bc * V * ES)), h);
-                        });
+                        F::store_lam(A, lds, p4, w, h);
                     }
                 }
         }
@@ -368,22 +284,10 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
     for (int h = 0; h < 2; h++) {
         if (!w.valid[h]) continue;
         const bool converged = res[h].converged();
-        static_for<0, Plan::NBC>([&](auto bcc) {   // hard(lam at convergence), or hard(channel LLR) for a frame out of turns
-            constexpr int bc = decltype(bcc)::value;
-            if constexpr ((bc % Plan::NP) == P) A.bits[w.fN[h] + bc * SZ + w.r0] = res[h].bits.get(bc / Plan::NP);
-        });
+        F::store_bits(A, w, h, res[h]);   // hard(lam at convergence), or hard(channel LLR) for a frame out of turns
         if (!converged && A.final_lam) {
             LDPC_COLD_PATH();
-            with_llr_format(A.llr_fmt, [&](auto fc) {
-                constexpr int FMT = decltype(fc)::value;
-                static_for<0, Plan::NBC>([&](auto bcc) {
-                    constexpr int bc = decltype(bcc)::value;
-                    if constexpr ((bc % Plan::NP) == P) {
-                        const size_t gi = w.fN[h] + bc * SZ + w.r0;
-                        A.final_lam[gi] = lam_of(neg_llr16(load_llr_as<float, FMT>(A.llr, gi)), 0);
-                    }
-                });
-            });
+            F::store_channel_lam(A, w, h);
         }
         if (w.r0 == 0 && P == 0) {
             if (A.iters) A.iters[w.frame0 + h] = converged ? res[h].turn() : turns;
@@ -395,13 +299,9 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
 template <class Plan, int SZ, class T>
 __device__ __forceinline__ void kernel_body(const FusedArgs &A) {
     using G = SplitGeom<Plan, SZ>;
-    __shared__ __attribute__((aligned(16))) char lds[(Plan::NBC * G::V * 4 + 15) / 16 * 16 + 4 * G::NW];
+    __shared__ __attribute__((aligned(16))) char lds[G::lds_bytes()];
     const uint32_t tid = threadIdx.x;
-    const uint32_t group = __builtin_amdgcn_readfirstlane(tid / G::VT);
-    static_for<0, Plan::NP>([&](auto pc) {
-        constexpr int P = decltype(pc)::value;
-        if (group == (uint32_t)P) body<Plan, SZ, T, P>(A, lds, tid);
-    });
+    in_own_group<Plan, G::VT>(tid, [&](auto pc) { body<Plan, SZ, T, decltype(pc)::value>(A, lds, tid); });
 }
 }  // namespace pk
 }  // namespace ldpc

@@ -5,8 +5,10 @@
 // The ahead-of-time f32 min-sum instances with whole waves of one frame (sz = 128) are built in a tighter form behind
 // SPLIT_WAVE_SPEC, SPLIT_FLAGS_LDS and SPLIT_NEG_LAM below; all three default to off here, so a run-time compiled instance
 // and the sz = 32 instances compile to what they were.
+// What is not about check rows or column rounds -- LDS layout, lane locator, per-frame workgroup OR, the stores of trace rows,
+// snapshots and results -- is shared with the packed-fp16 and the layered bodies: fused_frame.h.
 #pragma once
-#include "fused_rows.h"
+#include "fused_frame.h"   // (brings fused_rows.h)
 
 #ifndef SPLIT_ORIG_REGS
 #define SPLIT_ORIG_REGS 1
@@ -161,11 +163,11 @@ struct Split {
 template <typename CT, int VARIANT, class Plan, int SZ, class T>
 struct SplitLds {
     static constexpr int V = QcGeom<SZ>::V, VT = QcGeom<SZ>::VT, THREADS = Plan::NP * VT, NW = THREADS / 64, ES = sizeof(CT);
-    static constexpr int LAM_BYTES = (Plan::NBC * V * ES + 15) / 16 * 16;
+    static constexpr int LAM_BYTES = SplitGeom<Plan, SZ, ES>::LAM_BYTES;
     static constexpr int ORIG_OFF = LAM_BYTES + (4 * NW + 15) / 16 * 16;
     static constexpr int NOL_WANT = (VARIANT == LDPC_V_MINSUM && ES == 4 && SZ >= 64 && SPLIT_ORIG_REGS) ? SPLIT_ORIG_LDS : 0;
     static constexpr int NOL = NOL_WANT < Split<Plan, T>::NORIG ? NOL_WANT : Split<Plan, T>::NORIG;
-    static constexpr int BYTES = NOL ? ORIG_OFF + NOL * THREADS * ES : LAM_BYTES + 4 * NW;
+    static constexpr int BYTES = NOL ? ORIG_OFF + NOL * THREADS * ES : SplitGeom<Plan, SZ, ES>::lds_bytes();
     // byte offset of slot os of the thread in group P at lane offset p4 (= its lane index * ES): an immediate + p4
     static constexpr uint32_t orig_at(int P, int os) { return ORIG_OFF + (uint32_t)(os * THREADS + P * VT) * ES; }
 };
@@ -239,36 +241,24 @@ __device__ __forceinline__ void split_round(char *lds, uint32_t p4, uint32_t vma
 template <typename CT, int VARIANT, class Plan, int SZ, class T, int P, int WV>
 __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const uint32_t tid) {
     using S = Split<Plan, T>;
-    constexpr int CPW = QcGeom<SZ>::CPW, V = QcGeom<SZ>::V, VT = QcGeom<SZ>::VT;  // frames per workgroup, positions per block column, threads per group
-    constexpr int N = Plan::NBC * SZ, THREADS = Plan::NP * VT, NW = THREADS / 64;
-    constexpr uint32_t ES = sizeof(CT), vmask = V * ES - 1;
-    constexpr int LAM_BYTES = (Plan::NBC * V * (int)ES + 15) / 16 * 16;
+    // what LDS holds for a lam (and for a channel LLR among the round-0 copies), and back: lam itself, or 0 - lam (SPLIT_NEG_LAM)
+    constexpr bool NEG = SPLIT_NEG_LAM && kSplitWholeWaves<CT, VARIANT, SZ>;
+    using Cell = LamCell<CT, NEG>;
+    using F = Frame<Plan, SZ, P, Cell>;
+    using Where = typename F::W;
+    constexpr int CPW = F::CPW, V = F::V, VT = F::VT, NW = F::NW;  // frames per workgroup, positions per block column, threads per group, waves
+    constexpr uint32_t ES = sizeof(CT), vmask = F::vmask, FULL = F::FULL;
     // Only p4 (the lane's LDS byte offset inside a block column) lives across the iteration loop; everything else
     // about the lane's place -- frame, row, global offsets -- is recomputed from it where needed (Where), so that
     // it does not occupy registers next to the messages.
     if constexpr (VT != V) { if ((tid % VT) >= (uint32_t)V) return; }   // circulant size not a multiple of 64: the top lanes of the group idle
-    // what LDS holds for a lam (and for a channel LLR among the round-0 copies), and back: lam itself, or 0 - lam (SPLIT_NEG_LAM)
-    constexpr bool NEG = SPLIT_NEG_LAM && kSplitWholeWaves<CT, VARIANT, SZ>;
-    auto stored = [](CT x) { return NEG ? CT(0) - x : x; };
     const uint32_t b4 = (tid % (WV < 0 ? VT : 64)) * ES;
     const uint32_t p4 = b4 + (WV < 0 ? 0 : WV * 64) * ES;
     constexpr int WVA = (SPLIT_WAVE_PHASES & 1) ? WV : -1, WVB = (SPLIT_WAVE_PHASES & 2) ? WV : -1;   // per phase: specialised or not
-    struct Where {
-        uint32_t sub, r0; long long frame; bool valid; size_t fN, fE;
-        __device__ __forceinline__ Where(uint32_t p, int batch) {
-            asm volatile("" : "+v"(p));            // keep the compiler from carrying these over from an earlier Where
-            const uint32_t lane = p / ES;          // position inside the pair
-            sub = lane % CPW;                      // frame inside the workgroup (frames interleave lane by lane)
-            r0 = lane / CPW;                       // circulant row / own column inside a block
-            frame = (long long)blockIdx.x * CPW + sub;
-            valid = frame < batch;
-            fN = (size_t)(valid ? frame : 0) * N;  // lanes of a frame past the batch shadow frame 0 and store nothing
-            fE = (size_t)(valid ? frame : 0) * Plan::NEDGE * SZ;
-        }
-    };
+    auto fE_of = [](const Where &w) { return (size_t)(w.valid[0] ? w.frame0 : 0) * Plan::NEDGE * SZ; };   // the frame's messages (step mode)
     const Where w0(p4, A.batch);
     const uint32_t r0 = w0.r0;
-    const size_t fN = w0.fN, fE = w0.fE;
+    const size_t fN = w0.fN[0], fE = fE_of(w0);
     // ---- messages (own block rows) and round-0 channel LLRs (own round-0 edges)
     CT msg[S::NMSG];
     CT orig[SPLIT_ORIG_REGS ? S::NORIG : 1];
@@ -289,14 +279,12 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
     typename SplitResult<(Plan::NBC + Plan::NP - 1) / Plan::NP>::Bits obits{};
     with_llr_format(A.llr_fmt, [&](auto fc) {
         constexpr int FMT = decltype(fc)::value;
-        static_for<0, Plan::NBC>([&](auto bcc) {
+        own_columns<Plan, P>([&](auto bcc) {
             constexpr int bc = decltype(bcc)::value;
-            if constexpr ((bc % Plan::NP) == P) {
-                CT v = maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, fN + bc * SZ + r0), A.llr_round16);
-                obits.set(bc / Plan::NP, v > CT(0));
-                if (A.step_mode) v = (CT)A.st_lam[fN + bc * SZ + r0];
-                lds_st<CT>(lds, p4 + (bc * V * ES), stored(v));
-            }
+            CT v = maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, fN + bc * SZ + r0), A.llr_round16);
+            obits.set(bc / Plan::NP, v > CT(0));
+            if (A.step_mode) v = (CT)A.st_lam[fN + bc * SZ + r0];
+            lds_st<CT>(lds, p4 + (bc * V * ES), Cell::stored(v));
         });
         if (A.step_mode) {   // teacher-forced step: LDS holds the given lam, the channel LLRs come from memory
             static_for<0, Plan::NBC>([&](auto bcc) {
@@ -304,7 +292,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
                 if constexpr (SPLIT_ORIG_REGS && S::oowner(bc) == P) {
                     constexpr int e0 = Rounds<T>::round0_edge(bc);
                     constexpr int os = S::oslot(bc);
-                    put_orig(os, stored(maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, fN + bc * SZ + ((r0 + T::rot[e0]) % SZ)), A.llr_round16)));
+                    put_orig(os, Cell::stored(maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, fN + bc * SZ + ((r0 + T::rot[e0]) % SZ)), A.llr_round16)));
                 }
             });
         }
@@ -334,12 +322,11 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
         });
     }
 
-    const SynFlags<SPLIT_FLAGS_LDS && kSplitWholeWaves<CT, VARIANT, SZ>> flags(lds + LAM_BYTES);
+    const SynFlags<SPLIT_FLAGS_LDS && kSplitWholeWaves<CT, VARIANT, SZ>> flags(lds + F::LAM_BYTES);
     // done: bit s = frame s of this workgroup has finished.  Workgroup-uniform (derived from the shared flags), so
     // loop control and barriers stay uniform with several frames.  A finished frame keeps its answer in `snap`;
     // its lanes then keep computing on their own (disjoint) LDS columns until the workgroup's other frames are
     // done -- masking them off instead makes every message register live across divergent control flow.
-    constexpr uint32_t FULL = (1u << CPW) - 1;
     uint32_t done = 0;
 #pragma unroll
     for (int s2 = 0; s2 < CPW; s2++) done |= ((long long)blockIdx.x * CPW + s2 < A.batch) ? 0u : (1u << s2);
@@ -355,11 +342,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
         if (A.trace && !((done >> ((p4 / ES) % CPW)) & 1u)) {
             LDPC_COLD_PATH();
             const Where w(p4, A.batch);
-            static_for<0, Plan::NBC>([&](auto bcc) {
-                constexpr int bc = decltype(bcc)::value;
-                if constexpr ((bc % Plan::NP) == P)
-                    A.trace[((size_t)w.frame * (A.max_iters + 1) + n) * N + bc * SZ + w.r0] = (double)stored(lds_ld<CT>(lds, p4 + (bc * V * ES)));
-            });
+            F::trace_frame(A, lds, p4, w, 0, n);
         }
         const bool last = (n >= turns);
         // ---- phase A over the pair's block rows
@@ -374,23 +357,11 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
             }
         });
         // per wave: bit s = some lane of frame s saw an odd row parity (frames interleave lane by lane)
-        const unsigned long long ub = __ballot(unsat);
-        uint32_t wbits = 0;
-#pragma unroll
-        for (int s2 = 0; s2 < CPW; s2++) {
-            unsigned long long m = 0;
-            for (int i = 0; i < 64; i += CPW) m |= 1ull << i;
-            wbits |= ((ub & (m << s2)) != 0ull) ? (1u << s2) : 0u;
-        }
-        if ((tid & 63) == 0) flags[tid >> 6] = wbits;
-        __syncthreads();  // syndrome OR over the workgroup's waves; also fences phase A reads from phase B writes
-        uint32_t fbits = 0;
-#pragma unroll
-        for (int w = 0; w < NW; w++) fbits |= flags[w];
-        fbits = __builtin_amdgcn_readfirstlane(fbits);
+        // the barrier inside (syndrome OR over the workgroup's waves) also fences phase A reads from phase B writes
+        const uint32_t fbits = frames_with<CPW, NW, 1, false>(flags, tid, [&](int) { return unsat; });
         if (A.step_mode) {
             const Where w(p4, A.batch);
-            if (w.valid && w.r0 == 0 && P == 0) A.st_syn[w.frame] = ((fbits >> w.sub) & 1u) ? 0 : 1;
+            if (w.valid[0] && w.r0 == 0 && P == 0) A.st_syn[w.frame0] = ((fbits >> w.sub) & 1u) ? 0 : 1;
         } else {
             uint32_t newly = ~fbits & ~done & FULL;  // Orig.hs:69: frames whose syndrome is zero now
             if constexpr (kVetoesNonFinite<CT, VARIANT>) {
@@ -398,11 +369,12 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
                     LDPC_COLD_PATH();
                     bool nf = false;
                     if ((newly >> ((p4 / ES) % CPW)) & 1u)
-                        static_for<0, Plan::NBC>([&](auto bcc) {
+                        own_columns<Plan, P>([&](auto bcc) {
                             constexpr int bc = decltype(bcc)::value;
-                            if constexpr ((bc % Plan::NP) == P) nf |= not_finite(lds_ld<CT>(lds, p4 + (bc * V * ES)));
+                            nf |= not_finite(lds_ld<CT>(lds, p4 + (bc * V * ES)));
                         });
                     __syncthreads();   // every wave has read the syndrome flags
+                    // (written out: frames_with<CPW, NW, 1, true> here reorders the LDS reads above in the wave-specialised instance)
                     const unsigned long long vb = __ballot(nf);
                     uint32_t vbits = 0;
 #pragma unroll
@@ -425,19 +397,10 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
             if ((newly >> ((p4 / ES) % CPW)) & 1u) {
                 LDPC_COLD_PATH();   // once per frame
                 res.converge_at(n);
-                static_for<0, Plan::NBC>([&](auto bcc) {
-                    constexpr int bc = decltype(bcc)::value;
-                    if constexpr ((bc % Plan::NP) == P) {
-                        CT v = lds_ld<CT>(lds, p4 + (bc * V * ES));
-                        res.bits.set(bc / Plan::NP, NEG ? v < CT(0) : v > CT(0));
-                    }
-                });
+                F::hard_bits(lds, p4, 0, res.bits);
                 if (A.final_lam) {
                     const Where w(p4, A.batch);
-                    static_for<0, Plan::NBC>([&](auto bcc) {
-                        constexpr int bc = decltype(bcc)::value;
-                        if constexpr ((bc % Plan::NP) == P) A.final_lam[w.fN + bc * SZ + w.r0] = (double)stored(lds_ld<CT>(lds, p4 + (bc * V * ES)));
-                    });
+                    F::store_lam(A, lds, p4, w, 0);
                 }
             }
             done |= newly;
@@ -457,12 +420,9 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
     }
 
     const Where w(p4, A.batch);
-    if (!w.valid) return;
+    if (!w.valid[0]) return;
     if (A.step_mode) {
-        static_for<0, Plan::NBC>([&](auto bcc) {
-            constexpr int bc = decltype(bcc)::value;
-            if constexpr ((bc % Plan::NP) == P) A.final_lam[w.fN + bc * SZ + w.r0] = (double)stored(lds_ld<CT>(lds, p4 + (bc * V * ES)));
-        });
+        F::store_lam(A, lds, p4, w, 0);
         static_for<0, Plan::NBR>([&](auto brc) {
             constexpr int br = decltype(brc)::value;
             if constexpr (S::owner_br(br) == P) {
@@ -470,7 +430,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
                 static_for<0, D>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
                     constexpr int ms = S::slot(Plan::ebeg(br) + k);
-                    A.st_ne_out[w.fE + (size_t)SZ * Plan::ebeg(br) + (size_t)D * w.r0 + k] = (double)msg[ms];
+                    A.st_ne_out[fE_of(w) + (size_t)SZ * Plan::ebeg(br) + (size_t)D * w.r0 + k] = (double)msg[ms];
                 });
             }
         });
@@ -479,38 +439,16 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
     // ---- result: hard(lam at convergence) for a converged frame, hard(channel LLR) otherwise (Orig.hs:59,69-70)
     const bool converged = res.converged();
     if (converged) {
-        static_for<0, Plan::NBC>([&](auto bcc) {
-            constexpr int bc = decltype(bcc)::value;
-            if constexpr ((bc % Plan::NP) == P) A.bits[w.fN + bc * SZ + w.r0] = res.bits.get(bc / Plan::NP);
-        });
+        F::store_bits(A, w, 0, res);
     } else {
-        static_for<0, Plan::NBC>([&](auto bcc) {
-            constexpr int bc = decltype(bcc)::value;
-            if constexpr ((bc % Plan::NP) == P) A.bits[w.fN + bc * SZ + w.r0] = res.bits.get(bc / Plan::NP);   // hard(channel LLR)
-        });
-        if (A.final_lam) {
-            with_llr_format(A.llr_fmt, [&](auto fc) {
-                constexpr int FMT = decltype(fc)::value;
-                static_for<0, Plan::NBC>([&](auto bcc) {
-                    constexpr int bc = decltype(bcc)::value;
-                    if constexpr ((bc % Plan::NP) == P) {
-                        const size_t gi = w.fN + bc * SZ + w.r0;
-                        A.final_lam[gi] = (double)maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, gi), A.llr_round16);
-                    }
-                });
-            });
-        }
+        F::store_bits(A, w, 0, res);   // hard(channel LLR)
+        if (A.final_lam) F::store_channel_lam(A, w, 0);
     }
     if (w.r0 == 0 && P == 0) {
-        if (A.iters) A.iters[w.frame] = converged ? res.turn() : turns;
-        if (A.conv) A.conv[w.frame] = converged ? 1 : 0;
+        if (A.iters) A.iters[w.frame0] = converged ? res.turn() : turns;
+        if (A.conv) A.conv[w.frame0] = converged ? 1 : 0;
     }
 }
-
-template <class Plan, int SZ> struct SplitGeom {
-    static constexpr int CPW = QcGeom<SZ>::CPW, V = QcGeom<SZ>::V, VT = QcGeom<SZ>::VT, THREADS = Plan::NP * VT, NW = THREADS / 64;
-    static_assert(THREADS <= 1024, "a frame's wave groups must fit one workgroup");
-};
 
 // the kernel proper: every wave group runs its own straight-line program (same loop structure, same barriers)
 template <typename CT, int VARIANT, class Plan, int SZ, class T>
@@ -527,11 +465,7 @@ __device__ __forceinline__ void split_kernel_body(const FusedArgs &A) {
             if (wave == (uint32_t)decltype(wc)::value) split_body<CT, VARIANT, Plan, SZ, T, P, WV>(A, lds, tid);
         });
     } else {
-        const uint32_t pair = __builtin_amdgcn_readfirstlane(tid / G::VT);  // wave-uniform (VT is a multiple of 64)
-        static_for<0, Plan::NP>([&](auto pc) {
-            constexpr int P = decltype(pc)::value;
-            if (pair == (uint32_t)P) split_body<CT, VARIANT, Plan, SZ, T, P, -1>(A, lds, tid);
-        });
+        in_own_group<Plan, G::VT>(tid, [&](auto pc) { split_body<CT, VARIANT, Plan, SZ, T, decltype(pc)::value, -1>(A, lds, tid); });
     }
 }
 

@@ -25,6 +25,20 @@ def _frames(c, F, seed):
     return llr
 
 
+def _final_lam(dec, c, llr, emulate):
+    """want_lam=True at a turn limit that leaves both kinds of frame: lam at the turn a frame stopped by the rule, the channel LLRs
+    as stored (saturated at +-16384, rounded to fp16) for a frame out of turns"""
+    turns = int(np.median(emulate(c.graph, llr, 40)[1]))
+    eb, ei, ec, et = emulate(c.graph, llr, turns)
+    assert 0 < ec.sum() < len(llr), (turns, ei.tolist())
+    bits, its, conv, lam = dec.decode_batch(llr, turns, want_lam=True)
+    assert np.array_equal(bits, eb) and np.array_equal(its, ei) and np.array_equal(conv.astype(bool), ec)
+    want = -em.neg_llr16(llr).astype(np.float64)
+    for f in np.flatnonzero(ec):
+        want[f] = et[ei[f]][f].astype(np.float64)
+    assert np.array_equal(lam.astype(np.float64), want)
+
+
 @pytest.mark.parametrize("name", SHAPES)
 def test_packed_fp16_flooding(hip, name):
     c = synthetic(name)
@@ -45,6 +59,8 @@ def test_packed_fp16_flooding(hip, name):
     b3, i3, c3 = dec.decode_batch(llr[:3], 600)
     e3 = em.decode_minsum_pk16(c.graph, llr[:3], 600)
     assert np.array_equal(b3, e3[0]) and np.array_equal(i3, e3[1]) and np.array_equal(c3.astype(bool), e3[2])
+    if name == "small-2x4-sz32":
+        _final_lam(dec, c, llr, em.decode_minsum_pk16)
     print(f"{name}: {dec.kernel_name} {int(conv.sum())}/{F} converged, turns {sorted(set(its.tolist()))}")
     dec.close()
 
@@ -65,6 +81,8 @@ def test_packed_fp16_layered(hip, name):
         assert np.array_equal(trace[live, n, :], lam[live].astype(np.float64)), (name, n)
     b2, i2, c2 = dec.decode_batch(llr, 40)
     assert np.array_equal(b2, bits) and np.array_equal(i2, its) and np.array_equal(c2, conv)
+    if name == "small-2x4-sz32":
+        _final_lam(dec, c, llr, em.decode_minsum_pk16_layered)
     print(f"{name}: {dec.kernel_name} {int(conv.sum())}/{F} converged, sweeps {sorted(set(its.tolist()))}")
     dec.close()
 

@@ -159,3 +159,35 @@ def test_layered_trajectory_is_bit_exact_with_the_emulation(hip, name, per_db, d
     both = conv.astype(bool) & fl[2].astype(bool)
     assert both.sum() >= 3 and np.array_equal(bits[both], fl[0][both]) and its[both].mean() < 0.75 * fl[1][both].mean()
     dec.close()
+
+
+def final_lam_of_the_emulation(llr, ei, ec, et):
+    """what want_lam returns by the specification: lam at the turn a frame stopped by the rule, else the channel LLRs as the
+    kernel stores them (saturated at +-16384, rounded to fp16)"""
+    want = -em.neg_llr16(llr).astype(np.float64)
+    for f in np.flatnonzero(ec):
+        want[f] = et[ei[f]][f].astype(np.float64)
+    return want
+
+
+@pytest.mark.parametrize("schedule", ["flooding", "layered"])
+def test_final_lam_of_both_kinds_of_frame(hip, schedule):
+    """want_lam=True with "f16pk", both schedules: sz = 32 (four frames per wave), 13 frames (the last lane holds one frame only),
+    a turn limit -- the median of the emulation's own turn counts -- that leaves frames that converged and frames that did not."""
+    c = load("jpl.1024.4.5")
+    emulate = em.decode_minsum_pk16 if schedule == "flooding" else em.decode_minsum_pk16_layered
+    llr = _frames(c, 5, (2.0, 3.0, 4.0), 4900)[:13]
+    llr = llr[np.random.default_rng(7).permutation(len(llr))]
+    llr[2, :8] = [7e4, -7e4, 1e-9, -1e-9, 0.0, 65504.0, 3.0e-8, -6.0e-8]
+    turns = int(np.median(emulate(c.graph, llr, 50)[1]))
+    eb, ei, ec, et = emulate(c.graph, llr, turns)
+    assert 0 < ec.sum() < 13, (turns, ei.tolist())
+    kw = {} if schedule == "flooding" else {"schedule": "layered"}
+    dec = hip.Decoder(c.hip_code(hip), "min", "f16pk", 13, **kw)
+    assert ("fused_layered_pk16_kernel" if schedule == "layered" else "fused_pk16_kernel") in dec.kernel_name
+    bits, its, conv, lam = dec.decode_batch(llr, turns, want_lam=True)
+    assert np.array_equal(bits, eb) and np.array_equal(its, ei) and np.array_equal(conv.astype(bool), ec)
+    want = final_lam_of_the_emulation(llr, ei, ec, et)
+    for f in range(13):
+        assert np.array_equal(lam[f].astype(np.float64), want[f]), (f, bool(ec[f]), lam[f][:8], want[f][:8])
+    dec.close()
