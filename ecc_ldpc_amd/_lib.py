@@ -15,7 +15,7 @@ SO_PATH = (os.environ.get("LDPC_SO") or None) or os.path.join(HERE, "libldpc_hip
 
 OK, EINVAL, ENOMEM, EHIP, ENODEVICE, EUNSUPPORTED, EDEGREE, EFORMAT, ENOTFOUND = 0, -1, -2, -3, -4, -5, -6, -7, -8
 TANH, MINSUM, TANH_CM, TANH_CUDA32 = 0, 1, 2, 3
-F32, F64, F16, F16PK = 0, 1, 2, 3
+F32, F64, F16, F16PK, I8 = 0, 1, 2, 3, 4
 PATH_AUTO, PATH_FLOOD, PATH_FUSED = 0, 1, 2
 SCHED_FLOODING, SCHED_LAYERED = 0, 1
 SUM_REFERENCE, SUM_ARRAYLET, SUM_SPARSE = 0, 1, 2
@@ -23,7 +23,7 @@ SUM_REFERENCE, SUM_ARRAYLET, SUM_SPARSE = 0, 1, 2
 
 class CtxConfig(C.Structure):   # ldpc_ctx_config
     _fields_ = [("struct_size", C.c_size_t), ("device", C.c_int), ("variant", C.c_int), ("dtype", C.c_int), ("max_batch", C.c_int),
-                ("path", C.c_int), ("schedule", C.c_int), ("sum_order", C.c_int)]
+                ("path", C.c_int), ("schedule", C.c_int), ("sum_order", C.c_int), ("llr_qscale", C.c_float)]
 
 # every symbol include/ldpc_hip.h declares (tests/test_abi.py checks the library exports them all)
 ABI_SYMBOLS = [
@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "ldpc_code_create_qc", "ldpc_code_create_csr", "ldpc_code_destroy", "ldpc_code_dims", "ldpc_code_csr",
     "ldpc_ctx_create", "ldpc_ctx_create_ex", "ldpc_ctx_destroy", "ldpc_ctx_path", "ldpc_ctx_synchronize",
     "ldpc_decode_one", "ldpc_decode_batch", "ldpc_decode_batch_f64", "ldpc_decode_batch_dev",
+    "ldpc_decode_batch_i8", "ldpc_decode_batch_dev_i8", "ldpc_ctx_llr_qscale",
     "ldpc_decode_batch_f16", "ldpc_decode_batch_dev_f16", "ldpc_sim_generate_f16", "ldpc_decode_batch_dev_packed", "ldpc_decode_batch_packed",
     "ldpc_debug_step", "ldpc_decode_trace",
     "ldpc_host_alloc", "ldpc_host_free",
@@ -177,6 +178,10 @@ def lib():
     L.ldpc_decode_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.ldpc_decode_batch_f16.argtypes = [vp, C.c_int, C.c_int, vp, u8p, i32p, u8p]
     L.ldpc_decode_batch_dev_f16.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.ldpc_decode_batch_i8.argtypes = [vp, C.c_int, C.c_int, vp, u8p, i32p, u8p]
+    L.ldpc_decode_batch_dev_i8.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.ldpc_ctx_llr_qscale.restype = C.c_float
+    L.ldpc_ctx_llr_qscale.argtypes = [vp]
     L.ldpc_decode_batch_dev_packed.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.ldpc_decode_batch_packed.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, u8p, i32p, u8p]
     L.ldpc_debug_step.argtypes = [vp, C.c_int, f64p, f64p, f64p, f64p, f64p, u8p]
@@ -308,7 +313,7 @@ def init(device: int = 0):
 
 _VARIANTS = {"tanh": TANH, "min": MINSUM, "minsum": MINSUM, "min-sum": MINSUM, "cm": TANH_CM, "tanh-cm": TANH_CM, TANH: TANH, MINSUM: MINSUM,
              TANH_CM: TANH_CM, "cuda32": TANH_CUDA32, "cuda-arraylet2": TANH_CUDA32, TANH_CUDA32: TANH_CUDA32}
-_DTYPES = {"f32": F32, "f64": F64, "f16": F16, "f16pk": F16PK, F32: F32, F64: F64, F16: F16, F16PK: F16PK}
+_DTYPES = {"f32": F32, "f64": F64, "f16": F16, "f16pk": F16PK, "i8": I8, F32: F32, F64: F64, F16: F16, F16PK: F16PK, I8: I8}
 _PATHS = {"auto": PATH_AUTO, "flood": PATH_FLOOD, "fused": PATH_FUSED, 0: 0, 1: 1, 2: 2}
 _SUM_ORDERS = {"reference": SUM_REFERENCE, "arraylet": SUM_ARRAYLET, "sparse": SUM_SPARSE, 0: 0, 1: 1, 2: 2}
 _SCHEDULES = {"flooding": SCHED_FLOODING, "flood": SCHED_FLOODING, "layered": SCHED_LAYERED, 0: 0, 1: 1}
@@ -440,25 +445,26 @@ class Decoder:
     """One decoder replica (ldpc_ctx): the object behind the reference's per-frame closure."""
 
     def __init__(self, code: Code, variant="min", dtype="f32", max_batch=64, path="auto", _handle=None, device=None, schedule="flooding",
-                 sum_order="reference"):
+                 sum_order="reference", qscale=None):
         """sum_order: "reference" | "arraylet" | "sparse" -- the column-sum order of that family of the reference's decoders
-        (ldpc_sum_order: parity modes, flood path)"""
+        (ldpc_sum_order: parity modes, flood path); qscale: the quantiser's scale of dtype "i8" (None: the library's default, 4)"""
         self.code = code
         self.max_batch = int(max_batch)
         self._owned = _handle is None
         if _handle is not None:
             self._h = _handle
-        elif device is None and _SCHEDULES[schedule] == SCHED_FLOODING and _SUM_ORDERS[sum_order] == SUM_REFERENCE:
+        elif device is None and _SCHEDULES[schedule] == SCHED_FLOODING and _SUM_ORDERS[sum_order] == SUM_REFERENCE and qscale is None:
             self._h = lib().ldpc_ctx_create_ex(code._h, _VARIANTS[variant], _DTYPES[dtype], int(max_batch), _PATHS[path])
         else:   # explicit device (replicas of one code on several GPUs of this process) and/or the layered schedule
             cfg = CtxConfig(C.sizeof(CtxConfig), -1 if device is None else int(device), _VARIANTS[variant], _DTYPES[dtype], int(max_batch),
-                            _PATHS[path], _SCHEDULES[schedule], _SUM_ORDERS[sum_order])
+                            _PATHS[path], _SCHEDULES[schedule], _SUM_ORDERS[sum_order], 0.0 if qscale is None else float(qscale))
             self._h = lib().ldpc_ctx_create_cfg(code._h, C.byref(cfg))
         if not self._h:
             raise LdpcError(lib().ldpc_last_error_code(), last_error())
         _register(self)
         self.path = {PATH_FLOOD: "flood", PATH_FUSED: "fused"}[lib().ldpc_ctx_path(self._h)]
         self.schedule = {SCHED_FLOODING: "flooding", SCHED_LAYERED: "layered"}[lib().ldpc_ctx_schedule(self._h)]
+        self.qscale = float(lib().ldpc_ctx_llr_qscale(self._h))    # 0.0 unless dtype "i8"
 
     def decode_one(self, llr, max_iters):
         llr = np.ascontiguousarray(llr, np.float64)
@@ -469,7 +475,7 @@ class Decoder:
         return bits, it.value, bool(cv.value)
 
     def decode_batch(self, llr, max_iters, want_lam=False, out_bits=None):
-        """llr [F][N] float16, float32 or float64 (host).  -> bits [F][N], iters [F], converged [F] (, lam)"""
+        """llr [F][N] float16, float32 or float64 (host); int8 on an "i8" decoder.  -> bits [F][N], iters [F], converged [F] (, lam)"""
         llr = np.asarray(llr)
         F = llr.shape[0]
         assert llr.shape == (F, self.code.N)
@@ -477,6 +483,11 @@ class Decoder:
         assert bits.shape == (F, self.code.N) and bits.dtype == np.uint8 and bits.flags.c_contiguous
         iters = np.zeros(F, np.int32)
         conv = np.zeros(F, np.uint8)
+        if llr.dtype == np.int8:
+            assert not want_lam, "final LLRs come with float64 input (ldpc_decode_batch_f64)"
+            llr = np.ascontiguousarray(llr)
+            check(lib().ldpc_decode_batch_i8(self._h, int(max_iters), F, llr.ctypes.data_as(C.c_void_p), ptr(bits, C.c_uint8), ptr(iters, C.c_int32), ptr(conv, C.c_uint8)))
+            return bits, iters, conv
         if llr.dtype == np.float16 and not want_lam:
             llr = np.ascontiguousarray(llr)
             check(lib().ldpc_decode_batch_f16(self._h, int(max_iters), F, llr.ctypes.data_as(C.c_void_p), ptr(bits, C.c_uint8), ptr(iters, C.c_int32), ptr(conv, C.c_uint8)))
@@ -491,24 +502,24 @@ class Decoder:
         return (bits, iters, conv, lam) if want_lam else (bits, iters, conv)
 
     def decode_batch_packed(self, llr, max_iters):
-        """llr [F][N] float16 or float32 (host) -> packed bits [F][ceil(N/8)] (bit i of a frame: byte i // 8, bit i % 8), iters, converged"""
+        """llr [F][N] float16 or float32 (host), int8 on an "i8" decoder -> packed bits [F][ceil(N/8)] (bit i of a frame: byte i // 8, bit i % 8), iters, converged"""
         llr = np.ascontiguousarray(llr)
-        assert llr.dtype in (np.float16, np.float32) and llr.shape[1] == self.code.N
+        assert llr.dtype in (np.float16, np.float32, np.int8) and llr.shape[1] == self.code.N
         F = llr.shape[0]
         packed = np.zeros((F, (self.code.N + 7) // 8), np.uint8)
         iters = np.zeros(F, np.int32)
         conv = np.zeros(F, np.uint8)
-        check(lib().ldpc_decode_batch_packed(self._h, int(max_iters), F, llr.ctypes.data_as(C.c_void_p), 1 if llr.dtype == np.float16 else 0,
+        check(lib().ldpc_decode_batch_packed(self._h, int(max_iters), F, llr.ctypes.data_as(C.c_void_p), {np.dtype(np.float32): 0, np.dtype(np.float16): 1, np.dtype(np.int8): 2}[llr.dtype],
                                              ptr(packed, C.c_uint8), ptr(iters, C.c_int32), ptr(conv, C.c_uint8)))
         return packed, iters, conv
 
-    def decode_batch_dev_packed(self, d_llr_ptr, d_packed_ptr, batch, max_iters, d_iters_ptr=None, d_conv_ptr=None, stream=None, llr_f16=False):
-        """device pointers; d_packed [batch][ceil(N/8)] bytes"""
-        check(lib().ldpc_decode_batch_dev_packed(self._h, int(max_iters), int(batch), d_llr_ptr, 1 if llr_f16 else 0, d_packed_ptr, d_iters_ptr, d_conv_ptr, stream))
+    def decode_batch_dev_packed(self, d_llr_ptr, d_packed_ptr, batch, max_iters, d_iters_ptr=None, d_conv_ptr=None, stream=None, llr_f16=False, llr_i8=False):
+        """device pointers; d_packed [batch][ceil(N/8)] bytes; d_llr float32, float16 with llr_f16=True, int8 with llr_i8=True"""
+        check(lib().ldpc_decode_batch_dev_packed(self._h, int(max_iters), int(batch), d_llr_ptr, 2 if llr_i8 else 1 if llr_f16 else 0, d_packed_ptr, d_iters_ptr, d_conv_ptr, stream))
 
-    def decode_batch_dev(self, d_llr_ptr, d_bits_ptr, batch, max_iters, d_iters_ptr=None, d_conv_ptr=None, stream=None, llr_f16=False):
-        """device pointers; d_llr [batch][N] float32, or float16 with llr_f16=True"""
-        fn = lib().ldpc_decode_batch_dev_f16 if llr_f16 else lib().ldpc_decode_batch_dev
+    def decode_batch_dev(self, d_llr_ptr, d_bits_ptr, batch, max_iters, d_iters_ptr=None, d_conv_ptr=None, stream=None, llr_f16=False, llr_i8=False):
+        """device pointers; d_llr [batch][N] float32, float16 with llr_f16=True, or int8 with llr_i8=True (an "i8" decoder)"""
+        fn = lib().ldpc_decode_batch_dev_i8 if llr_i8 else lib().ldpc_decode_batch_dev_f16 if llr_f16 else lib().ldpc_decode_batch_dev
         check(fn(self._h, int(max_iters), int(batch), d_llr_ptr, d_bits_ptr, d_iters_ptr, d_conv_ptr, stream))
 
     def synchronize(self):

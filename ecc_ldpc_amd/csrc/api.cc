@@ -47,7 +47,8 @@ using ldpc::set_error;
 
 struct ldpc_ctx {
     const ldpc_code *code = nullptr;
-    int max_batch = 0, device = 0, schedule = LDPC_SCHED_FLOODING;
+    int max_batch = 0, device = 0, schedule = LDPC_SCHED_FLOODING, dtype = LDPC_F32;
+    float llr_qscale = 0.f;             // LDPC_I8: the quantiser's scale (0 for every other dtype)
     hipStream_t stream = nullptr;
     ldpc::Backend *backend = nullptr;   // the context's decoder (select.cc make_backend)
     // staging of the host-pointer entry points, allocated on first use.  kSlots slots, each with its own stream
@@ -61,7 +62,7 @@ struct ldpc_ctx {
     hipStream_t pstream[kSlots] = {};   // [0] aliases `stream`
     hipEvent_t decoded = nullptr;       // (slots > 1) recorded after each chunk's decode; the next chunk's decode waits for it
     int slots = 0, chunk = 0;
-    void *d_in[kSlots] = {};            // [chunk][N] float, double or half
+    void *d_in[kSlots] = {};            // [chunk][N] float, double, half or int8
     uint8_t *d_bits[kSlots] = {};       // [chunk][N]
     int32_t *d_iters[kSlots] = {};
     uint8_t *d_conv[kSlots] = {};
@@ -118,7 +119,7 @@ extern "C" {
 
 const char *ldpc_last_error(void) { return ldpc::g_err; }
 int ldpc_last_error_code(void) { return ldpc::g_err_code; }
-int ldpc_abi_version(void) { return 2; }
+int ldpc_abi_version(void) { return 3; }
 
 int ldpc_device_count(void) {
     int n = 0;
@@ -439,6 +440,7 @@ const ldpc_code *ldpc_ctx_code(const ldpc_ctx *ctx) { return ctx ? ctx->code : n
 int ldpc_ctx_max_batch(const ldpc_ctx *ctx) { return ctx ? ctx->max_batch : set_error(LDPC_EINVAL, "null ctx"); }
 int ldpc_ctx_device(const ldpc_ctx *ctx) { return ctx ? ctx->device : set_error(LDPC_EINVAL, "null ctx"); }
 int ldpc_ctx_schedule(const ldpc_ctx *ctx) { return ctx ? ctx->schedule : set_error(LDPC_EINVAL, "null ctx"); }
+float ldpc_ctx_llr_qscale(const ldpc_ctx *ctx) { return ctx ? ctx->llr_qscale : 0.f; }
 
 ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cfg) {
     if (!cfg || cfg->struct_size < offsetof(ldpc_ctx_config, schedule)) { set_error(LDPC_EINVAL, "ldpc_ctx_create_cfg: bad config"); return nullptr; }
@@ -450,6 +452,11 @@ ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cf
     if (schedule != LDPC_SCHED_FLOODING && schedule != LDPC_SCHED_LAYERED) { set_error(LDPC_EINVAL, "unknown schedule %d", schedule); return nullptr; }
     const int sum_order = cfg->struct_size >= offsetof(ldpc_ctx_config, sum_order) + sizeof(int) ? cfg->sum_order : LDPC_SUM_REFERENCE;
     if (sum_order != LDPC_SUM_REFERENCE && sum_order != LDPC_SUM_ARRAYLET && sum_order != LDPC_SUM_SPARSE) { set_error(LDPC_EINVAL, "unknown sum order %d", sum_order); return nullptr; }
+    // llr_qscale sits where the structure ended in padding before it was added: it is looked at for LDPC_I8 alone, a dtype no caller
+    // built against the older header can name
+    float llr_qscale = dtype == LDPC_I8 && cfg->struct_size >= offsetof(ldpc_ctx_config, llr_qscale) + sizeof(float) ? cfg->llr_qscale : 0.f;
+    if (!(llr_qscale >= 0.f) || llr_qscale > 3.4028234e38f) { set_error(LDPC_EINVAL, "llr_qscale %g: the quantiser's scale must be finite and > 0 (0: the default, 4)", (double)cfg->llr_qscale); return nullptr; }
+    if (llr_qscale == 0.f) llr_qscale = 4.f;
     if (sum_order != LDPC_SUM_REFERENCE && (schedule != LDPC_SCHED_FLOODING || path == LDPC_PATH_FUSED || cfg->dtype == LDPC_F16 || cfg->dtype == LDPC_F16PK)) {
         set_error(LDPC_EUNSUPPORTED, "LDPC_SUM_ARRAYLET / LDPC_SUM_SPARSE are parity modes: flooding schedule, flood path, f32 or f64");
         return nullptr;
@@ -464,7 +471,7 @@ ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cf
         return nullptr;
     }
     if (!code || max_batch <= 0 || (variant != LDPC_TANH && variant != LDPC_MINSUM && variant != LDPC_TANH_CM && variant != LDPC_TANH_CUDA32) ||
-        (dtype != LDPC_F32 && dtype != LDPC_F64 && dtype != LDPC_F16 && dtype != LDPC_F16PK) ||
+        (dtype != LDPC_F32 && dtype != LDPC_F64 && dtype != LDPC_F16 && dtype != LDPC_F16PK && dtype != LDPC_I8) ||
         (path != LDPC_PATH_AUTO && path != LDPC_PATH_FLOOD && path != LDPC_PATH_FUSED)) {
         set_error(LDPC_EINVAL, "ldpc_ctx_create: bad arguments (variant=%d dtype=%d max_batch=%d path=%d)", variant, dtype, max_batch, path);
         return nullptr;
@@ -481,11 +488,12 @@ ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cf
     ldpc_code_dev tabs;
     if (code_upload(code, device, &tabs) != LDPC_OK) return nullptr;
 
-    ldpc::Backend *backend = ldpc::make_backend(*code, tabs, variant, dtype, schedule, sum_order, path, max_batch);
+    ldpc::Backend *backend = ldpc::make_backend(*code, tabs, variant, dtype, schedule, sum_order, path, max_batch, llr_qscale);
     if (!backend) return nullptr;
     ldpc_ctx *ctx = new (std::nothrow) ldpc_ctx();
     if (!ctx) { delete backend; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
     ctx->code = code; ctx->max_batch = max_batch; ctx->device = device; ctx->schedule = schedule; ctx->backend = backend;
+    ctx->dtype = dtype; ctx->llr_qscale = dtype == LDPC_I8 ? llr_qscale : 0.f;
     backend->timer = &ctx->timer;
     hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -527,7 +535,17 @@ static int check_call(ldpc_ctx *ctx, int max_iters, int batch) {
     return LDPC_OK;
 }
 
-// device-side core: d_llr is [batch][N] of element type fmt (ldpc::LLR_F32 / LLR_F64 / LLR_F16); outputs device pointers (may be null)
+// int8 LLRs (ldpc::LLR_I8) are the input of the fixed-point decoder alone
+static int check_format(const ldpc_ctx *ctx, int fmt) {
+    if (fmt == ldpc::LLR_I8 && ctx->dtype != LDPC_I8)
+        return set_error(LDPC_EUNSUPPORTED, "int8 LLRs are accepted by LDPC_I8 contexts only (this context's dtype is %d)", ctx->dtype);
+    return LDPC_OK;
+}
+static size_t llr_bytes(int fmt) { return fmt == ldpc::LLR_F64 ? 8 : fmt == ldpc::LLR_F16 ? 2 : fmt == ldpc::LLR_I8 ? 1 : 4; }
+// the packed entry points' llr_f16 argument: 0 float32, 1 binary16 patterns, 2 int8
+static int packed_format(int llr_f16) { return llr_f16 == 2 ? ldpc::LLR_I8 : llr_f16 ? ldpc::LLR_F16 : ldpc::LLR_F32; }
+
+// device-side core: d_llr is [batch][N] of element type fmt (ldpc::LLR_F32 / LLR_F64 / LLR_F16 / LLR_I8); outputs device pointers (may be null)
 static int decode_dev(ldpc_ctx *ctx, hipStream_t st, int max_iters, int batch, const void *d_llr, int fmt,
                       uint8_t *d_bits, int32_t *d_iters, uint8_t *d_conv, double *d_final, double *d_trace) {
     if (batch == 0) return LDPC_OK;
@@ -599,6 +617,7 @@ static int decode_chunk(ldpc_ctx *ctx, hipStream_t st, int max_iters, int batch,
 static int decode_host(ldpc_ctx *ctx, int max_iters, int batch, const void *llr, int fmt, uint8_t *bits,
                        int32_t *iters, uint8_t *converged, double *final_lam, double *trace_lam) {
     int rc = check_call(ctx, max_iters, batch);
+    if (rc == LDPC_OK) rc = check_format(ctx, fmt);
     if (rc != LDPC_OK) return rc;
     if (batch == 0) return LDPC_OK;
     if (!llr || !bits) return set_error(LDPC_EINVAL, "null llr/bits");
@@ -631,7 +650,7 @@ static int decode_host(ldpc_ctx *ctx, int max_iters, int batch, const void *llr,
             return rc;
         }
     }
-    const size_t N = (size_t)ctx->code->N, es = fmt == ldpc::LLR_F64 ? 8 : (fmt == ldpc::LLR_F16 ? 2 : 4);
+    const size_t N = (size_t)ctx->code->N, es = llr_bytes(fmt);
     if (batch <= ldpc_ctx::kSmallFrames && !final_lam && !trace_lam) {   // latency path (allocates 16 frames, never the full-size staging)
         const size_t cap = (size_t)ldpc_ctx::kSmallFrames;
         const size_t out_cap = cap * N + cap * sizeof(int32_t) + cap + 16;
@@ -738,6 +757,7 @@ int ldpc_decode_one(ldpc_ctx *ctx, int max_iters, const double *llr, uint8_t *bi
 static int decode_dev_checked(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int fmt, uint8_t *d_bits,
                               int32_t *d_iters, uint8_t *d_converged, void *stream) {
     int rc = check_call(ctx, max_iters, batch);
+    if (rc == LDPC_OK) rc = check_format(ctx, fmt);
     if (rc != LDPC_OK) return rc;
     if (batch == 0) return LDPC_OK;
     if (!d_llr || !d_bits) return set_error(LDPC_EINVAL, "null d_llr/d_bits");
@@ -755,25 +775,37 @@ int ldpc_decode_batch_dev_f16(ldpc_ctx *ctx, int max_iters, int batch, const uin
     return decode_dev_checked(ctx, max_iters, batch, d_llr, ldpc::LLR_F16, d_bits, d_iters, d_converged, stream);
 }
 
+int ldpc_decode_batch_i8(ldpc_ctx *ctx, int max_iters, int batch, const int8_t *llr, uint8_t *bits, int32_t *iters,
+                         uint8_t *converged) {
+    return decode_host(ctx, max_iters, batch, llr, ldpc::LLR_I8, bits, iters, converged, nullptr, nullptr);
+}
+
+int ldpc_decode_batch_dev_i8(ldpc_ctx *ctx, int max_iters, int batch, const int8_t *d_llr, uint8_t *d_bits,
+                             int32_t *d_iters, uint8_t *d_converged, void *stream) {
+    return decode_dev_checked(ctx, max_iters, batch, d_llr, ldpc::LLR_I8, d_bits, d_iters, d_converged, stream);
+}
+
 int ldpc_decode_batch_dev_packed(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int llr_f16, uint8_t *d_packed, int32_t *d_iters,
                                  uint8_t *d_converged, void *stream) {
     int rc = check_call(ctx, max_iters, batch);
+    if (rc == LDPC_OK) rc = check_format(ctx, packed_format(llr_f16));
     if (rc != LDPC_OK) return rc;
     if (batch == 0) return LDPC_OK;
     if (!d_llr || !d_packed) return set_error(LDPC_EINVAL, "null d_llr/d_packed");
     if (!ctx->d_unpacked) HIPCHK(hipMalloc((void **)&ctx->d_unpacked, (size_t)ctx->max_batch * ctx->code->N));
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    rc = decode_dev(ctx, st, max_iters, batch, d_llr, llr_f16 ? ldpc::LLR_F16 : ldpc::LLR_F32, ctx->d_unpacked, d_iters, d_converged, nullptr, nullptr);
+    rc = decode_dev(ctx, st, max_iters, batch, d_llr, packed_format(llr_f16), ctx->d_unpacked, d_iters, d_converged, nullptr, nullptr);
     if (rc != LDPC_OK) return rc;
     return ldpc::pack_bits(st, ctx->d_unpacked, d_packed, batch, ctx->code->N);
 }
 
 int ldpc_decode_batch_packed(ldpc_ctx *ctx, int max_iters, int batch, const void *llr, int llr_f16, uint8_t *packed, int32_t *iters, uint8_t *converged) {
     int rc = check_call(ctx, max_iters, batch);
+    if (rc == LDPC_OK) rc = check_format(ctx, packed_format(llr_f16));
     if (rc != LDPC_OK) return rc;
     if (batch == 0) return LDPC_OK;
     if (!llr || !packed) return set_error(LDPC_EINVAL, "null llr/packed");
-    const size_t N = (size_t)ctx->code->N, PB = (N + 7) / 8, es = llr_f16 ? 2 : 4;
+    const size_t N = (size_t)ctx->code->N, PB = (N + 7) / 8, es = llr_bytes(packed_format(llr_f16));
     if ((rc = ensure_staging(ctx, false)) != LDPC_OK) return rc;       // (d_in / d_iters / d_conv of the chunked pipeline; its d_bits slots are not used here)
     if (!ctx->d_packed) HIPCHK(hipMalloc((void **)&ctx->d_packed, (size_t)ctx->max_batch * PB));
     hipError_t e = hipSuccess;
@@ -784,7 +816,7 @@ int ldpc_decode_batch_packed(ldpc_ctx *ctx, int max_iters, int batch, const void
         hipStream_t st = ctx->pstream[slot];
         e = hipMemcpyAsync(ctx->d_in[slot], (const char *)llr + (size_t)f0 * N * es, (size_t)nb * N * es, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) break;
-        rc = decode_chunk(ctx, st, max_iters, nb, ctx->d_in[slot], llr_f16 ? ldpc::LLR_F16 : ldpc::LLR_F32, ctx->d_bits[slot], ctx->d_iters[slot], ctx->d_conv[slot], nullptr, nullptr);
+        rc = decode_chunk(ctx, st, max_iters, nb, ctx->d_in[slot], packed_format(llr_f16), ctx->d_bits[slot], ctx->d_iters[slot], ctx->d_conv[slot], nullptr, nullptr);
         if (rc == LDPC_OK) rc = ldpc::pack_bits(st, ctx->d_bits[slot], ctx->d_packed + (size_t)f0 * PB, nb, (int)N);
         if (rc != LDPC_OK) break;
         e = hipMemcpyAsync(packed + (size_t)f0 * PB, ctx->d_packed + (size_t)f0 * PB, (size_t)nb * PB, hipMemcpyDeviceToHost, st);

@@ -17,7 +17,8 @@ struct Backend {
     // families whose instance depends on the call
     LaunchInfo info;
     virtual ~Backend() {}
-    // d_llr [batch][N] of element type llr_fmt (LLR_F32 / LLR_F64 / LLR_F16); device outputs, all but d_bits may be null
+    // d_llr [batch][N] of element type llr_fmt (LLR_F32 / LLR_F64 / LLR_F16; LLR_I8 reaches LDPC_I8 contexts only: api.cc decode_dev);
+    // device outputs, all but d_bits may be null
     virtual int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                        uint8_t *d_conv, double *d_final, double *d_trace) = 0;
     // one teacher-forced iteration from given (lam, ne) in f64 (ldpc_debug_step), or LDPC_EUNSUPPORTED with the reason
@@ -30,9 +31,10 @@ struct Backend {
 };
 
 // The decoder for a validated context configuration (api.cc ldpc_ctx_create_cfg), on the calling thread's current device, whose
-// graph tables are `tabs`.  nullptr + set_error when no kernel serves the configuration or creating it failed.
+// graph tables are `tabs`.  nullptr + set_error when no kernel serves the configuration or creating it failed.  llr_qscale: the
+// quantiser's scale of an LDPC_I8 context.
 Backend *make_backend(const ldpc_code &c, const ldpc_code_dev &tabs, int variant, int dtype, int schedule, int sum_order, int path,
-                      int max_batch);
+                      int max_batch, float llr_qscale = 0.f);
 
 // null when the row-layered schedule's layers are the block rows of the code's QC description, else why not
 const char *layers_why_not(const ldpc_code &c);

@@ -5,7 +5,7 @@
 //     message_length, codeword_length, with the same code-name grammar (Utils.hs:82-88,100-108):
 //       ldpc/<decoder>/<matrix>/<max-rounds>[/<x>/<y>]      rate = x % y
 //     decoders registered here: hip-tanh, hip-minsum, optionally -layered (row-layered schedule, an extension),
-//     then an optional dtype suffix -f32 (default), -f64, -f16 (new tokens next to the reference's registry,
+//     then an optional dtype suffix -f32 (default), -f64, -f16, -i8 (new tokens next to the reference's registry,
 //     main/Main.hs:34-36).
 // GHC is not available in this image, so this layer is C++ behind the same C ABI; INTEGRATION.md
 // has the Haskell module that calls the ABI from the reference itself.
@@ -469,6 +469,7 @@ ldpc_ecc *ldpc_ecc_create_replicas(const char *codes_dir, const char *code_name,
         if (ends("-f16pk")) { dtype = LDPC_F16PK; dec.resize(dec.size() - 6); }   // packed fp16 arithmetic, two frames per lane (min-sum)
         else if (ends("-f64")) { dtype = LDPC_F64; dec.resize(dec.size() - 4); }
         else if (ends("-f16")) { dtype = LDPC_F16; dec.resize(dec.size() - 4); }
+        else if (ends("-i8")) { dtype = LDPC_I8; dec.resize(dec.size() - 3); }        // int8 fixed-point layered min-sum (qscale 4)
         else if (ends("-f32")) { dec.resize(dec.size() - 4); }
         int variant, schedule = LDPC_SCHED_FLOODING;
         bool as_bool = false;   // "-bool": take H as a plain Boolean matrix (the Haskell binding's `Matrix Bool` flavour, haskell/.../HIP.hs)
@@ -500,7 +501,7 @@ ldpc_ecc *ldpc_ecc_create_replicas(const char *codes_dir, const char *code_name,
         else if (dec == "hip-tanh-cm") variant = LDPC_TANH_CM;   // the reference's `arraylet-cm` numerics (f64 parity mode)
         else if (dec == "hip-tanh-cuda32") variant = LDPC_TANH_CUDA32;   // the reference's `cuda-arraylet2` numerics (f32 parity mode)
         else if (dec == "hip-minsum") variant = LDPC_MINSUM;
-        else { set_error(LDPC_ENOTFOUND, "decoder '%s' is not provided by libldpc_hip (hip-tanh, hip-minsum [-layered][-bool][-f32|-f64|-f16], or a reference name: reference, min, sparse, sparsemin, arraylet, arraylet-min, arraylet-cm, cuda-arraylet1/2)", xs[1].c_str()); return nullptr; }
+        else { set_error(LDPC_ENOTFOUND, "decoder '%s' is not provided by libldpc_hip (hip-tanh, hip-minsum [-layered][-bool][-f32|-f64|-f16|-i8], or a reference name: reference, min, sparse, sparsemin, arraylet, arraylet-min, arraylet-cm, cuda-arraylet1/2)", xs[1].c_str()); return nullptr; }
 
         // A matrix name that is a plain FILE under codes_dir is a stand-alone parity-check matrix in
         // MacKay's alist order with no generator (codes/1920.1280.3.303; the reference cannot load it,

@@ -11,7 +11,8 @@
 
 namespace ldpc {
 // element type of the [batch][N] channel-LLR array a decode entry point hands to the kernels
-enum { LLR_F32 = 0, LLR_F64 = 1, LLR_F16 = 2 };
+// (LLR_I8: int8 fixed-point LLRs, taken by LDPC_I8 contexts only -- csrc/layered_csr.hip dispatches it itself)
+enum { LLR_F32 = 0, LLR_F64 = 1, LLR_F16 = 2, LLR_I8 = 3 };
 
 
 int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));

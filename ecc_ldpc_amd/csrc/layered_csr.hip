@@ -19,6 +19,12 @@
 // saturation a frame that diverges reaches +-inf, then NaN, whose hard decisions are an all-zero "codeword": that instance carries the
 // non-finite veto of ldpc_math.h kVetoesNonFinite -- when a frame's stop rule fires the workgroup scans its lam once, and any cell
 // that is not finite turns "converged" into "failed" (flag 0, the sweep limit as its count, the channel's decisions and LLRs).
+// int8_t (LDPC_I8) is a FIXED-POINT decoder, the kind hardware receivers implement -- specification tests/layered_i8_spec.py,
+// reproduced bit for bit: the channel LLRs are quantised on load, q = clip(rint(llr * qscale), -127, 127) with one float multiply
+// (int8 LLRs, format LLR_I8, are taken as they are, -128 as -127); lam is one byte per column (N + 32 bytes of LDS, byte LDS loads and
+// stores); a row is 32-bit integer arithmetic with the 3/4 as (3 m + 2) >> 2 and every lam write clipped to +-127 -- no float
+// instruction inside a sweep, no veto (the clip bounds the state); a row record is 8 bytes {3/4 min1 | 3/4 min2 << 16, signs |
+// arg-min}, one dwordx2 each way: sweeps * 16 M bytes per frame.  Same column table, steps, slabs and control words.
 // Algorithmic HBM bytes per frame: sweeps * 24 M (the first sweep writes only) + the LLRs in + the bits out; the column table
 // (2 bytes per padded edge) is read by every workgroup every sweep and stays in L2.
 #include <stdio.h>
@@ -37,6 +43,8 @@ namespace ldpc {
 typedef const __attribute__((address_space(4))) int32_t *ctab_t;   // graph tables: scalar loads (never written by the kernel)
 
 struct CsrRec { float c1, c2; uint32_t meta; };   // meta: bit (deg-1-k) = sign bit of the message on edge k; bits 27..31 = an arg-min edge
+// int8 lam: the two message magnitudes (3/4 min1 in bits 0..15, 3/4 min2 in bits 16..31; both < 2^9) and the same meta word
+struct __attribute__((aligned(8))) CsrRecI8 { uint32_t mags, meta; };
 
 constexpr uint16_t kNoEdge = 0xFFFF;
 
@@ -50,6 +58,7 @@ struct CsrLayDev {
 
 struct CsrLayArgs {
     const void *llr; int llr_fmt;   // [batch][N]
+    float qscale;                   // (int8 lam) the quantiser's scale
     uint8_t *bits; int32_t *iters; uint8_t *conv;
     double *final_lam;              // may be null
     int batch, max_iters;
@@ -73,12 +82,14 @@ typedef float float8 __attribute__((ext_vector_type(8)));
 template <typename LT> struct Cell;
 template <> struct Cell<_Float16> {
     typedef half8 vec8;
+    typedef CsrRec Rec;
     static __device__ __forceinline__ _Float16 of(float v) { return sat16(v); }
     static __device__ __forceinline__ void st8(_Float16 *p, const half8 &h) { *reinterpret_cast<half8 *>(p) = h; }
     static __device__ __forceinline__ half8 ld8(const _Float16 *p) { return *reinterpret_cast<const half8 *>(p); }
 };
 template <> struct Cell<float> {
     typedef float8 vec8;
+    typedef CsrRec Rec;
     static __device__ __forceinline__ float of(float v) { return v; }
     static __device__ __forceinline__ void st8(float *p, const float8 &h) {      // two 16-byte LDS stores
         *reinterpret_cast<float4 *>(p) = make_float4(h[0], h[1], h[2], h[3]);
@@ -111,6 +122,111 @@ template <typename LT, int FMT> __device__ __forceinline__ void load_llr8(const 
 
 template <typename LT> __device__ __forceinline__ __attribute__((address_space(3))) LT *lds_cell(uint32_t byte_addr) {
     return (__attribute__((address_space(3))) LT *)(uintptr_t)byte_addr;
+}
+
+// ---- int8 lam (LDPC_I8): the quantiser of tests/layered_i8_spec.py, the frame's way in and out, the row in integers
+template <> struct Cell<int8_t> { typedef uint2 vec8; typedef CsrRecI8 Rec; };      // (eight cells: the bytes of two words)
+
+__device__ __forceinline__ int quant_i8(float v, float qs) {
+    const float r = __builtin_rintf(v * qs);           // ONE float multiply (no contraction), ties to even
+    return r != r ? 0 : (int)__builtin_amdgcn_fmed3f(r, -127.f, 127.f);
+}
+// LLR_I8 is dispatched here only: the other kernels' prologues (ldpc_math.h with_llr_format / load_llr_as) do not know it
+template <class F> __device__ __forceinline__ void with_llr_format_i8(int fmt, F &&f) {
+    if (fmt == LLR_I8) f(std::integral_constant<int, LLR_I8>{});
+    else with_llr_format(fmt, f);
+}
+template <int FMT> __device__ __forceinline__ int load_q(const void *base, size_t i, float qs) {
+    if constexpr (FMT == LLR_I8) return max((int)reinterpret_cast<const int8_t *>(base)[i], -127);
+    else return quant_i8(load_llr_as<float, FMT>(base, i), qs);
+}
+// eight channel LLRs as the eight cells of two words (one 8-byte request of int8 LLRs, 16-byte requests of fp16 / f32 ones)
+template <int FMT> __device__ __forceinline__ uint2 load_q8(const void *base, size_t i, float qs) {
+    int q[8];
+    if constexpr (FMT == LLR_I8) {
+        const uint2 w = *reinterpret_cast<const uint2 *>(reinterpret_cast<const int8_t *>(base) + i);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { q[k] = max((int)(int8_t)(w.x >> (8 * k)), -127); q[k + 4] = max((int)(int8_t)(w.y >> (8 * k)), -127); }
+    } else if constexpr (FMT == LLR_F16) {
+        const half8 v = *reinterpret_cast<const half8 *>(reinterpret_cast<const _Float16 *>(base) + i);
+#pragma unroll
+        for (int k = 0; k < 8; k++) q[k] = quant_i8((float)v[k], qs);
+    } else if constexpr (FMT == LLR_F32) {
+        const float4 a = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + i);
+        const float4 b = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + i + 4);
+        q[0] = quant_i8(a.x, qs); q[1] = quant_i8(a.y, qs); q[2] = quant_i8(a.z, qs); q[3] = quant_i8(a.w, qs);
+        q[4] = quant_i8(b.x, qs); q[5] = quant_i8(b.y, qs); q[6] = quant_i8(b.z, qs); q[7] = quant_i8(b.w, qs);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; k++) q[k] = load_q<FMT>(base, i + k, qs);
+    }
+    uint2 w = make_uint2(0u, 0u);
+#pragma unroll
+    for (int k = 0; k < 4; k++) { w.x |= ((uint32_t)q[k] & 0xFFu) << (8 * k); w.y |= ((uint32_t)q[k + 4] & 0xFFu) << (8 * k); }
+    return w;
+}
+// the hard decisions of eight cells, one byte per bit
+__device__ __forceinline__ uint2 hard_q8(uint2 w) {
+    uint2 b = make_uint2(0u, 0u);
+#pragma unroll
+    for (int k = 0; k < 4; k++) { b.x |= ((int8_t)(w.x >> (8 * k)) > 0 ? 1u : 0u) << (8 * k); b.y |= ((int8_t)(w.y >> (8 * k)) > 0 ? 1u : 0u) << (8 * k); }
+    return b;
+}
+
+// one check row in 32-bit integers (tests/layered_i8_spec.py row_update); same table walk, same meta word as csr_row below
+template <typename LT, int D, bool EXACT, bool FIRST>
+__device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint32_t lam0, const CsrRecI8 &in, CsrRecI8 &out, bool &odd, bool &flip) {
+    uint32_t ad[D];
+    int t[D];
+    int deg = EXACT ? D : 0;
+#pragma unroll
+    for (int k = 0; k < D; k++) {
+        const uint32_t c = (EXACT || k < wd) ? (uint32_t)cp[(size_t)k * T] : (uint32_t)kNoEdge;
+        const bool v = EXACT || c != kNoEdge;
+        if constexpr (!EXACT) deg += v ? 1 : 0;
+        ad[k] = lam0 + (v ? c : 0u);
+    }
+#pragma unroll
+    for (int k = 0; k < D; k++) t[k] = (int)*lds_cell<int8_t>(ad[k]);
+    uint32_t hl = 0, X = 0;                             // hl: hard(lam) of edge k at bit k; X: bit 31 = xor of the signs of t
+    int m1 = 0x7FFF, m2 = 0x7FFF;
+    const int i1 = (int)(in.mags & 0xFFFFu), i2 = (int)(in.mags >> 16);
+    const uint32_t oidx = in.meta >> 27;
+#pragma unroll
+    for (int k = 0; k < D; k++) {
+        if (EXACT || k < deg) {
+            hl |= (t[k] > 0 ? 1u : 0u) << k;
+            if constexpr (!FIRST) {
+                const int mag = ((uint32_t)k == oidx) ? i2 : i1;
+                const int sg = (int)(in.meta << (32 - deg + k)) >> 31;      // -1: the message is negative
+                t[k] -= (mag ^ sg) - sg;
+            }
+            X ^= (uint32_t)t[k];
+            const int a = abs(t[k]);
+            m2 = min(m2, max(m1, a));
+            m1 = min(m1, a);
+        }
+    }
+    odd |= (__builtin_popcount(hl) & 1) != 0;
+    const int n1 = (3 * m1 + 2) >> 2, n2 = (3 * m2 + 2) >> 2;      // 3/4, rounded half up
+    // message k is negative iff (deg odd) ^ (xor of all signs of t) ^ (sign of t_k)
+    const int fl = -(int)(((X >> 31) ^ (uint32_t)deg) & 1u);       // -1 or 0
+    uint32_t tsig = 0, nidx = 0;
+#pragma unroll
+    for (int k = 0; k < D; k++) {
+        if (EXACT || k < deg) {
+            const bool ismin = abs(t[k]) == m1;             // ties: n2 == n1, either answer gives the same message
+            const int sg = fl ^ (t[k] >> 31);
+            const int mag = ismin ? n2 : n1;
+            nidx = ismin ? (uint32_t)k : nidx;
+            tsig = (tsig << 1) | ((uint32_t)t[k] >> 31);
+            const int nw = min(max(t[k] + ((mag ^ sg) - sg), -127), 127);
+            flip |= (nw > 0) != (((hl >> k) & 1u) != 0);
+            *lds_cell<int8_t>(ad[k]) = (int8_t)nw;
+        }
+    }
+    const uint32_t nsig = tsig ^ (fl ? ((1u << deg) - 1u) : 0u);
+    out.mags = (uint32_t)n1 | ((uint32_t)n2 << 16); out.meta = nsig | (nidx << 27);
 }
 
 // one check row: layered_lds.hip lds_row with the row's weight per LANE (deg <= D; EXACT: every lane's row has weight D).  cp: this
@@ -173,7 +289,8 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
 
 // the instance for a wave: wd = its heaviest row, uni = all its rows have that weight
 template <typename LT, int DCLASS, bool FIRST>
-__device__ __forceinline__ void csr_row_at(const uint16_t *cp, int T, int wd, bool uni, uint32_t lam0, const CsrRec &in, CsrRec &out, bool &odd, bool &flip) {
+__device__ __forceinline__ void csr_row_at(const uint16_t *cp, int T, int wd, bool uni, uint32_t lam0, const typename Cell<LT>::Rec &in,
+                                           typename Cell<LT>::Rec &out, bool &odd, bool &flip) {
     if (uni) {
         switch (wd) {
             case 2: csr_row<LT, 2, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
@@ -202,8 +319,10 @@ __device__ __forceinline__ void csr_row_at(const uint16_t *cp, int T, int wd, bo
 // up to 27 addresses, LLRs and differences per lane: that instance is built for 512 threads (256 registers per lane, no spill).
 constexpr int csr_max_threads(int dclass) { return dclass > 20 ? 512 : 1024; }
 template <int DCLASS, typename LT = _Float16>
-__global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(CsrLayDev g, CsrRec *rec_all, CsrLayArgs A) {
+__global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(CsrLayDev g, typename Cell<LT>::Rec *rec_all, CsrLayArgs A) {
     typedef typename Cell<LT>::vec8 cell8;
+    typedef typename Cell<LT>::Rec Rec;               // the row record follows the lam cell: 12 bytes (fp16, f32), 8 bytes (int8)
+    constexpr bool kInt8 = std::is_same<LT, int8_t>::value;
     constexpr bool kVeto = kVetoesNonFinite<float, LDPC_V_MINSUM> && sizeof(LT) == 4;    // (fp16 lam saturates by its own rule)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     LT *lam = reinterpret_cast<LT *>(smem);
@@ -214,14 +333,32 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
     const int W = T >> 6, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nslab = ((ctab_t)g.step_ptr)[g.nstep];
     const uint32_t lam0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem;   // LDS byte address of lam
-    CsrRec *const rec = rec_all + (size_t)blockIdx.x * nslab * T + tid;     // this thread's record of slab s: rec[s T]
+    Rec *const rec = rec_all + (size_t)blockIdx.x * nslab * T + tid;        // this thread's record of slab s: rec[s T]
     int frame = blockIdx.x;
     while (frame < A.batch) {
         const size_t fN = (size_t)frame * g.N;
         // ---- lam <- channel LLRs, as stored: saturated, rounded to fp16 / the float (eight per lane and request when the frame is 16-byte aligned)
-        const bool wide = (g.N & 7) == 0 && A.llr_fmt != LLR_F64 && !A.final_lam &&
+        bool wide;
+        if constexpr (kInt8)    // (int8 LLRs: 8 cells are one 8-byte request)
+            wide = (g.N & 7) == 0 && A.llr_fmt != LLR_F64 && !A.final_lam && (((uintptr_t)A.bits + fN) & 7) == 0 &&
+                   (((uintptr_t)A.llr + fN * (A.llr_fmt == LLR_I8 ? 1 : A.llr_fmt == LLR_F16 ? 2 : 4)) & (A.llr_fmt == LLR_I8 ? 7 : 15)) == 0;
+        else
+            wide = (g.N & 7) == 0 && A.llr_fmt != LLR_F64 && !A.final_lam &&
                           (((uintptr_t)A.llr + fN * (A.llr_fmt == LLR_F16 ? 2 : 4)) & 15) == 0 && (((uintptr_t)A.bits + fN) & 7) == 0;   // (uniform)
-        if (wide) {
+        if constexpr (kInt8) {
+            // ---- lam <- the quantised channel LLRs (int8 LLRs as they are)
+            if (wide) {
+                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 4
+                    for (int i = tid * 8; i < g.N; i += T * 8) *reinterpret_cast<uint2 *>(lam + i) = load_q8<decltype(fmt)::value>(A.llr, fN + i, A.qscale);
+                });
+            } else {
+                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 8
+                    for (int i = tid; i < g.N; i += T) lam[i] = (int8_t)load_q<decltype(fmt)::value>(A.llr, fN + i, A.qscale);
+                });
+            }
+        } else if (wide) {
             with_llr_format(A.llr_fmt, [&](auto fmt) {
 #pragma unroll 4
                 for (int i = tid * 8; i < g.N; i += T * 8) {
@@ -265,12 +402,12 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
                     for (int s = s0; s < s1; s++) {
                         const int c0 = ((ctab_t)g.slab)[2 * s], wv = ((ctab_t)g.wdeg)[s * W + wave];
                         const uint16_t *cp = g.cols + c0 + tid;
-                        CsrRec out;
+                        Rec out;
                         if (n == 1) {
-                            const CsrRec none{0.f, 0.f, 0u};
+                            const Rec none{};
                             csr_row_at<LT, DCLASS, true>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, none, out, odd, flip);
                         } else {
-                            const CsrRec in = rec[(size_t)s * T];
+                            const Rec in = rec[(size_t)s * T];
                             csr_row_at<LT, DCLASS, false>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, in, out, odd, flip);
                         }
                         rec[(size_t)s * T] = out;
@@ -294,7 +431,27 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
             }
         }
         // ---- result: hard(lam) of a frame that stopped by the rule, the channel's decisions (as stored) otherwise (Orig.hs:69-70)
-        if (wide) {
+        if constexpr (kInt8) {
+            // a frame out of sweeps quantises its channel LLRs again; no veto: the clip bounds the state
+            if (wide) {
+                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 4
+                    for (int i = tid * 8; i < g.N; i += T * 8) {
+                        const uint2 w = conv ? *reinterpret_cast<const uint2 *>(lam + i) : load_q8<decltype(fmt)::value>(A.llr, fN + i, A.qscale);
+                        *reinterpret_cast<uint2 *>(A.bits + fN + i) = hard_q8(w);
+                    }
+                });
+            } else {
+                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 4
+                    for (int i = tid; i < g.N; i += T) {
+                        const int v = conv ? (int)lam[i] : load_q<decltype(fmt)::value>(A.llr, fN + i, A.qscale);
+                        A.bits[fN + i] = v > 0 ? 1 : 0;
+                        if (A.final_lam) A.final_lam[fN + i] = (double)v / (double)A.qscale;
+                    }
+                });
+            }
+        } else if (wide) {
             auto put = [&](int i, const cell8 &h) {
                 uint32_t lo = 0, hi = 0;
 #pragma unroll
@@ -338,23 +495,31 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
 namespace {
 
 int dclass_of(int max_row_deg) { return max_row_deg <= 8 ? 8 : (max_row_deg <= 20 ? 20 : 32); }
-size_t lds_bytes_for(const ldpc_code &c, int dtype) { return (((size_t)c.N * (dtype == LDPC_F32 ? 4 : 2) + 15) & ~(size_t)15) + 32; }
-typedef void (*csr_kernel_t)(CsrLayDev, CsrRec *, CsrLayArgs);
-template <typename LT> csr_kernel_t kernel_for(int dclass) {
+size_t cell_bytes(int dtype) { return dtype == LDPC_F32 ? 4 : dtype == LDPC_I8 ? 1 : 2; }
+size_t rec_bytes(int dtype) { return dtype == LDPC_I8 ? sizeof(CsrRecI8) : sizeof(CsrRec); }
+size_t lds_bytes_for(const ldpc_code &c, int dtype) { return (((size_t)c.N * cell_bytes(dtype) + 15) & ~(size_t)15) + 32; }
+template <typename LT> using csr_kernel_t = void (*)(CsrLayDev, typename Cell<LT>::Rec *, CsrLayArgs);
+template <typename LT> csr_kernel_t<LT> kernel_for(int dclass) {
     return dclass == 8 ? layered_csr_kernel<8, LT> : dclass == 20 ? layered_csr_kernel<20, LT> : layered_csr_kernel<32, LT>;
 }
-csr_kernel_t pick_kernel(int dclass, bool f32) { return f32 ? kernel_for<float>(dclass) : kernel_for<_Float16>(dclass); }
+const void *pick_kernel(int dclass, int dtype) {
+    return dtype == LDPC_F32 ? (const void *)kernel_for<float>(dclass) : dtype == LDPC_I8 ? (const void *)kernel_for<int8_t>(dclass) : (const void *)kernel_for<_Float16>(dclass);
+}
+template <typename LT> void launch(int dclass, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, void *rec, const CsrLayArgs &a) {
+    hipLaunchKernelGGL(kernel_for<LT>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a);
+}
 
 // ------------------------------------------------------------------ host side
 struct LayeredCsrState : Backend {
     int max_batch = 0, dclass = 8, grid = 0, nslab = 0;
-    bool f32 = false;           // lam cells are floats (LDPC_F32), not fp16
+    int dtype = LDPC_F16;       // the lam cell: fp16 (LDPC_F16), float (LDPC_F32) or int8 (LDPC_I8)
+    float qscale = 0.f;         // (LDPC_I8) the quantiser's scale
     size_t lds = 0;
     CsrLayDev g{};
     uint16_t *d_cols = nullptr;
     int32_t *d_slab = nullptr, *d_wdeg = nullptr, *d_step = nullptr;
     int *d_counter = nullptr;
-    CsrRec *rec = nullptr;
+    void *rec = nullptr;        // [grid][nslab][T] row records (CsrRec, or CsrRecI8 with int8 lam)
 
     ~LayeredCsrState() override {
         (void)hipFree(d_cols); (void)hipFree(d_slab); (void)hipFree(d_wdeg); (void)hipFree(d_step); (void)hipFree(d_counter); (void)hipFree(rec);
@@ -362,8 +527,9 @@ struct LayeredCsrState : Backend {
     int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                uint8_t *d_conv, double *d_final, double *d_trace) override;
     int step(hipStream_t, int, const double *, const double *, const double *, double *, double *, uint8_t *) override {
-        return set_error(LDPC_EUNSUPPORTED, f32 ? "no teacher-forced step on the on-chip layered kernel for any H (the record kernels keep no per-edge messages)"
-                                                : "no teacher-forced step with fp16 lam storage (the record kernels keep no per-edge messages)");
+        return set_error(LDPC_EUNSUPPORTED, dtype == LDPC_I8 ? "no teacher-forced step with LDPC_I8 (fixed-point state; the record kernels keep no per-edge messages)"
+                                            : dtype == LDPC_F32 ? "no teacher-forced step on the on-chip layered kernel for any H (the record kernels keep no per-edge messages)"
+                                                                : "no teacher-forced step with fp16 lam storage (the record kernels keep no per-edge messages)");
     }
     bool reads_llr_once(int) const override { return true; }
 };
@@ -372,22 +538,22 @@ struct LayeredCsrState : Backend {
 
 const char *layered_csr_why_not(const ldpc_code &c, int variant, int dtype) {
     if (variant != LDPC_MINSUM) return "the on-chip layered kernel for any H implements min-sum";
-    if (dtype != LDPC_F16 && dtype != LDPC_F32) return "the on-chip layered kernel for any H stores lam in fp16 (LDPC_F16) or in f32 (LDPC_F32)";
+    if (dtype != LDPC_F16 && dtype != LDPC_F32 && dtype != LDPC_I8) return "the on-chip layered kernel for any H stores lam in fp16 (LDPC_F16), in f32 (LDPC_F32) or in int8 (LDPC_I8)";
     if (c.max_row_deg > 27) return "check rows above weight 27 (a row record holds 27 sign bits)";
-    if (lds_bytes_for(c, dtype) > 160 * 1024) return dtype == LDPC_F32 ? "a frame's f32 LLRs exceed the 160 KB of LDS" : "a frame's fp16 LLRs exceed the 160 KB of LDS";
+    if (dtype != LDPC_I8 && lds_bytes_for(c, dtype) > 160 * 1024) return dtype == LDPC_F32 ? "a frame's f32 LLRs exceed the 160 KB of LDS" : "a frame's fp16 LLRs exceed the 160 KB of LDS";
     if (c.N > 65535) return "more than 65 535 columns (16-bit column table)";
     const char *e = getenv("LDPC_LAYERED_CSR");
     if (e && !strcmp(e, "0")) return "disabled (LDPC_LAYERED_CSR=0)";
     return nullptr;
 }
 
-Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch) {
+Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float qscale) {
     LayeredCsrState *s = new (std::nothrow) LayeredCsrState();
     if (!s) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
     try {
         // lam stays on-chip for the whole decode in one launch (only the row records travel to HBM): reported as the on-chip path
         s->path = LDPC_PATH_FUSED;
-        s->max_batch = max_batch; s->dclass = dclass_of(c.max_row_deg); s->f32 = dtype == LDPC_F32;
+        s->max_batch = max_batch; s->dclass = dclass_of(c.max_row_deg); s->dtype = dtype; s->qscale = qscale;
         // barrier steps: maximal runs of consecutive layers that share no column
         std::vector<std::vector<int>> steps;
         {
@@ -410,7 +576,27 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch) {
             std::stable_sort(st.begin(), st.end(), [&](int a, int b) { return deg(a) > deg(b); });   // heaviest first: uniform waves
             rmax = std::max(rmax, st.size());
         }
-        const int T = (int)std::min<size_t>(csr_max_threads(s->dclass), (rmax + 63) / 64 * 64), W = T / 64;
+        int T = (int)std::min<size_t>(csr_max_threads(s->dclass), (rmax + 63) / 64 * 64);
+        s->lds = lds_bytes_for(c, dtype);
+        const void *kern = pick_kernel(s->dclass, dtype);
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds);
+        // int8 lam: a frame of N = 64 800 takes 64.8 KB of LDS, so two workgroups fit a CU -- when the registers allow it.  1024 threads
+        // at more than 64 VGPRs fill the CU's register files alone; 512 threads leave room for a second workgroup, whose rows run
+        // while the first waits at a barrier.  Taken when it at least doubles the resident workgroups; the slabs only regroup rows
+        // of one step (column-disjoint), so the results do not depend on it.  The choice is to rest on the measurement that
+        // tools/layered_csr_rate.py --lam i8 makes of both sizes (LDPC_LAYERED_CSR_THREADS forces one); until that has been run on an
+        // MI355X it rests on this occupancy arithmetic alone.
+        if (dtype == LDPC_I8 && T > 512 && e == hipSuccess) {
+            int occ_t = 0, occ_half = 0;
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_t, kern, T, s->lds);
+            if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_half, kern, 512, s->lds);
+            if (e == hipSuccess && occ_half >= 2 * std::max(occ_t, 1)) T = 512;
+        }
+        if (const char *force = getenv("LDPC_LAYERED_CSR_THREADS")) {      // A/B switch (any lam type): a multiple of 64 within the instance's bound
+            const int t = atoi(force);
+            if (t >= 64 && t % 64 == 0 && t <= csr_max_threads(s->dclass)) T = t;
+        }
+        const int W = T / 64;
         std::vector<uint16_t> cols;
         std::vector<int32_t> slab, wdeg, step_ptr(1, 0);
         for (auto &st : steps) {
@@ -437,9 +623,6 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch) {
         }
         s->nslab = (int)(slab.size() / 2);
         s->g.N = c.N; s->g.T = T; s->g.nstep = (int)steps.size();
-        s->lds = lds_bytes_for(c, dtype);
-        const void *kern = (const void *)pick_kernel(s->dclass, s->f32);
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds);
         int per_cu = 0, dev = 0;
         hipDeviceProp_t prop;
         if (e == hipSuccess) e = hipGetDevice(&dev);
@@ -452,19 +635,19 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch) {
         if (e == hipSuccess) e = hipMalloc((void **)&s->d_wdeg, sizeof(int32_t) * std::max<size_t>(wdeg.size(), 1));
         if (e == hipSuccess) e = hipMalloc((void **)&s->d_step, sizeof(int32_t) * step_ptr.size());
         if (e == hipSuccess) e = hipMalloc((void **)&s->d_counter, sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&s->rec, sizeof(CsrRec) * (size_t)s->grid * std::max(s->nslab, 1) * T);
+        if (e == hipSuccess) e = hipMalloc(&s->rec, rec_bytes(dtype) * (size_t)s->grid * std::max(s->nslab, 1) * T);
         if (e == hipSuccess && !cols.empty()) e = hipMemcpy(s->d_cols, cols.data(), sizeof(uint16_t) * cols.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess && !slab.empty()) e = hipMemcpy(s->d_slab, slab.data(), sizeof(int32_t) * slab.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess && !wdeg.empty()) e = hipMemcpy(s->d_wdeg, wdeg.data(), sizeof(int32_t) * wdeg.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(s->d_step, step_ptr.data(), sizeof(int32_t) * step_ptr.size(), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             set_error(e == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "layered_csr_create (%d workgroups x %zu bytes of records): %s", s->grid,
-                      sizeof(CsrRec) * (size_t)s->nslab * T, hipGetErrorString(e));
+                      rec_bytes(dtype) * (size_t)s->nslab * T, hipGetErrorString(e));
             delete s;
             return nullptr;
         }
         s->g.cols = s->d_cols; s->g.slab = s->d_slab; s->g.wdeg = s->d_wdeg; s->g.step_ptr = s->d_step;
-        snprintf(s->info.name, sizeof(s->info.name), s->f32 ? "ldpc::layered_csr_kernel<%d, float>" : "ldpc::layered_csr_kernel<%d>", s->dclass);
+        snprintf(s->info.name, sizeof(s->info.name), dtype == LDPC_I8 ? "ldpc::layered_csr_kernel<%d, signed char>" : dtype == LDPC_F32 ? "ldpc::layered_csr_kernel<%d, float>" : "ldpc::layered_csr_kernel<%d>", s->dclass);
         s->info.threads = T; s->info.frames_per_wg = 1;
         return s;
     } catch (...) { delete s; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
@@ -474,13 +657,16 @@ int LayeredCsrState::decode(hipStream_t st, int max_iters, int batch, const void
                             uint8_t *d_conv, double *d_final, double *d_trace) {
     if (d_trace) return set_error(LDPC_EUNSUPPORTED, "layered_csr: no per-sweep trace (decode without one)");
     CsrLayArgs a{};
-    a.llr = d_llr; a.llr_fmt = llr_fmt; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final;
+    if (llr_fmt == LLR_I8 && dtype != LDPC_I8) return set_error(LDPC_EUNSUPPORTED, "int8 LLRs are taken by LDPC_I8 contexts only");
+    a.llr = d_llr; a.llr_fmt = llr_fmt; a.qscale = qscale; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final;
     a.batch = batch; a.max_iters = max_iters; a.work_counter = d_counter;
     hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(int), st);
     if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
     const dim3 grid(std::min(batch, this->grid)), block(g.T);
     if (timer) timer->begin(st);
-    hipLaunchKernelGGL(pick_kernel(dclass, f32), grid, block, lds, st, g, rec, a);
+    if (dtype == LDPC_I8) launch<int8_t>(dclass, grid, block, lds, st, g, rec, a);
+    else if (dtype == LDPC_F32) launch<float>(dclass, grid, block, lds, st, g, rec, a);
+    else launch<_Float16>(dclass, grid, block, lds, st, g, rec, a);
     if (timer) timer->end(st);
     e = hipGetLastError();
     if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr launch: %s", hipGetErrorString(e));

@@ -12,8 +12,9 @@ Backend *layered_qc_create(const ldpc_code &c, int variant, int dtype, int max_b
 const char *layered_lds_why_not(const ldpc_code &c, int variant, int dtype);
 Backend *layered_lds_create(const ldpc_code &c, int max_batch);
 // layered_csr.hip: the same for ANY H (column table in device memory, the code's layers merged into barrier steps) -- min-sum with
-// lam stored as fp16 (LDPC_F16, 2 N bytes of LDS) or as f32 (LDPC_F32, 4 N bytes: N <= 40 952; with the non-finite veto); lam never
-// leaves the chip, so the context reports LDPC_PATH_FUSED
+// lam stored as fp16 (LDPC_F16, 2 N bytes of LDS) or as f32 (LDPC_F32, 4 N bytes: N <= 40 952; with the non-finite veto), or the
+// int8 fixed-point decoder (LDPC_I8, N bytes; llr_qscale: its quantiser's scale); lam never leaves the chip, so the context reports
+// LDPC_PATH_FUSED
 const char *layered_csr_why_not(const ldpc_code &c, int variant, int dtype);
-Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch);
+Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float llr_qscale = 0.f);
 }  // namespace ldpc

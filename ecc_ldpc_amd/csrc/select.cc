@@ -20,6 +20,8 @@
 //                         - lam as f32 (LDPC_F32, N <= 40 952): LDPC_PATH_FUSED only.  LDPC_PATH_AUTO keeps such a context on (7): that
 //                           routing follows a measurement of this instance against flood.hip's layered kernel on the same frames and
 //                           layers (tools/layered_csr_rate.py --lam f32), it does not precede it
+//                         - lam as int8 (LDPC_I8, the fixed-point decoder): the only kernel of that dtype, so it is taken ahead of the
+//                           ladder, on any code (a QC code as its CSR form, with the layers it has): LDPC_PATH_AUTO or LDPC_PATH_FUSED
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -174,7 +176,15 @@ static Backend *frame_per_workgroup(const ldpc_code &c, int variant, int dtype, 
 }
 
 Backend *make_backend(const ldpc_code &c, const ldpc_code_dev &tabs, int variant, int dtype, int schedule, int sum_order, int path,
-                      int max_batch) {
+                      int max_batch, float llr_qscale) {
+    if (dtype == LDPC_I8) {     // the int8 fixed-point decoder: layered min-sum in csrc/layered_csr.hip, nothing else
+        const char *why = schedule != LDPC_SCHED_LAYERED ? "the flooding schedule (LDPC_SCHED_LAYERED only)"
+                          : variant != LDPC_MINSUM || sum_order != LDPC_SUM_REFERENCE ? "any rule but min-sum"
+                          : path == LDPC_PATH_FLOOD ? "LDPC_PATH_FLOOD (lam is kept on-chip: LDPC_PATH_AUTO or LDPC_PATH_FUSED)"
+                          : layered_csr_why_not(c, variant, dtype);
+        if (why) { set_error(LDPC_EUNSUPPORTED, "LDPC_I8 (int8 fixed-point layered min-sum) does not serve this request: %s", why); return nullptr; }
+        return layered_csr_create(c, dtype, max_batch, llr_qscale);
+    }
     if (dtype == LDPC_F16PK && (variant != LDPC_MINSUM || path == LDPC_PATH_FLOOD)) {
         set_error(LDPC_EUNSUPPORTED, "LDPC_F16PK (packed fp16 arithmetic, two frames per lane) exists for min-sum on the on-chip path");
         return nullptr;

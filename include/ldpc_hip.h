@@ -80,7 +80,19 @@ typedef enum { LDPC_TANH = 0, LDPC_MINSUM = 1, LDPC_TANH_CM = 2, LDPC_TANH_CUDA3
  *      run-time specialised ones for any other (ldpc_jit_prepare_for); anything else: LDPC_EUNSUPPORTED.  Its checker is the
  *      bit-exact emulation oracle/emulate_f16.py decode_minsum_pk16 / decode_minsum_pk16_layered; BER next to the F32
  *      decoder: DESIGN.md, profiles/r03_ber_pk16_vs_f32.txt. */
-typedef enum { LDPC_F32 = 0, LDPC_F64 = 1, LDPC_F16 = 2, LDPC_F16PK = 3 } ldpc_dtype;
+/* I8 (extension): a FIXED-POINT decoder, the arithmetic of hardware receivers (6-8 bit LLRs, layered min-sum); integers only, so a
+ *      BER is reproducible bit for bit.  Channel LLRs are quantised on load, q = clip(rint(float32(llr) * llr_qscale), -127, 127) -- one
+ *      float32 multiply, ties to even, NaN -> 0; int8 LLRs (ldpc_decode_batch_i8) are taken as they are, -128 as -127.  lam is an int8
+ *      cell in -127..127, hard(lam) = lam > 0.  A row: t_k = lam[c_k] - msg_k (not clamped), m1 / m2 the two smallest |t_k|,
+ *      |msg'_k| = (3 m + 2) >> 2 of the smallest of the OTHER edges (the 3/4 of Min.hs:78, rounded half up), negative iff
+ *      (weight odd) ^ (xor of the signs of all t_j) ^ (sign of t_k), a zero counting as positive; lam'[c_k] = clip(t_k + msg'_k, -127, 127).
+ *      Stopping rule of LDPC_SCHED_LAYERED; final_lam = lam / llr_qscale (the quantised channel LLRs / llr_qscale for a frame out of
+ *      sweeps).  Specification: tests/layered_i8_spec.py, reproduced bit for bit.  Min-sum, LDPC_SCHED_LAYERED, LDPC_PATH_AUTO or
+ *      LDPC_PATH_FUSED, on ANY code (a quasi-cyclic code as its CSR form, with the layers it has): csrc/layered_csr.hip with one byte of
+ *      LDS per column and 8-byte row records.  Row weight 2..27, N <= 65 535; the context reports LDPC_PATH_FUSED.  Anything else --
+ *      flooding, another rule, LDPC_PATH_FLOOD, ldpc_debug_step, ldpc_decode_trace, ldpc_jit_* -- is LDPC_EUNSUPPORTED.  Every decode
+ *      entry point is accepted (f32, fp16, f64 LLRs are quantised on load). */
+typedef enum { LDPC_F32 = 0, LDPC_F64 = 1, LDPC_F16 = 2, LDPC_F16PK = 3, LDPC_I8 = 4 } ldpc_dtype;
 /* message-passing schedule.  FLOODING: the reference's (Orig.hs:81-98: all checks, then all variables).
  * LAYERED (extension, no reference counterpart): checks layer by layer, each seeing the LLRs the layers before it
  * updated in the same sweep -- about half the sweeps to converge; stopping rule: before the first sweep the
@@ -186,9 +198,12 @@ typedef struct {
     size_t struct_size;
     int device, variant, dtype, max_batch, path, schedule;
     int sum_order;   /* ldpc_sum_order; read when struct_size covers it, else LDPC_SUM_REFERENCE */
+    float llr_qscale; /* LDPC_I8: the quantiser's scale (LLR units per integer step = 1 / llr_qscale); read for that dtype when struct_size
+                         covers it; 0 or absent: 4.0; anything else must be finite and > 0 (LDPC_EINVAL) */
 } ldpc_ctx_config;
 ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code, const ldpc_ctx_config *cfg);
 int ldpc_ctx_schedule(const ldpc_ctx *ctx);
+float ldpc_ctx_llr_qscale(const ldpc_ctx *ctx);   /* the quantiser's scale of an LDPC_I8 context, 0 for every other dtype */
 const ldpc_code *ldpc_ctx_code(const ldpc_ctx *ctx);
 int ldpc_ctx_max_batch(const ldpc_ctx *ctx);
 int ldpc_ctx_device(const ldpc_ctx *ctx);
@@ -229,9 +244,17 @@ int ldpc_decode_batch_f16(ldpc_ctx *ctx, int max_iters, int batch, const uint16_
                           int32_t *iters, uint8_t *converged);
 int ldpc_decode_batch_dev_f16(ldpc_ctx *ctx, int max_iters, int batch, const uint16_t *d_llr,
                               uint8_t *d_bits, int32_t *d_iters, uint8_t *d_converged, void *stream);
+/* int8 channel LLRs, what a demapper delivers: a quarter of the float32 bytes per frame over PCIe / out of HBM (the zero-copy route of
+ * page-locked buffers reads 1 byte per element).  Accepted by LDPC_I8 contexts only -- LDPC_EUNSUPPORTED on any other; the values
+ * are the decoder's integers as they are (-128 is taken as -127), llr_qscale plays no part.  Same three host routes as
+ * ldpc_decode_batch.  No counterpart in the reference. */
+int ldpc_decode_batch_i8(ldpc_ctx *ctx, int max_iters, int batch, const int8_t *llr, uint8_t *bits,
+                         int32_t *iters, uint8_t *converged);
+int ldpc_decode_batch_dev_i8(ldpc_ctx *ctx, int max_iters, int batch, const int8_t *d_llr,
+                             uint8_t *d_bits, int32_t *d_iters, uint8_t *d_converged, void *stream);
 /* PACKED result bits (r04): ceil(N/8) bytes per frame instead of N -- bit i of a frame is bit (i % 8) of byte i / 8 (LSB first; what
  * SURVEY.md section 8d's byte model counts as a frame's output) -- an eighth of the bytes back over PCIe or out to the caller's HBM
- * buffer; the decoded values are those of the unpacked entry points.  llr_f16 != 0: d_llr / llr are IEEE binary16 patterns.  The decode
+ * buffer; the decoded values are those of the unpacked entry points.  llr_f16 = 1: d_llr / llr are IEEE binary16 patterns; 2: int8 LLRs (LDPC_I8 contexts only); 0: float32.  The decode
  * kernels write one byte per bit into the context's own staging buffer (max_batch x N bytes, allocated on first use) and a second
  * kernel packs them.  The reference returns `Vector Bool` (Arraylet2.hs:271-273): one value per bit, no counterpart. */
 int ldpc_decode_batch_dev_packed(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int llr_f16, uint8_t *d_packed,
@@ -386,7 +409,7 @@ ldpc_code *ldpc_code_from_matrix(const ldpc_matrix *m);
  * C mirror of what mkLDPC returns (src/ECC/Code/LDPC/Utils.hs:35-75): ECC{name, encode, decode,
  * message_length, codeword_length}, selected by the reference's code-name grammar
  *   ldpc/<decoder>/<matrix-name>/<max-rounds>[/<x>/<y>]        (Utils.hs:82-88,100-108; rate x%y)
- * with <decoder> in {hip-tanh, hip-minsum}[-layered][-bool][-f32|-f64|-f16] or hip-tanh-cm-f64 (-bool: H taken as a plain
+ * with <decoder> in {hip-tanh, hip-minsum}[-layered][-bool][-f32|-f64|-f16|-i8] (-i8: hip-minsum-layered only) or hip-tanh-cm-f64 (-bool: H taken as a plain
  * Boolean matrix, the `Matrix Bool` decoders' input).  The reference's own decoder names are accepted as aliases, so a
  * command line written for it runs unchanged: reference, sparse -> hip-tanh-bool; min, sparsemin -> hip-minsum-bool;
  * arraylet, cuda-arraylet1, cuda-arraylet2, two-arrays, cuda-arraylet-cm -> hip-tanh; arraylet-min -> hip-minsum;

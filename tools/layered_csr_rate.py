@@ -8,11 +8,15 @@
   --lam f32|f16|both: the f32-lam instances (layered_csr_kernel<D, float>, path="fused") next to the fp16-lam ones and flood.hip f32
   layered, on identical frames and layers, at 1.5 / 2.0 / 2.5 dB: codes/1920.1280.3.303 and the DVB-S2 short-frame structure
   (tests/dvbs2_short.py), both in helper order.  The legs of one point take turns launch by launch (warm-up launch first).
+  --lam i8: the int8 fixed-point instances (LDPC_I8, layered_csr_kernel<D, signed char>, qscale 4) next to the fp16-lam ones on identical
+  frames and layers, same method, on those two codes and on the N = 64 800 code of tests/dvbs2_natural.py: rate, workgroups per CU,
+  threads, VGPRs, record bytes per sweep, and the frame / bit error rates and mean sweeps of both.  The int8 leg runs at the threads per
+  workgroup the library chooses and, where that differs from the fp16 leg's, at those too (LDPC_LAYERED_CSR_THREADS).
 Decoded-information Gbit/s = frames x k / kernel time (HIP events around the decode kernel, the median of the timed launches);
 frames: the all-zero codeword + AWGN, f32 LLRs generated on the device.
 
-usage: python tools/layered_csr_rate.py [--frames 16384] [--reps 3] [--quick] [--lam f32|f16|both [--lam-only]] [--asm FILE]
-(profiles/r07_layered_csr_f32_rate.txt: --lam both --lam-only --reps 5)"""
+usage: python tools/layered_csr_rate.py [--frames 16384] [--reps 3] [--quick] [--lam f32|f16|both|i8 [--lam-only]] [--asm FILE]
+(profiles/r07_layered_csr_f32_rate.txt: --lam both --lam-only --reps 5; profiles/r09_layered_csr_i8_rate.txt: --lam i8 --lam-only --reps 5)"""
 from __future__ import annotations
 
 import argparse
@@ -38,12 +42,12 @@ ASM = os.path.join(ROOT, "ecc_ldpc_amd", "build", "layered_csr-hip-amdgcn-amd-am
 
 def kernel_resources(dclass, lam="f16"):
     """(vgpr_count, private_segment_fixed_size) of layered_csr_kernel<dclass, lam cell type> from the device assembly the build keeps
-    (the cell type is part of the mangled name: DF16_ = _Float16, f = float)"""
+    (the cell type is part of the mangled name: DF16_ = _Float16, f = float, a = signed char)"""
     try:
         text = open(ASM).read()
     except OSError:
         return None, None
-    m = re.search(r"\.name:\s+_ZN4ldpc18layered_csr_kernelILi%dE%sEE\S*\n((?:\s+\.[a-z_]+:.*\n)+)" % (dclass, "f" if lam == "f32" else "DF16_"), text)
+    m = re.search(r"\.name:\s+_ZN4ldpc18layered_csr_kernelILi%dE%sEE\S*\n((?:\s+\.[a-z_]+:.*\n)+)" % (dclass, {"f32": "f", "i8": "a"}.get(lam, "DF16_")), text)
     if not m:
         return None, None
     f = dict(re.findall(r"\.([a-z_]+):\s+(\d+)", m.group(1)))
@@ -66,9 +70,9 @@ def rate(dec, llr, k, max_iters, reps):
 def describe(dec, lds=None):
     t, f = dec.kernel_geometry
     s = f"{dec.kernel_name} path={dec.path} threads/wg={t} frames/wg={f}"
-    m = re.search(r"layered_csr_kernel<(\d+)(, float)?>", dec.kernel_name)
+    m = re.search(r"layered_csr_kernel<(\d+)(, float|, signed char)?>", dec.kernel_name)
     if m:
-        v, sc = kernel_resources(int(m.group(1)), "f32" if m.group(2) else "f16")
+        v, sc = kernel_resources(int(m.group(1)), {", float": "f32", ", signed char": "i8"}.get(m.group(2), "f16"))
         s += f" LDS={lds} B VGPRs={v} scratch={sc} B"
     return s
 
@@ -106,6 +110,65 @@ def all_resources(out):
         for d in (8, 20, 32):
             v, sc = kernel_resources(d, lam)
             out(f"#   layered_csr_kernel<{d}{', float' if lam == 'f32' else ''}>: VGPRs={v} scratch={sc} B")
+
+
+def workgroups_per_cu(threads, lds, vgprs):
+    """resident workgroups of one CU (4 SIMDs x 512 VGPRs, 2048 threads, 160 KB of LDS), from the launch geometry and the registers"""
+    waves = threads // 64
+    by_regs = (4 * (512 // (-(-vgprs // 8) * 8))) // waves if vgprs and vgprs > 0 else None
+    return min(x for x in (160 * 1024 // lds, 2048 // threads, by_regs) if x is not None)
+
+
+def i8_comparison(a, out):
+    """int8 lam (LDPC_I8, qscale 4) / fp16 lam on identical frames and layers: rate and error rates"""
+    F, MI = a.frames, a.max_iters
+    H = formats.read_alist_mackay(open(os.path.join(ROOT, "codes", "1920.1280.3.303")).read())
+    rp3 = np.concatenate([[0], np.cumsum(H.sum(1))]).astype(np.int32)
+    ci3 = np.nonzero(H)[1].astype(np.int32)
+    rps, cis = dvbs2_short.csr()
+    rpn, cin = dvbs2_natural.csr()
+    out(f"# int8 lam (LDPC_I8, qscale 4) next to fp16 lam (--lam i8): {F} frames, {MI} sweeps at most, {a.reps} timed launches per leg "
+        "(median [min..max]), legs alternating, f32 LLRs on the device (all-zero codeword + AWGN), helper order; "
+        "FER / BER over the N codeword bits of the last launch")
+    for d in (8, 20, 32):
+        for lam in ("f16", "i8"):
+            v, sc = kernel_resources(d, lam)
+            out(f"#   layered_csr_kernel<{d}{', signed char' if lam == 'i8' else ''}>: VGPRs={v} scratch={sc} B")
+    for label, rp, ci, N, k, seed in (("1920.1280.3.303", rp3, ci3, H.shape[1], 640, 23), ("dvbs2-short", rps, cis, dvbs2_short.N, dvbs2_short.K, 29),
+                                      ("dvbs2-natural", rpn, cin, dvbs2_natural.N, dvbs2_natural.K, 17)):
+        M = len(rp) - 1
+        perm, lp = E.Code.csr_layer_order(rp, ci, N)
+        prp, pci = E.Code.permute_rows(rp, ci, perm)
+        code = E.Code.from_csr(prp, pci, N)
+        code.set_layers(lp)
+        os.environ.pop("LDPC_LAYERED_CSR_THREADS", None)
+        d16 = E.Decoder(code, "min", "f16", F, schedule="layered", path="fused")
+        d8 = E.Decoder(code, "min", "i8", F, schedule="layered")
+        legs = [("fp16 lam   ", d16, ((2 * N + 15) // 16) * 16 + 32, 24 * M), ("int8 lam   ", d8, ((N + 15) // 16) * 16 + 32, 16 * M)]
+        t16, t8 = d16.kernel_geometry[0], d8.kernel_geometry[0]
+        if t16 != t8:                                               # the int8 instance at the fp16 leg's threads per workgroup as well
+            os.environ["LDPC_LAYERED_CSR_THREADS"] = str(t16)
+            legs.append((f"int8 T={t16:<4d}", E.Decoder(code, "min", "i8", F, schedule="layered"), legs[1][2], 16 * M))
+            os.environ.pop("LDPC_LAYERED_CSR_THREADS")
+        out(f"{label} N={N} M={M} E={len(ci)} k={k} layers (helper order)={len(lp) - 1}")
+        for name, dec, lds, rb in legs:
+            m = re.search(r"layered_csr_kernel<(\d+)(, signed char)?>", dec.kernel_name)
+            v, _ = kernel_resources(int(m.group(1)), "i8" if m.group(2) else "f16")
+            out(f"  {name}: {describe(dec, lds)} workgroups/CU={workgroups_per_cu(dec.kernel_geometry[0], lds, v)} record bytes/sweep={rb}")
+        for db in (1.5, 2.0, 2.5):
+            llr = device_frames(F, N, k, db, seed)
+            res = rates_in_turn([d for _, d, _, _ in legs], llr, k, MI, a.reps)
+            for (name, _, _, _), r in zip(legs, res):
+                fer, ber = float(r["bits"].any(dim=1).float().mean()), float(r["bits"].sum(dtype=torch.int64)) / r["bits"].numel()
+                out(f"  {db:.1f} dB {name}: {r['gbps']:.2f} Gbit/s  {r['ms']:.2f} ms [{r['min']:.2f}..{r['max']:.2f}]  sweeps {r['sweeps']:.2f}  "
+                    f"converged {r['conv']:.4f}  FER {fer:.4e}  BER {ber:.4e}")
+            out(f"  {db:.1f} dB int8 / fp16 rate: {res[1]['gbps'] / res[0]['gbps']:.2f}x" +
+                (f"  (int8 at {t16} threads: {res[2]['gbps'] / res[0]['gbps']:.2f}x; its bits equal the default int8 leg's: "
+                 f"{bool(torch.equal(res[1]['bits'], res[2]['bits']))})" if len(legs) > 2 else ""))
+            del llr, res
+            torch.cuda.empty_cache()
+        for _, dec, _, _ in legs:
+            dec.close()
 
 
 def lam_comparison(a, out):
@@ -152,7 +215,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--max-iters", type=int, default=50)
     ap.add_argument("--quick", action="store_true", help="(a) at 2 dB only (profiler runs)")
-    ap.add_argument("--lam", choices=("f32", "f16", "both"), help="add the lam cell type comparison with these on-chip legs")
+    ap.add_argument("--lam", choices=("f32", "f16", "both", "i8"), help="add the lam cell type comparison with these on-chip legs (i8: int8 next to fp16)")
     ap.add_argument("--lam-only", action="store_true", help="only the --lam comparison")
     ap.add_argument("--asm", help="the device assembly of layered_csr.hip, where the build directory's copy is not at hand")
     a = ap.parse_args()
@@ -164,7 +227,7 @@ def main():
     out = lambda s: print(s, flush=True)   # noqa: E731
     if a.lam_only:
         a.lam = a.lam or "both"
-        lam_comparison(a, out)
+        (i8_comparison if a.lam == "i8" else lam_comparison)(a, out)
         E.close_all()
         return
     out(f"# layered_csr rate: {F} frames, {MI} sweeps at most, {a.reps} timed launches (median), f32 LLRs on the device")
@@ -237,7 +300,7 @@ def main():
         out(f"  flood.hip f32 layered, {label}: {r['gbps']:.2f} Gbit/s  {r['ms']:.2f} ms  sweeps {r['sweeps']:.2f}  converged {r['conv']:.4f}")
         d3.close(); f3.close()
     if a.lam:
-        lam_comparison(a, out)
+        (i8_comparison if a.lam == "i8" else lam_comparison)(a, out)
     E.close_all()
 
 
