@@ -1,5 +1,6 @@
 // api.cc -- the C ABI of include/ldpc_hip.h: graph objects, decoder replicas, host<->device plumbing.
 // No C++ exception leaves this file; every failure becomes an LDPC_E* code + thread-local message.
+#include <math.h>
 #include <stdarg.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -49,6 +50,7 @@ struct ldpc_ctx {
     const ldpc_code *code = nullptr;
     int max_batch = 0, device = 0, schedule = LDPC_SCHED_FLOODING, dtype = LDPC_F32;
     float llr_qscale = 0.f;             // LDPC_I8: the quantiser's scale (0 for every other dtype)
+    float cn_scale = 0.f, cn_offset = 0.f;  // the min-sum check-node rule the kernel computes with (0.75, 0 unless configured; 0, 0: tanh)
     hipStream_t stream = nullptr;
     ldpc::Backend *backend = nullptr;   // the context's decoder (select.cc make_backend)
     // staging of the host-pointer entry points, allocated on first use.  kSlots slots, each with its own stream
@@ -441,6 +443,8 @@ int ldpc_ctx_max_batch(const ldpc_ctx *ctx) { return ctx ? ctx->max_batch : set_
 int ldpc_ctx_device(const ldpc_ctx *ctx) { return ctx ? ctx->device : set_error(LDPC_EINVAL, "null ctx"); }
 int ldpc_ctx_schedule(const ldpc_ctx *ctx) { return ctx ? ctx->schedule : set_error(LDPC_EINVAL, "null ctx"); }
 float ldpc_ctx_llr_qscale(const ldpc_ctx *ctx) { return ctx ? ctx->llr_qscale : 0.f; }
+float ldpc_ctx_cn_scale(const ldpc_ctx *ctx) { return ctx ? ctx->cn_scale : 0.f; }
+float ldpc_ctx_cn_offset(const ldpc_ctx *ctx) { return ctx ? ctx->cn_offset : 0.f; }
 
 ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cfg) {
     if (!cfg || cfg->struct_size < offsetof(ldpc_ctx_config, schedule)) { set_error(LDPC_EINVAL, "ldpc_ctx_create_cfg: bad config"); return nullptr; }
@@ -457,15 +461,34 @@ ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cf
     float llr_qscale = dtype == LDPC_I8 && cfg->struct_size >= offsetof(ldpc_ctx_config, llr_qscale) + sizeof(float) ? cfg->llr_qscale : 0.f;
     if (!(llr_qscale >= 0.f) || llr_qscale > 3.4028234e38f) { set_error(LDPC_EINVAL, "llr_qscale %g: the quantiser's scale must be finite and > 0 (0: the default, 4)", (double)cfg->llr_qscale); return nullptr; }
     if (llr_qscale == 0.f) llr_qscale = 4.f;
-    if (sum_order != LDPC_SUM_REFERENCE && (schedule != LDPC_SCHED_FLOODING || path == LDPC_PATH_FUSED || cfg->dtype == LDPC_F16 || cfg->dtype == LDPC_F16PK)) {
+    // the check-node rule: |msg'| = max(cn_scale * min - cn_offset, 0).  0 / absent, or an explicit (0.75, 0): the 3/4 of every kernel,
+    // and the context is selected exactly as without the fields.  Anything else is a rule of its own (csrc/layered_csr.hip
+    // layered_csr_kernel<D, Ruled<LT>>); an LDPC_I8 context computes with a / 16 and b quantiser steps, and one whose integers are (12, 0) is
+    // the default context
+    float cn_scale = cfg->struct_size >= offsetof(ldpc_ctx_config, cn_scale) + sizeof(float) ? cfg->cn_scale : 0.f;
+    float cn_offset = cfg->struct_size >= offsetof(ldpc_ctx_config, cn_offset) + sizeof(float) ? cfg->cn_offset : 0.f;
+    if (!(cn_scale >= 0.f && cn_scale <= 1.f)) { set_error(LDPC_EINVAL, "cn_scale %g: the check-node rule's scale must be finite and in (0, 1] (0: the default, 3/4)", (double)cn_scale); return nullptr; }
+    if (!(cn_offset >= 0.f) || cn_offset > 3.4028234e38f) { set_error(LDPC_EINVAL, "cn_offset %g: the check-node rule's offset must be finite and >= 0", (double)cn_offset); return nullptr; }
+    if (cn_scale == 0.f) cn_scale = 0.75f;
+    ldpc::CnRule rule{cn_scale, cn_offset, 12, 0};
+    if (dtype == LDPC_I8) {
+        const float a = rintf(cn_scale * 16.f), b = rintf(cn_offset * llr_qscale);       // (ties to even; 16 alpha is exact)
+        if (a < 1.f) { set_error(LDPC_EINVAL, "cn_scale %g: LDPC_I8 computes with rint(16 cn_scale) sixteenths, which is 0", (double)cn_scale); return nullptr; }
+        if (!(b <= 127.f)) { set_error(LDPC_EINVAL, "cn_offset %g: LDPC_I8 computes with rint(cn_offset * llr_qscale) = %g quantiser steps, above 127", (double)cn_offset, (double)b); return nullptr; }
+        rule.a = (int)a; rule.b = (int)b;
+        rule.scale = (float)rule.a / 16.f; rule.offset = (float)rule.b / llr_qscale;
+    }
+    const bool has_rule = dtype == LDPC_I8 ? (rule.a != 12 || rule.b != 0) : (cn_scale != 0.75f || cn_offset != 0.f);
+    // (a context with a rule of its own is refused by make_backend, whose message names the rule, not by the parity-mode checks below)
+    if (!has_rule && sum_order != LDPC_SUM_REFERENCE && (schedule != LDPC_SCHED_FLOODING || path == LDPC_PATH_FUSED || cfg->dtype == LDPC_F16 || cfg->dtype == LDPC_F16PK)) {
         set_error(LDPC_EUNSUPPORTED, "LDPC_SUM_ARRAYLET / LDPC_SUM_SPARSE are parity modes: flooding schedule, flood path, f32 or f64");
         return nullptr;
     }
-    if (variant == LDPC_TANH_CM && (dtype != LDPC_F64 || schedule != LDPC_SCHED_FLOODING || path == LDPC_PATH_FUSED)) {
+    if (!has_rule && variant == LDPC_TANH_CM && (dtype != LDPC_F64 || schedule != LDPC_SCHED_FLOODING || path == LDPC_PATH_FUSED)) {
         set_error(LDPC_EUNSUPPORTED, "LDPC_TANH_CM (arraylet-cm numerics) is a parity mode: f64, flooding schedule, flood path (an f32 kernel is 1e-5 away from either tanh flavour)");
         return nullptr;
     }
-    if (variant == LDPC_TANH_CUDA32 && (dtype != LDPC_F32 || schedule != LDPC_SCHED_FLOODING || path == LDPC_PATH_FUSED || sum_order != LDPC_SUM_REFERENCE ||
+    if (!has_rule && variant == LDPC_TANH_CUDA32 && (dtype != LDPC_F32 || schedule != LDPC_SCHED_FLOODING || path == LDPC_PATH_FUSED || sum_order != LDPC_SUM_REFERENCE ||
                                         (code && code->max_row_deg > 32))) {
         set_error(LDPC_EUNSUPPORTED, "LDPC_TANH_CUDA32 (cuda-arraylet2 numerics) is a parity mode: f32, flooding schedule, flood path, rows up to weight 32");
         return nullptr;
@@ -488,12 +511,14 @@ ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cf
     ldpc_code_dev tabs;
     if (code_upload(code, device, &tabs) != LDPC_OK) return nullptr;
 
-    ldpc::Backend *backend = ldpc::make_backend(*code, tabs, variant, dtype, schedule, sum_order, path, max_batch, llr_qscale);
+    ldpc::Backend *backend = ldpc::make_backend(*code, tabs, variant, dtype, schedule, sum_order, path, max_batch, llr_qscale, has_rule ? &rule : nullptr);
     if (!backend) return nullptr;
     ldpc_ctx *ctx = new (std::nothrow) ldpc_ctx();
     if (!ctx) { delete backend; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
     ctx->code = code; ctx->max_batch = max_batch; ctx->device = device; ctx->schedule = schedule; ctx->backend = backend;
     ctx->dtype = dtype; ctx->llr_qscale = dtype == LDPC_I8 ? llr_qscale : 0.f;
+    const bool minsum = variant == LDPC_MINSUM;
+    ctx->cn_scale = minsum ? rule.scale : 0.f; ctx->cn_offset = minsum ? rule.offset : 0.f;
     backend->timer = &ctx->timer;
     hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {

@@ -30,11 +30,16 @@ struct Backend {
     virtual bool reads_llr_once(int max_iters) const = 0;
 };
 
+// A min-sum check-node rule other than the library's 3/4 (ldpc_ctx_config cn_scale / cn_offset, validated by api.cc):
+// |msg'| = max(scale * min - offset, 0) in float cells; a / 16 and b quantiser steps in the integers of an LDPC_I8 context
+// (a = clip(rint(16 scale), 1, 16), b = rint(offset * llr_qscale)).  Served by csrc/layered_csr.hip alone.
+struct CnRule { float scale, offset; int a, b; };
+
 // The decoder for a validated context configuration (api.cc ldpc_ctx_create_cfg), on the calling thread's current device, whose
 // graph tables are `tabs`.  nullptr + set_error when no kernel serves the configuration or creating it failed.  llr_qscale: the
-// quantiser's scale of an LDPC_I8 context.
+// quantiser's scale of an LDPC_I8 context.  rule: null for the 3/4 every kernel computes with, else the context's check-node rule.
 Backend *make_backend(const ldpc_code &c, const ldpc_code_dev &tabs, int variant, int dtype, int schedule, int sum_order, int path,
-                      int max_batch, float llr_qscale = 0.f);
+                      int max_batch, float llr_qscale = 0.f, const CnRule *rule = nullptr);
 
 // null when the row-layered schedule's layers are the block rows of the code's QC description, else why not
 const char *layers_why_not(const ldpc_code &c);

@@ -466,6 +466,20 @@ ldpc_ecc *ldpc_ecc_create_replicas(const char *codes_dir, const char *code_name,
         std::string dec = xs[1];
         int dtype = LDPC_F32;
         auto ends = [&](const char *suf) { size_t n = strlen(suf); return dec.size() > n && dec.compare(dec.size() - n, n, suf) == 0; };
+        // the check-node rule of hip-minsum-layered, after the dtype suffix: [-s<decimal>][-o<decimal>] (cn_scale, cn_offset of ldpc_ctx_config)
+        float cn_scale = 0.f, cn_offset = 0.f;
+        bool has_rule = false;
+        for (const char tag : {'o', 's'}) {
+            const size_t d = dec.rfind('-');
+            if (d == std::string::npos || d + 2 >= dec.size() || dec[d + 1] != tag) continue;
+            const std::string num = dec.substr(d + 2);
+            const size_t digits = (size_t)std::count_if(num.begin(), num.end(), [](char c) { return c >= '0' && c <= '9'; });
+            const size_t points = (size_t)std::count(num.begin(), num.end(), '.');
+            if (digits == 0 || points > 1 || digits + points != num.size()) continue;
+            (tag == 'o' ? cn_offset : cn_scale) = strtof(num.c_str(), nullptr);
+            has_rule = true;
+            dec.resize(d);
+        }
         if (ends("-f16pk")) { dtype = LDPC_F16PK; dec.resize(dec.size() - 6); }   // packed fp16 arithmetic, two frames per lane (min-sum)
         else if (ends("-f64")) { dtype = LDPC_F64; dec.resize(dec.size() - 4); }
         else if (ends("-f16")) { dtype = LDPC_F16; dec.resize(dec.size() - 4); }
@@ -475,6 +489,10 @@ ldpc_ecc *ldpc_ecc_create_replicas(const char *codes_dir, const char *code_name,
         bool as_bool = false;   // "-bool": take H as a plain Boolean matrix (the Haskell binding's `Matrix Bool` flavour, haskell/.../HIP.hs)
         if (ends("-bool")) { as_bool = true; dec.resize(dec.size() - 5); }
         if (ends("-layered")) { schedule = LDPC_SCHED_LAYERED; dec.resize(dec.size() - 8); }   // extension: row-layered schedule
+        if (has_rule && !(dec == "hip-minsum" && schedule == LDPC_SCHED_LAYERED)) {
+            set_error(LDPC_ENOTFOUND, "decoder '%s' is not provided by libldpc_hip (the rule suffix -s<scale> / -o<offset> belongs to hip-minsum-layered[-bool][-f32|-f16|-i8])", xs[1].c_str());
+            return nullptr;
+        }
         // The reference's own decoder names are accepted as aliases of the decoder that computes the same thing here, so
         // that a command line written for the reference runs unchanged (the ECC keeps the name it was asked for):
         //   reference, sparse (Reference/Orig.hs:21, Sparse.hs:39) and min, sparsemin (Min.hs:24, SparseMin.hs:42) take H
@@ -591,6 +609,7 @@ ldpc_ecc *ldpc_ecc_create_replicas(const char *codes_dir, const char *code_name,
                 ldpc_ctx_config cfg{};
                 cfg.struct_size = sizeof(cfg); cfg.device = devices ? devices[i] : -1; cfg.variant = variant; cfg.dtype = dtype; cfg.max_batch = max_batch;
                 cfg.path = (sum_order != LDPC_SUM_REFERENCE) ? LDPC_PATH_FLOOD : path; cfg.schedule = schedule; cfg.sum_order = sum_order;
+                cfg.cn_scale = cn_scale; cfg.cn_offset = cn_offset;
                 r->ctx = ldpc_ctx_create_cfg(e->code, &cfg);
                 ldpc_ecc_replica *rp = r.get();
                 e->reps.push_back(std::move(r));      // owned by the record from here on (ldpc_ecc_destroy frees it)

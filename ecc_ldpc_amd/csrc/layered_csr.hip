@@ -27,6 +27,15 @@
 // arg-min}, one dwordx2 each way: sweeps * 16 M bytes per frame.  Same column table, steps, slabs and control words.
 // Algorithmic HBM bytes per frame: sweeps * 24 M (the first sweep writes only) + the LLRs in + the bits out; the column table
 // (2 bytes per padded edge) is read by every workgroup every sweep and stays in L2.
+// THE CHECK-NODE RULE (ldpc_ctx_config cn_scale = alpha, cn_offset = beta; specification tests/layered_rule_spec.py, reproduced bit for
+// bit).  layered_csr_kernel<D, LT> computes |msg'| = 3/4 min as above and knows no other rule.  A context with another rule runs
+// layered_csr_kernel<D, Ruled<LT>>: the same kernel compiled with RULE = true, in which the ONE line of a row that turns its two minima
+// into its two message magnitudes reads the rule from the last member of the argument structure (wave-uniform: SGPRs) --
+//   float cells: n = fl(fl(alpha) * m) - fl(beta), then n < 0 ? 0 : n (two roundings -- the library is built with contraction off and
+//                the function says so again --, a compare-select so that a NaN stays a NaN and the f32 instance's veto sees what it saw);
+//   int8 cells:  n = min(max(((a m + 8) >> 4) - b, 0), 511), a = clip(rint(16 alpha), 1, 16), b = rint(beta qscale): integers only.
+// Nothing per edge: a subtract and a select (int8: a max and a min) per minimum, two minima per row.  The nine layered_csr_kernel
+// plain instances are instruction for instruction what they were before the rule existed (profiles/r10_layered_rule_default_ab.txt).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -56,6 +65,14 @@ struct CsrLayDev {
     const int32_t *step_ptr;    // [nstep + 1]: the slabs of each barrier step
 };
 
+// the check-node rule of the Ruled instances (float cells read scale / offset, int8 cells a / b)
+struct CsrRule { float scale, offset; int a, b; };
+// the kernel's second template argument: the lam cell's type -- _Float16, float, int8_t: the 3/4 --, or Ruled<that type>: the same
+// kernel with the context's rule in place of the 3/4 (a compile-time flag: the plain instances hold no trace of it)
+template <typename LT> struct Ruled {};
+template <typename X> struct CellOf { typedef X type; static constexpr bool rule = false; };
+template <typename X> struct CellOf<Ruled<X>> { typedef X type; static constexpr bool rule = true; };
+
 struct CsrLayArgs {
     const void *llr; int llr_fmt;   // [batch][N]
     float qscale;                   // (int8 lam) the quantiser's scale
@@ -63,6 +80,7 @@ struct CsrLayArgs {
     double *final_lam;              // may be null
     int batch, max_iters;
     int *work_counter;              // next frame to take = gridDim.x + atomicAdd(work_counter, 1)
+    CsrRule rule;                   // (last: the Ruled instances alone read it; every other member sits where it sat without it)
 };
 
 namespace {   // (the device helpers below are layered_lds.hip's, kept local to this file)
@@ -126,6 +144,7 @@ template <typename LT> __device__ __forceinline__ __attribute__((address_space(3
 
 // ---- int8 lam (LDPC_I8): the quantiser of tests/layered_i8_spec.py, the frame's way in and out, the row in integers
 template <> struct Cell<int8_t> { typedef uint2 vec8; typedef CsrRecI8 Rec; };      // (eight cells: the bytes of two words)
+template <typename LT> struct Cell<Ruled<LT>> : Cell<LT> {};                         // (the rule changes no cell and no record)
 
 __device__ __forceinline__ int quant_i8(float v, float qs) {
     const float r = __builtin_rintf(v * qs);           // ONE float multiply (no contraction), ties to even
@@ -173,9 +192,18 @@ __device__ __forceinline__ uint2 hard_q8(uint2 w) {
     return b;
 }
 
+// a message magnitude under the rule (alpha, beta), float cells: the product rounded, then the difference rounded -- never one fused
+// multiply-add --, then a compare-select (not a max: max(NaN, 0) is 0, and a NaN has to stay one)
+__device__ __forceinline__ float rule_mag(float m, float alpha, float beta) {
+#pragma clang fp contract(off)
+    const float p = alpha * m;
+    const float n = p - beta;
+    return n < 0.f ? 0.f : n;
+}
+
 // one check row in 32-bit integers (tests/layered_i8_spec.py row_update); same table walk, same meta word as csr_row below
-template <typename LT, int D, bool EXACT, bool FIRST>
-__device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint32_t lam0, const CsrRecI8 &in, CsrRecI8 &out, bool &odd, bool &flip) {
+template <typename LT, int D, bool EXACT, bool FIRST, bool RULE>
+__device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint32_t lam0, const CsrRecI8 &in, CsrRecI8 &out, bool &odd, bool &flip, CsrRule rule) {
     uint32_t ad[D];
     int t[D];
     int deg = EXACT ? D : 0;
@@ -208,7 +236,12 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
         }
     }
     odd |= (__builtin_popcount(hl) & 1) != 0;
-    const int n1 = (3 * m1 + 2) >> 2, n2 = (3 * m2 + 2) >> 2;      // 3/4, rounded half up
+    int n1, n2;
+    if constexpr (RULE) {   // a / 16 rounded half up, less b, in 0..511 (the cap: at a = 16 no induction keeps a magnitude below 2^9)
+        n1 = min(max(((rule.a * m1 + 8) >> 4) - rule.b, 0), 511); n2 = min(max(((rule.a * m2 + 8) >> 4) - rule.b, 0), 511);
+    } else {
+        n1 = (3 * m1 + 2) >> 2; n2 = (3 * m2 + 2) >> 2;             // 3/4, rounded half up
+    }
     // message k is negative iff (deg odd) ^ (xor of all signs of t) ^ (sign of t_k)
     const int fl = -(int)(((X >> 31) ^ (uint32_t)deg) & 1u);       // -1 or 0
     uint32_t tsig = 0, nidx = 0;
@@ -231,8 +264,8 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
 
 // one check row: layered_lds.hip lds_row with the row's weight per LANE (deg <= D; EXACT: every lane's row has weight D).  cp: this
 // lane's entry of edge 0 in the column table, edge k at cp[k T]; wd: the heaviest row of the wave (entries past it are not read).
-template <typename LT, int D, bool EXACT, bool FIRST>
-__device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint32_t lam0, const CsrRec &in, CsrRec &out, bool &odd, bool &flip) {
+template <typename LT, int D, bool EXACT, bool FIRST, bool RULE>
+__device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint32_t lam0, const CsrRec &in, CsrRec &out, bool &odd, bool &flip, CsrRule rule) {
     uint32_t ad[D];
     float l[D], t[D];
     int deg = EXACT ? D : 0;
@@ -266,7 +299,12 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
         } else t[k] = INFINITY;
     }
     odd |= par;
-    const float n1 = 0.75f * m1, n2 = 0.75f * m2;      // |(-3/4) * acc|: the one rounding of Min.hs:78
+    float n1, n2;
+    if constexpr (RULE) {
+        n1 = rule_mag(m1, rule.scale, rule.offset); n2 = rule_mag(m2, rule.scale, rule.offset);
+    } else {
+        n1 = 0.75f * m1; n2 = 0.75f * m2;               // |(-3/4) * acc|: the one rounding of Min.hs:78
+    }
     // sign bit of message k = (deg odd) ^ (xor of all sign bits of t) ^ (sign bit of t_k)   (cn_update_padded)
     const uint32_t fl = (X ^ ((deg & 1) ? 0x80000000u : 0u)) & 0x80000000u;
     uint32_t c1 = __float_as_uint(n1) ^ fl, c2 = __float_as_uint(n2) ^ fl;
@@ -288,29 +326,29 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
 }
 
 // the instance for a wave: wd = its heaviest row, uni = all its rows have that weight
-template <typename LT, int DCLASS, bool FIRST>
+template <typename LT, int DCLASS, bool FIRST, bool RULE>
 __device__ __forceinline__ void csr_row_at(const uint16_t *cp, int T, int wd, bool uni, uint32_t lam0, const typename Cell<LT>::Rec &in,
-                                           typename Cell<LT>::Rec &out, bool &odd, bool &flip) {
+                                           typename Cell<LT>::Rec &out, bool &odd, bool &flip, CsrRule rule) {
     if (uni) {
         switch (wd) {
-            case 2: csr_row<LT, 2, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 3: csr_row<LT, 3, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 4: csr_row<LT, 4, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 5: csr_row<LT, 5, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 6: csr_row<LT, 6, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 7: csr_row<LT, 7, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
-            case 8: csr_row<LT, 8, true, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return;
+            case 2: csr_row<LT, 2, true, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return;
+            case 3: csr_row<LT, 3, true, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return;
+            case 4: csr_row<LT, 4, true, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return;
+            case 5: csr_row<LT, 5, true, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return;
+            case 6: csr_row<LT, 6, true, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return;
+            case 7: csr_row<LT, 7, true, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return;
+            case 8: csr_row<LT, 8, true, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return;
             default: break;
         }
     }
     if (wd <= 0) { out = in; return; }                  // (a wave of idle lanes or empty rows)
-    if (wd <= 4) { csr_row<LT, 4, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
-    if (wd <= 8) { csr_row<LT, 8, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
+    if (wd <= 4) { csr_row<LT, 4, false, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return; }
+    if (wd <= 8) { csr_row<LT, 8, false, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return; }
     if constexpr (DCLASS >= 20) {
-        if (wd <= 12) { csr_row<LT, 12, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
-        if (wd <= 20) { csr_row<LT, 20, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip); return; }
+        if (wd <= 12) { csr_row<LT, 12, false, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return; }
+        if (wd <= 20) { csr_row<LT, 20, false, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule); return; }
     }
-    if constexpr (DCLASS >= 32) csr_row<LT, 27, false, FIRST>(cp, T, wd, lam0, in, out, odd, flip);
+    if constexpr (DCLASS >= 32) csr_row<LT, 27, false, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule);
 }
 
 }  // namespace
@@ -318,8 +356,13 @@ __device__ __forceinline__ void csr_row_at(const uint16_t *cp, int T, int wd, bo
 // block = T threads (a multiple of 64, at most csr_max_threads); grid = resident workgroups (persistent).  Rows above weight 20 keep
 // up to 27 addresses, LLRs and differences per lane: that instance is built for 512 threads (256 registers per lane, no spill).
 constexpr int csr_max_threads(int dclass) { return dclass > 20 ? 512 : 1024; }
-template <int DCLASS, typename LT = _Float16>
-__global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(CsrLayDev g, typename Cell<LT>::Rec *rec_all, CsrLayArgs A) {
+// CELL: the lam cell's type (the 3/4, A.rule is not read), or Ruled<that type> (the rule of A.rule)
+template <int DCLASS, typename CELL = _Float16>
+__global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(CsrLayDev g, typename Cell<CELL>::Rec *rec_all, CsrLayArgs A) {
+    typedef typename CellOf<CELL>::type LT;
+    constexpr bool RULE = CellOf<CELL>::rule;
+    CsrRule rule{};
+    if constexpr (RULE) rule = A.rule;
     typedef typename Cell<LT>::vec8 cell8;
     typedef typename Cell<LT>::Rec Rec;               // the row record follows the lam cell: 12 bytes (fp16, f32), 8 bytes (int8)
     constexpr bool kInt8 = std::is_same<LT, int8_t>::value;
@@ -405,10 +448,10 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
                         Rec out;
                         if (n == 1) {
                             const Rec none{};
-                            csr_row_at<LT, DCLASS, true>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, none, out, odd, flip);
+                            csr_row_at<LT, DCLASS, true, RULE>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, none, out, odd, flip, rule);
                         } else {
                             const Rec in = rec[(size_t)s * T];
-                            csr_row_at<LT, DCLASS, false>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, in, out, odd, flip);
+                            csr_row_at<LT, DCLASS, false, RULE>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, in, out, odd, flip, rule);
                         }
                         rec[(size_t)s * T] = out;
                     }
@@ -502,11 +545,13 @@ template <typename LT> using csr_kernel_t = void (*)(CsrLayDev, typename Cell<LT
 template <typename LT> csr_kernel_t<LT> kernel_for(int dclass) {
     return dclass == 8 ? layered_csr_kernel<8, LT> : dclass == 20 ? layered_csr_kernel<20, LT> : layered_csr_kernel<32, LT>;
 }
-const void *pick_kernel(int dclass, int dtype) {
+const void *pick_kernel(int dclass, int dtype, bool rule) {
+    if (rule) return dtype == LDPC_F32 ? (const void *)kernel_for<Ruled<float>>(dclass) : dtype == LDPC_I8 ? (const void *)kernel_for<Ruled<int8_t>>(dclass) : (const void *)kernel_for<Ruled<_Float16>>(dclass);
     return dtype == LDPC_F32 ? (const void *)kernel_for<float>(dclass) : dtype == LDPC_I8 ? (const void *)kernel_for<int8_t>(dclass) : (const void *)kernel_for<_Float16>(dclass);
 }
-template <typename LT> void launch(int dclass, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, void *rec, const CsrLayArgs &a) {
-    hipLaunchKernelGGL(kernel_for<LT>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a);
+template <typename LT> void launch(int dclass, bool rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, void *rec, const CsrLayArgs &a) {
+    if (rule) hipLaunchKernelGGL(kernel_for<Ruled<LT>>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a);
+    else hipLaunchKernelGGL(kernel_for<LT>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a);
 }
 
 // ------------------------------------------------------------------ host side
@@ -514,6 +559,8 @@ struct LayeredCsrState : Backend {
     int max_batch = 0, dclass = 8, grid = 0, nslab = 0;
     int dtype = LDPC_F16;       // the lam cell: fp16 (LDPC_F16), float (LDPC_F32) or int8 (LDPC_I8)
     float qscale = 0.f;         // (LDPC_I8) the quantiser's scale
+    bool has_rule = false;      // a check-node rule other than the 3/4: the Ruled instances with `rule`
+    CsrRule rule{};
     size_t lds = 0;
     CsrLayDev g{};
     uint16_t *d_cols = nullptr;
@@ -527,6 +574,7 @@ struct LayeredCsrState : Backend {
     int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                uint8_t *d_conv, double *d_final, double *d_trace) override;
     int step(hipStream_t, int, const double *, const double *, const double *, double *, double *, uint8_t *) override {
+        if (has_rule) return set_error(LDPC_EUNSUPPORTED, "no teacher-forced step with a check-node rule (cn_scale / cn_offset: the record kernels keep no per-edge messages)");
         return set_error(LDPC_EUNSUPPORTED, dtype == LDPC_I8 ? "no teacher-forced step with LDPC_I8 (fixed-point state; the record kernels keep no per-edge messages)"
                                             : dtype == LDPC_F32 ? "no teacher-forced step on the on-chip layered kernel for any H (the record kernels keep no per-edge messages)"
                                                                 : "no teacher-forced step with fp16 lam storage (the record kernels keep no per-edge messages)");
@@ -547,13 +595,14 @@ const char *layered_csr_why_not(const ldpc_code &c, int variant, int dtype) {
     return nullptr;
 }
 
-Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float qscale) {
+Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float qscale, const CnRule *cn) {
     LayeredCsrState *s = new (std::nothrow) LayeredCsrState();
     if (!s) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
     try {
         // lam stays on-chip for the whole decode in one launch (only the row records travel to HBM): reported as the on-chip path
         s->path = LDPC_PATH_FUSED;
         s->max_batch = max_batch; s->dclass = dclass_of(c.max_row_deg); s->dtype = dtype; s->qscale = qscale;
+        if (cn) { s->has_rule = true; s->rule.scale = cn->scale; s->rule.offset = cn->offset; s->rule.a = cn->a; s->rule.b = cn->b; }
         // barrier steps: maximal runs of consecutive layers that share no column
         std::vector<std::vector<int>> steps;
         {
@@ -578,7 +627,7 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
         }
         int T = (int)std::min<size_t>(csr_max_threads(s->dclass), (rmax + 63) / 64 * 64);
         s->lds = lds_bytes_for(c, dtype);
-        const void *kern = pick_kernel(s->dclass, dtype);
+        const void *kern = pick_kernel(s->dclass, dtype, s->has_rule);
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds);
         // int8 lam: a frame of N = 64 800 takes 64.8 KB of LDS, so two workgroups fit a CU -- when the registers allow it.  1024 threads
         // at more than 64 VGPRs fill the CU's register files alone; 512 threads leave room for a second workgroup, whose rows run
@@ -647,7 +696,8 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
             return nullptr;
         }
         s->g.cols = s->d_cols; s->g.slab = s->d_slab; s->g.wdeg = s->d_wdeg; s->g.step_ptr = s->d_step;
-        snprintf(s->info.name, sizeof(s->info.name), dtype == LDPC_I8 ? "ldpc::layered_csr_kernel<%d, signed char>" : dtype == LDPC_F32 ? "ldpc::layered_csr_kernel<%d, float>" : "ldpc::layered_csr_kernel<%d>", s->dclass);
+        if (s->has_rule) snprintf(s->info.name, sizeof(s->info.name), "ldpc::layered_csr_kernel<%d, ldpc::Ruled<%s>>", s->dclass, dtype == LDPC_I8 ? "signed char" : dtype == LDPC_F32 ? "float" : "_Float16");
+        else snprintf(s->info.name, sizeof(s->info.name), dtype == LDPC_I8 ? "ldpc::layered_csr_kernel<%d, signed char>" : dtype == LDPC_F32 ? "ldpc::layered_csr_kernel<%d, float>" : "ldpc::layered_csr_kernel<%d>", s->dclass);
         s->info.threads = T; s->info.frames_per_wg = 1;
         return s;
     } catch (...) { delete s; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
@@ -655,18 +705,18 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
 
 int LayeredCsrState::decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                             uint8_t *d_conv, double *d_final, double *d_trace) {
-    if (d_trace) return set_error(LDPC_EUNSUPPORTED, "layered_csr: no per-sweep trace (decode without one)");
+    if (d_trace) return set_error(LDPC_EUNSUPPORTED, has_rule ? "layered_csr: no per-sweep trace with a check-node rule (cn_scale / cn_offset; decode without one)" : "layered_csr: no per-sweep trace (decode without one)");
     CsrLayArgs a{};
     if (llr_fmt == LLR_I8 && dtype != LDPC_I8) return set_error(LDPC_EUNSUPPORTED, "int8 LLRs are taken by LDPC_I8 contexts only");
     a.llr = d_llr; a.llr_fmt = llr_fmt; a.qscale = qscale; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final;
-    a.batch = batch; a.max_iters = max_iters; a.work_counter = d_counter;
+    a.batch = batch; a.max_iters = max_iters; a.work_counter = d_counter; a.rule = rule;
     hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(int), st);
     if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
     const dim3 grid(std::min(batch, this->grid)), block(g.T);
     if (timer) timer->begin(st);
-    if (dtype == LDPC_I8) launch<int8_t>(dclass, grid, block, lds, st, g, rec, a);
-    else if (dtype == LDPC_F32) launch<float>(dclass, grid, block, lds, st, g, rec, a);
-    else launch<_Float16>(dclass, grid, block, lds, st, g, rec, a);
+    if (dtype == LDPC_I8) launch<int8_t>(dclass, has_rule, grid, block, lds, st, g, rec, a);
+    else if (dtype == LDPC_F32) launch<float>(dclass, has_rule, grid, block, lds, st, g, rec, a);
+    else launch<_Float16>(dclass, has_rule, grid, block, lds, st, g, rec, a);
     if (timer) timer->end(st);
     e = hipGetLastError();
     if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr launch: %s", hipGetErrorString(e));

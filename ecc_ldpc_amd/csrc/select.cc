@@ -22,6 +22,9 @@
 //                           layers (tools/layered_csr_rate.py --lam f32), it does not precede it
 //                         - lam as int8 (LDPC_I8, the fixed-point decoder): the only kernel of that dtype, so it is taken ahead of the
 //                           ladder, on any code (a QC code as its CSR form, with the layers it has): LDPC_PATH_AUTO or LDPC_PATH_FUSED
+//                         - a check-node rule other than the 3/4 (cn_scale / cn_offset; LDPC_F16, LDPC_F32 or LDPC_I8): only this family
+//                           has instances that read one (layered_csr_kernel<D, Ruled<LT>>), so such a context is routed here ahead of the ladder
+//                           too, a QC code as its CSR form: LDPC_PATH_AUTO or LDPC_PATH_FUSED
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -176,7 +179,16 @@ static Backend *frame_per_workgroup(const ldpc_code &c, int variant, int dtype, 
 }
 
 Backend *make_backend(const ldpc_code &c, const ldpc_code_dev &tabs, int variant, int dtype, int schedule, int sum_order, int path,
-                      int max_batch, float llr_qscale) {
+                      int max_batch, float llr_qscale, const CnRule *rule) {
+    if (rule) {     // a check-node rule other than the 3/4: layered min-sum in csrc/layered_csr.hip (layered_csr_kernel<D, Ruled<LT>>), nothing else
+        const char *why = schedule != LDPC_SCHED_LAYERED ? "the flooding schedule (its kernels compute 3/4 min, always; LDPC_SCHED_LAYERED only)"
+                          : variant != LDPC_MINSUM || sum_order != LDPC_SUM_REFERENCE ? "any rule but min-sum (the tanh rule and the parity modes have no scale or offset)"
+                          : dtype != LDPC_F16 && dtype != LDPC_F32 && dtype != LDPC_I8 ? "this dtype (LDPC_F16, LDPC_F32 or LDPC_I8 only)"
+                          : path == LDPC_PATH_FLOOD ? "LDPC_PATH_FLOOD (lam is kept on-chip: LDPC_PATH_AUTO or LDPC_PATH_FUSED)"
+                          : layered_csr_why_not(c, variant, dtype);
+        if (why) { set_error(LDPC_EUNSUPPORTED, "a check-node rule (cn_scale / cn_offset) other than 3/4 min does not serve this request: %s", why); return nullptr; }
+        return layered_csr_create(c, dtype, max_batch, dtype == LDPC_I8 ? llr_qscale : 0.f, rule);
+    }
     if (dtype == LDPC_I8) {     // the int8 fixed-point decoder: layered min-sum in csrc/layered_csr.hip, nothing else
         const char *why = schedule != LDPC_SCHED_LAYERED ? "the flooding schedule (LDPC_SCHED_LAYERED only)"
                           : variant != LDPC_MINSUM || sum_order != LDPC_SUM_REFERENCE ? "any rule but min-sum"

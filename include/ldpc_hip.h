@@ -193,17 +193,40 @@ ldpc_ctx *ldpc_ctx_create_ex(const ldpc_code *code, int variant, int dtype, int 
  * devices, its graph tables are uploaded once per device) */
 ldpc_ctx *ldpc_ctx_create_on(const ldpc_code *code, int device, int variant, int dtype, int max_batch, int path);
 /* everything above, plus what was added later, in one extensible structure: set struct_size = sizeof(ldpc_ctx_config)
- * and zero the rest before filling in; device = -1 means the calling thread's device */
+ * and zero the rest before filling in; device = -1 means the calling thread's device.
+ * THE MIN-SUM CHECK-NODE RULE (cn_scale = alpha, cn_offset = beta; extension, no reference counterpart).  Every min-sum kernel of the
+ * library computes |msg'| = 3/4 min (Min.hs:78) -- the flooding kernels, the parity modes, the quasi-cyclic on-chip and long-code
+ * layered kernels, the run-time specialised ones (ldpc_jit_*: they take a code, not a context, and build 3/4 kernels) do so ALWAYS.
+ * The on-chip layered kernel for any H (csrc/layered_csr.hip) also exists with |msg'| = max(alpha min - beta, 0): normalised
+ * (beta = 0) or offset (alpha = 1) min-sum, what hardware receivers run.  Float cells (LDPC_F16, LDPC_F32), in float32:
+ *   n = fl(fl(alpha) * m) - fl(beta) -- two roundings, no fused multiply-add --, then n < 0 ? 0 : n (a NaN stays a NaN);
+ * LDPC_I8, integers only: a = clip(rint(float32(alpha) * 16), 1, 16), b = rint(float32(beta) * float32(llr_qscale)) (ties to even),
+ *   n = min(max(((a m + 8) >> 4) - b, 0), 511); the default is a = 12, b = 0, and (12 m + 8) >> 4 == (3 m + 2) >> 2.
+ * Everything else of a row -- gathers, signs, arg-min, lam writes, stopping rule, final_lam -- is unchanged.  Specification:
+ * tests/layered_rule_spec.py, reproduced bit for bit.  A context whose two fields are 0 or absent, or an explicit (0.75, 0), is
+ * selected, named and decoded exactly as without them.  Any other rule is accepted for LDPC_MINSUM, LDPC_SCHED_LAYERED,
+ * LDPC_PATH_AUTO or LDPC_PATH_FUSED and LDPC_F16, LDPC_F32 or LDPC_I8, on any code within that kernel's limits (rows of weight
+ * 2..27, N <= 65 535, f32 lam N <= 40 952; a quasi-cyclic code is taken as its CSR form with its layers), reports LDPC_PATH_FUSED and
+ * ldpc::layered_csr_kernel<D, ldpc::Ruled<LT>>; the flooding schedule, tanh and the parity modes, LDPC_F64, LDPC_F16PK, LDPC_PATH_FLOOD,
+ * ldpc_debug_step and ldpc_decode_trace are LDPC_EUNSUPPORTED with a message that names the rule. */
 typedef struct {
     size_t struct_size;
     int device, variant, dtype, max_batch, path, schedule;
     int sum_order;   /* ldpc_sum_order; read when struct_size covers it, else LDPC_SUM_REFERENCE */
     float llr_qscale; /* LDPC_I8: the quantiser's scale (LLR units per integer step = 1 / llr_qscale); read for that dtype when struct_size
                          covers it; 0 or absent: 4.0; anything else must be finite and > 0 (LDPC_EINVAL) */
+    float cn_scale;   /* alpha; read when struct_size covers it; 0 or absent: 3/4; anything else must be finite and in (0, 1] (LDPC_EINVAL);
+                         LDPC_I8: rint(16 alpha) must not be 0 (LDPC_EINVAL) */
+    float cn_offset;  /* beta, in LLR units; read when struct_size covers it; 0 or absent: none; anything else must be finite and >= 0
+                         (LDPC_EINVAL); LDPC_I8: rint(beta * llr_qscale) must not exceed 127 (LDPC_EINVAL) */
 } ldpc_ctx_config;
 ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code, const ldpc_ctx_config *cfg);
 int ldpc_ctx_schedule(const ldpc_ctx *ctx);
 float ldpc_ctx_llr_qscale(const ldpc_ctx *ctx);   /* the quantiser's scale of an LDPC_I8 context, 0 for every other dtype */
+/* the min-sum check-node rule the context really computes with: 0.75 and 0 unless configured; the float32 values of the fields for
+ * LDPC_F16 / LDPC_F32; the quantised ones, a / 16 and b / llr_qscale, for LDPC_I8; 0 and 0 on a context of the tanh rule */
+float ldpc_ctx_cn_scale(const ldpc_ctx *ctx);
+float ldpc_ctx_cn_offset(const ldpc_ctx *ctx);
 const ldpc_code *ldpc_ctx_code(const ldpc_ctx *ctx);
 int ldpc_ctx_max_batch(const ldpc_ctx *ctx);
 int ldpc_ctx_device(const ldpc_ctx *ctx);
@@ -410,7 +433,9 @@ ldpc_code *ldpc_code_from_matrix(const ldpc_matrix *m);
  * message_length, codeword_length}, selected by the reference's code-name grammar
  *   ldpc/<decoder>/<matrix-name>/<max-rounds>[/<x>/<y>]        (Utils.hs:82-88,100-108; rate x%y)
  * with <decoder> in {hip-tanh, hip-minsum}[-layered][-bool][-f32|-f64|-f16|-i8] (-i8: hip-minsum-layered only) or hip-tanh-cm-f64 (-bool: H taken as a plain
- * Boolean matrix, the `Matrix Bool` decoders' input).  The reference's own decoder names are accepted as aliases, so a
+ * Boolean matrix, the `Matrix Bool` decoders' input).  hip-minsum-layered takes the check-node rule after the dtype suffix:
+ * [-s<decimal>][-o<decimal>] = cn_scale, cn_offset of ldpc_ctx_config, e.g. ldpc/hip-minsum-layered-i8-s1-o0.5/<matrix>/<rounds>
+ * (<decimal>: digits with at most one point; on any other decoder name the suffix makes the name unknown: LDPC_ENOTFOUND).  The reference's own decoder names are accepted as aliases, so a
  * command line written for it runs unchanged: reference, sparse -> hip-tanh-bool; min, sparsemin -> hip-minsum-bool;
  * arraylet, cuda-arraylet1, cuda-arraylet2, two-arrays, cuda-arraylet-cm -> hip-tanh; arraylet-min -> hip-minsum;
  * arraylet-cm -> hip-tanh-cm-f64 (a dtype suffix may follow: ldpc/reference-f64/...).  The ECC keeps the name it was

@@ -12,11 +12,17 @@
   frames and layers, same method, on those two codes and on the N = 64 800 code of tests/dvbs2_natural.py: rate, workgroups per CU,
   threads, VGPRs, record bytes per sweep, and the frame / bit error rates and mean sweeps of both.  The int8 leg runs at the threads per
   workgroup the library chooses and, where that differs from the fp16 leg's, at those too (LDPC_LAYERED_CSR_THREADS).
+  --cn-scale A [A ...] --cn-offset B [B ...]: the check-node rule (ldpc_ctx_config cn_scale / cn_offset), pair by pair (a single value of
+  one list goes with every value of the other; 0.75 / 0 is the default rule): fp16 and int8 lam under each rule on identical frames and
+  layers, same method, on tests/dvbs2_short.py and tests/dvbs2_natural.py at 1.5 / 2.0 / 2.5 dB -- rate, mean sweeps, converged share,
+  frame and bit error rate per leg.  Nothing else is run.
 Decoded-information Gbit/s = frames x k / kernel time (HIP events around the decode kernel, the median of the timed launches);
 frames: the all-zero codeword + AWGN, f32 LLRs generated on the device.
 
 usage: python tools/layered_csr_rate.py [--frames 16384] [--reps 3] [--quick] [--lam f32|f16|both|i8 [--lam-only]] [--asm FILE]
-(profiles/r07_layered_csr_f32_rate.txt: --lam both --lam-only --reps 5; profiles/r09_layered_csr_i8_rate.txt: --lam i8 --lam-only --reps 5)"""
+                                        [--cn-scale A [A ...]] [--cn-offset B [B ...]]
+(profiles/r07_layered_csr_f32_rate.txt: --lam both --lam-only --reps 5; profiles/r09_layered_csr_i8_rate.txt: --lam i8 --lam-only --reps 5;
+profiles/r10_layered_rule_ber.txt: --cn-scale 0.75 0.8125 0.875 1 1 --cn-offset 0 0 0 0.25 0.5 --reps 5)"""
 from __future__ import annotations
 
 import argparse
@@ -40,14 +46,15 @@ from tests import dvbs2_natural, dvbs2_short  # noqa: E402
 ASM = os.path.join(ROOT, "ecc_ldpc_amd", "build", "layered_csr-hip-amdgcn-amd-amdhsa-gfx950.s")
 
 
-def kernel_resources(dclass, lam="f16"):
+def kernel_resources(dclass, lam="f16", rule=False):
     """(vgpr_count, private_segment_fixed_size) of layered_csr_kernel<dclass, lam cell type> from the device assembly the build keeps
-    (the cell type is part of the mangled name: DF16_ = _Float16, f = float, a = signed char)"""
+    (the cell type is part of the mangled name: DF16_ = _Float16, f = float, a = signed char; rule: the Ruled<cell type> instance)"""
     try:
         text = open(ASM).read()
     except OSError:
         return None, None
-    m = re.search(r"\.name:\s+_ZN4ldpc18layered_csr_kernelILi%dE%sEE\S*\n((?:\s+\.[a-z_]+:.*\n)+)" % (dclass, {"f32": "f", "i8": "a"}.get(lam, "DF16_")), text)
+    cell = {"f32": "f", "i8": "a"}.get(lam, "DF16_")
+    m = re.search(r"\.name:\s+_ZN4ldpc18layered_csr_kernelILi%dE%sEE\S*\n((?:\s+\.[a-z_]+:.*\n)+)" % (dclass, "NS_5RuledI%sEE" % cell if rule else cell), text)
     if not m:
         return None, None
     f = dict(re.findall(r"\.([a-z_]+):\s+(\d+)", m.group(1)))
@@ -171,6 +178,53 @@ def i8_comparison(a, out):
             dec.close()
 
 
+def rule_comparison(a, out):
+    """the check-node rules of --cn-scale / --cn-offset, fp16 and int8 lam, on identical frames and layers: rate and error rates"""
+    F, MI = a.frames, a.max_iters
+    n = max(len(a.cn_scale), len(a.cn_offset))
+    rules = list(zip(a.cn_scale * (n if len(a.cn_scale) == 1 else 1), a.cn_offset * (n if len(a.cn_offset) == 1 else 1)))
+    assert len(rules) == n, "--cn-scale and --cn-offset: lists of one length, or one of them a single value"
+    out(f"# check-node rules (--cn-scale / --cn-offset), |msg'| = max(scale * min - offset, 0): {F} frames, {MI} sweeps at most, {a.reps} timed "
+        "launches per leg (median [min..max]), legs alternating, f32 LLRs on the device (all-zero codeword + AWGN), identical for every leg of "
+        "a point, helper order; int8 lam at qscale 4; FER / BER over the N codeword bits of the last launch")
+    out("# CAVEAT: the tool transmits the all-zero codeword and hard(0) = 0, so an LLR that is exactly zero -- common in int8, rare in fp16 -- "
+        "is decided in that codeword's favour.  On a toy (720, 360) code, mirroring the same noise onto random codewords raised the int8 bit "
+        "error count at 2 dB by 10 % at qscale 4 (23 % at qscale 2) and barely moved the frame error count: the BERs below flatter int8 "
+        "relative to fp16 by about that much.")
+    for d in (8, 20, 32):
+        for lam in ("f16", "i8"):
+            (v0, s0), (v1, s1) = kernel_resources(d, lam), kernel_resources(d, lam, rule=True)
+            cell = "signed char" if lam == "i8" else "_Float16"
+            out(f"#   layered_csr_kernel<{d}, {cell}>: VGPRs={v0} scratch={s0} B;  <{d}, Ruled<{cell}>>: VGPRs={v1} scratch={s1} B")
+    rps, cis = dvbs2_short.csr()
+    rpn, cin = dvbs2_natural.csr()
+    for label, rp, ci, N, k, seed in (("dvbs2-short", rps, cis, dvbs2_short.N, dvbs2_short.K, 29), ("dvbs2-natural", rpn, cin, dvbs2_natural.N, dvbs2_natural.K, 17)):
+        perm, lp = E.Code.csr_layer_order(rp, ci, N)
+        prp, pci = E.Code.permute_rows(rp, ci, perm)
+        code = E.Code.from_csr(prp, pci, N)
+        code.set_layers(lp)
+        legs = []
+        for lam in ("f16", "i8"):
+            for sc, off in rules:
+                default = (sc, off) == (0.75, 0.0)
+                dec = E.Decoder(code, "min", lam, F, schedule="layered", path="fused", cn_scale=None if default else sc, cn_offset=None if default else off)
+                legs.append((f"{'fp16' if lam == 'f16' else 'int8'} ({dec.cn_scale:g}, {dec.cn_offset:g})", dec))
+        out(f"{label} N={N} M={len(rp) - 1} E={len(ci)} k={k} layers (helper order)={len(lp) - 1}")
+        for name, dec in legs:
+            out(f"  {name:<22s}: {dec.kernel_name} threads/wg={dec.kernel_geometry[0]}")
+        for db in (1.5, 2.0, 2.5):
+            llr = device_frames(F, N, k, db, seed)
+            res = rates_in_turn([d for _, d in legs], llr, k, MI, a.reps)
+            for (name, _), r in zip(legs, res):
+                fer, ber = float(r["bits"].any(dim=1).float().mean()), float(r["bits"].sum(dtype=torch.int64)) / r["bits"].numel()
+                out(f"  {db:.1f} dB {name:<22s}: {r['gbps']:.2f} Gbit/s  {r['ms']:.2f} ms [{r['min']:.2f}..{r['max']:.2f}]  sweeps {r['sweeps']:.2f}  "
+                    f"converged {r['conv']:.4f}  FER {fer:.4e}  BER {ber:.4e}")
+            del llr, res
+            torch.cuda.empty_cache()
+        for _, dec in legs:
+            dec.close()
+
+
 def lam_comparison(a, out):
     """f32 lam / fp16 lam / flood.hip f32 layered on identical frames and layers"""
     F, MI = a.frames, a.max_iters
@@ -217,6 +271,8 @@ def main():
     ap.add_argument("--quick", action="store_true", help="(a) at 2 dB only (profiler runs)")
     ap.add_argument("--lam", choices=("f32", "f16", "both", "i8"), help="add the lam cell type comparison with these on-chip legs (i8: int8 next to fp16)")
     ap.add_argument("--lam-only", action="store_true", help="only the --lam comparison")
+    ap.add_argument("--cn-scale", type=float, nargs="+", help="check-node rule comparison: the scales (0.75: the default)")
+    ap.add_argument("--cn-offset", type=float, nargs="+", help="check-node rule comparison: the offsets, in LLR units (0: none)")
     ap.add_argument("--asm", help="the device assembly of layered_csr.hip, where the build directory's copy is not at hand")
     a = ap.parse_args()
     if a.asm:
@@ -225,6 +281,11 @@ def main():
     E.init(0)
     F, MI = a.frames, a.max_iters
     out = lambda s: print(s, flush=True)   # noqa: E731
+    if a.cn_scale or a.cn_offset:
+        a.cn_scale, a.cn_offset = a.cn_scale or [0.75], a.cn_offset or [0.0]
+        rule_comparison(a, out)
+        E.close_all()
+        return
     if a.lam_only:
         a.lam = a.lam or "both"
         (i8_comparison if a.lam == "i8" else lam_comparison)(a, out)
