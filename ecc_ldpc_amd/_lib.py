@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "ldpc_ctx_set_timing", "ldpc_ctx_kernel_time", "ldpc_ctx_kernel_name", "ldpc_ctx_kernel_geometry", "ldpc_jit_cache_dir", "ldpc_jit_source", "ldpc_jit_prepare", "ldpc_jit_source_for", "ldpc_jit_prepare_for",
     "ldpc_sim_create", "ldpc_sim_destroy", "ldpc_sim_generate", "ldpc_sim_tally", "ldpc_sim_encode_host",
     "ldpc_sim_create_qc_on", "ldpc_sim_encoder", "ldpc_sim_encode_batch", "ldpc_matrix_qc_words", "ldpc_matrix_rank",
+    "ldpc_csr_triangular_order", "ldpc_sim_create_sparse_on",
     "ldpc_matrix_load", "ldpc_matrix_load_mackay", "ldpc_matrix_destroy", "ldpc_matrix_info", "ldpc_matrix_dense",
     "ldpc_matrix_qc_offsets", "ldpc_code_from_matrix",
     "ldpc_ecc_create", "ldpc_ecc_destroy", "ldpc_ecc_name", "ldpc_ecc_message_length", "ldpc_ecc_codeword_length",
@@ -217,6 +218,9 @@ def lib():
     L.ldpc_sim_create_qc_on.restype = vp
     L.ldpc_sim_create_qc_on.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_int]
     L.ldpc_sim_encoder.argtypes = [vp]
+    L.ldpc_csr_triangular_order.argtypes = [C.c_int, C.c_int, i32p, i32p, i32p]
+    L.ldpc_sim_create_sparse_on.restype = vp
+    L.ldpc_sim_create_sparse_on.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.ldpc_sim_encode_batch.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp, vp]
     L.ldpc_matrix_qc_words.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.ldpc_matrix_rank.argtypes = [vp]
@@ -366,6 +370,18 @@ class Code:
         if n < 0:
             raise LdpcError(lib().ldpc_last_error_code(), last_error())
         return perm[:M], lp[: n + 1]
+
+    @staticmethod
+    def csr_triangular_order(row_ptr, col_idx, N):
+        """-> order: order[j] = the row of H whose largest column is K + j, K = N - M (ldpc_csr_triangular_order): in that order the
+        parity part of H is unit lower-triangular and H encodes by back-substitution (Sim(..., from_H=True)).  LdpcError -5, naming
+        the offending row or rows, for an H that does not qualify"""
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        ci = np.ascontiguousarray(col_idx, dtype=np.int32)
+        M = max(len(rp) - 1, 0)
+        order = np.zeros(max(M, 1), np.int32)
+        check(lib().ldpc_csr_triangular_order(M, int(N), ptr(rp, C.c_int32), ptr(ci, C.c_int32), ptr(order, C.c_int32)))
+        return order[:M]
 
     @staticmethod
     def permute_rows(row_ptr, col_idx, perm):
@@ -699,16 +715,21 @@ class Matrix:
 class Sim:
     """Device-side frame source + error tally (ldpc_sim)."""
 
-    def __init__(self, code: Code, k, n_tx, G=None, max_batch=64, _handle=None, device=None, G_qc=None):
+    def __init__(self, code: Code, k, n_tx, G=None, max_batch=64, _handle=None, device=None, G_qc=None, from_H=False):
         """G: dense generator [k][p] bytes; G_qc = (sz, words [block_rows][block_cols][sz/32] uint32): the quasi-cyclic form
-        (Matrix.qc_words), encoded by rotate-and-xor like Fast/Encoder.hs; neither: all-zero codewords"""
+        (Matrix.qc_words), encoded by rotate-and-xor like Fast/Encoder.hs; from_H: the code's own parity-check matrix, by
+        back-substitution (k must be N - M; Code.csr_triangular_order says whether H qualifies); none of them: all-zero codewords"""
         self.code, self.k, self.n_tx = code, int(k), int(n_tx)
         self._owned = _handle is None
         if _handle is None:
             dev = int(device) if device is not None else lib().ldpc_current_device()
             if dev < 0:
                 raise LdpcError(ENODEVICE, "ldpc_init() has not succeeded")
-            if G_qc is not None:
+            if from_H:
+                if G is not None or G_qc is not None or int(k) != code.N - code.M:
+                    raise LdpcError(EINVAL, f"Sim(from_H=True): no generator is taken and k must be N - M = {code.N - code.M}")
+                _handle = lib().ldpc_sim_create_sparse_on(code._h, dev, int(n_tx), int(max_batch))
+            elif G_qc is not None:
                 sz, words = G_qc
                 words = np.ascontiguousarray(words, np.uint32)
                 _handle = lib().ldpc_sim_create_qc_on(code._h, dev, int(k), int(n_tx), int(sz), words.shape[0], words.shape[1], ptr(words, C.c_uint32), int(max_batch))
@@ -729,7 +750,7 @@ class Sim:
 
     @property
     def encoder(self):
-        return {0: "none", 1: "dense", 2: "qc"}[lib().ldpc_sim_encoder(self._h)]
+        return {0: "none", 1: "dense", 2: "qc", 3: "sparse"}[lib().ldpc_sim_encoder(self._h)]
 
     def encode_batch(self, seed, first_frame, batch, d_codewords_ptr, d_msg_ptr=None, stream=None):
         """the encoder alone: codewords [batch][n_tx] bytes on the device"""

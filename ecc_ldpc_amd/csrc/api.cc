@@ -349,6 +349,36 @@ int ldpc_csr_layer_order(int M, int N, const int32_t *row_ptr, const int32_t *co
     } catch (...) { return set_error(LDPC_ENOMEM, "out of host memory"); }
 }
 
+// the rule of the encoder from H (include/ldpc_hip.h): order[j] = the row whose largest column is K + j
+static int triangular_order(const char *who, int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int32_t *order) {
+    const int K = N - M;
+    if (K <= 0) return set_error(LDPC_EUNSUPPORTED, "%s: M = %d >= N = %d leaves no message columns", who, M, N);
+    try {
+        std::vector<int32_t> owner((size_t)M, -1);
+        for (int m = 0; m < M; m++) {
+            if (row_ptr[m + 1] == row_ptr[m]) return set_error(LDPC_EUNSUPPORTED, "%s: row %d is empty", who, m);
+            const int last = col_idx[row_ptr[m + 1] - 1];   // (columns ascend inside a row)
+            if (last < K) return set_error(LDPC_EUNSUPPORTED, "%s: row %d ends in column %d, inside the message part (K = %d)", who, m, last, K);
+            if (owner[last - K] >= 0) return set_error(LDPC_EUNSUPPORTED, "%s: rows %d and %d end in column %d", who, owner[last - K], m, last);
+            owner[last - K] = m;
+        }
+        memcpy(order, owner.data(), sizeof(int32_t) * (size_t)M);   // M rows into M places without a collision: a bijection
+    } catch (...) { return set_error(LDPC_ENOMEM, "out of host memory"); }
+    return LDPC_OK;
+}
+
+int ldpc_csr_triangular_order(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int32_t *order) {
+    if (M <= 0 || N <= 0 || !row_ptr || !col_idx || !order || row_ptr[0] != 0)
+        return set_error(LDPC_EINVAL, "ldpc_csr_triangular_order: bad arguments (M=%d N=%d)", M, N);
+    for (int m = 0; m < M; m++) {
+        if (row_ptr[m + 1] < row_ptr[m]) return set_error(LDPC_EINVAL, "ldpc_csr_triangular_order: row_ptr decreases at row %d", m);
+        for (int q = row_ptr[m]; q < row_ptr[m + 1]; q++)
+            if (col_idx[q] < 0 || col_idx[q] >= N || (q > row_ptr[m] && col_idx[q] <= col_idx[q - 1]))
+                return set_error(LDPC_EINVAL, "ldpc_csr_triangular_order: row %d: columns not strictly ascending inside [0, %d)", m, N);
+    }
+    return triangular_order("ldpc_csr_triangular_order", M, N, row_ptr, col_idx, order);
+}
+
 int ldpc_code_set_layers(ldpc_code *code, int n_layers, const int32_t *layer_ptr) {
     if (!code || n_layers <= 0 || !layer_ptr) return set_error(LDPC_EINVAL, "ldpc_code_set_layers: bad arguments");
     {
@@ -967,6 +997,13 @@ struct ldpc_sim {
     std::vector<uint32_t> gt_host;     // dense generator, packed columns (host encode)
     std::vector<uint32_t> qc_host;     // quasi-cyclic generator: [brows][bcols][W] first-row words
     uint32_t *d_gt = nullptr, *d_msgw = nullptr, *d_rot = nullptr, *d_parw = nullptr;
+    // encoder from H: row order[j] of H without its last column K + j, as [sp_ptr[j], sp_ptr[j+1]) of sp_col (host encode);
+    // the device tables of sim_sparse.hip in one allocation, and its bit-sliced scratch
+    bool sparse = false;
+    ldpc::SimSparse sp{};
+    std::vector<int32_t> sp_ptr, sp_col;
+    int32_t *d_sp = nullptr;
+    uint32_t *d_x = nullptr;
 };
 extern "C" {
 
@@ -977,6 +1014,8 @@ void ldpc_sim_destroy(ldpc_sim *sim) {
     hipFree(sim->d_rot);
     hipFree(sim->d_parw);
     hipFree(sim->d_msgw);
+    hipFree(sim->d_sp);
+    hipFree(sim->d_x);
     delete sim;
 }
 
@@ -1065,8 +1104,66 @@ ldpc_sim *ldpc_sim_create_qc_on(const ldpc_code *code, int device, int k, int n_
     return s;
 }
 
+// The encoder from H (csrc/sim_sparse.hip).  Scratch: 4 N min(ceil(max_batch / 32), kSparseFwCap) bytes; a larger batch goes
+// through it in chunks of 32 * kSparseFwCap frames.
+static const int kSparseFwCap = 512;
+ldpc_sim *ldpc_sim_create_sparse_on(const ldpc_code *code, int device, int n_tx, int max_batch) {
+    if (!code || max_batch <= 0) {
+        set_error(LDPC_EINVAL, "ldpc_sim_create_sparse: bad arguments (n_tx=%d max_batch=%d N=%d)", n_tx, max_batch, code ? code->N : -1);
+        return nullptr;
+    }
+    const int M = code->M, N = code->N, K = N - M;
+    std::vector<int32_t> order((size_t)M);
+    if (triangular_order("ldpc_sim_create_sparse", M, N, code->row_ptr.data(), code->col_idx.data(), order.data()) != LDPC_OK) return nullptr;
+    if (n_tx < K || n_tx > N) {
+        set_error(LDPC_EINVAL, "ldpc_sim_create_sparse: bad arguments (k=%d n_tx=%d N=%d)", K, n_tx, N);
+        return nullptr;
+    }
+    ldpc_sim *s = sim_new(code, device, K, n_tx, max_batch);
+    if (!s) return nullptr;
+    s->p = M;
+    s->sparse = true;
+    s->dev.pwords = (M + 31) / 32;
+    // device tables, one allocation: a_ptr [M+1] | b_meta [M+1] | a_col [na] | b_far [nb]
+    std::vector<int32_t> a_ptr((size_t)M + 1, 0), b_meta((size_t)M + 1, 0), a_col, b_far;
+    s->sp_ptr.assign((size_t)M + 1, 0);
+    for (int j = 0; j < M; j++) {
+        const int m = order[j];
+        bool prev = false;
+        for (int q = code->row_ptr[m]; q < code->row_ptr[m + 1] - 1; q++) {   // (the last column is K + j itself)
+            const int c = code->col_idx[q];
+            s->sp_col.push_back(c);
+            if (c < K) a_col.push_back(c);
+            else if (c == K + j - 1) prev = true;
+            else b_far.push_back(c - K);
+        }
+        s->sp_ptr[j + 1] = (int32_t)s->sp_col.size();
+        a_ptr[j + 1] = (int32_t)a_col.size();
+        b_meta[j] |= prev ? (int32_t)0x80000000u : 0;
+        b_meta[j + 1] = (int32_t)b_far.size();
+    }
+    std::vector<int32_t> tab;
+    tab.insert(tab.end(), a_ptr.begin(), a_ptr.end());
+    tab.insert(tab.end(), b_meta.begin(), b_meta.end());
+    tab.insert(tab.end(), a_col.begin(), a_col.end());
+    tab.insert(tab.end(), b_far.begin(), b_far.end());
+    const int fw_cap = std::min((max_batch + 31) / 32, kSparseFwCap);
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_sp, tab.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(s->d_sp, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_x, (size_t)N * fw_cap * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_parw, (size_t)max_batch * s->dev.pwords * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_msgw, (size_t)max_batch * s->dev.kwords * 4);
+    if (e != hipSuccess) { set_error(LDPC_EHIP, "ldpc_sim_create_sparse: %s", hipGetErrorString(e)); ldpc_sim_destroy(s); return nullptr; }
+    s->sp.M = M; s->sp.K = K; s->sp.x = s->d_x; s->sp.fw_cap = fw_cap;
+    s->sp.a_ptr = s->d_sp; s->sp.b_meta = s->d_sp + (M + 1);
+    s->sp.a_col = s->d_sp + 2 * (size_t)(M + 1); s->sp.b_far = s->sp.a_col + a_col.size();
+    return s;
+}
+
 int ldpc_sim_encoder(const ldpc_sim *sim) {
     if (!sim) return set_error(LDPC_EINVAL, "null sim");
+    if (sim->sparse) return LDPC_ENCODER_SPARSE;
     return sim->dev.qc_rot ? LDPC_ENCODER_QC : (sim->dev.gt ? LDPC_ENCODER_DENSE : LDPC_ENCODER_NONE);
 }
 
@@ -1075,7 +1172,7 @@ static int sim_generate_any(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, 
     if (!sim || !d_out || batch < 0 || batch > sim->max_batch) return set_error(LDPC_EINVAL, "ldpc_sim_generate: bad arguments");
     if (batch == 0) return LDPC_OK;
     HIPCHK(hipSetDevice(sim->device));
-    return ldpc::sim_generate(sim->dev, sim->d_msgw, sim->d_parw, (hipStream_t)stream, seed, first_frame, batch, ebn0_db, d_out, out_fmt, d_msg);
+    return ldpc::sim_generate(sim->dev, sim->sparse ? &sim->sp : nullptr, sim->d_msgw, sim->d_parw, (hipStream_t)stream, seed, first_frame, batch, ebn0_db, d_out, out_fmt, d_msg);
 }
 
 int ldpc_sim_generate(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, float *d_llr,
@@ -1104,6 +1201,18 @@ int ldpc_sim_encode_host(const ldpc_sim *sim, const uint8_t *msg, uint8_t *parit
     const int kw = sim->dev.kwords;
     std::vector<uint32_t> mw((size_t)kw, 0u);
     for (int r = 0; r < sim->dev.k; r++) if (msg[r]) mw[r >> 5] |= 1u << (r & 31);
+    if (sim->sparse) {   // back-substitution: parity bit j = XOR of the other columns of row order[j], all of them earlier
+        const int K = sim->dev.k;
+        for (int j = 0; j < sim->p; j++) {
+            unsigned b = 0;
+            for (int q = sim->sp_ptr[j]; q < sim->sp_ptr[j + 1]; q++) {
+                const int c = sim->sp_col[q];
+                b ^= c < K ? (unsigned)(msg[c] != 0) : (unsigned)parity[c - K];
+            }
+            parity[j] = (uint8_t)b;
+        }
+        return LDPC_OK;
+    }
     if (!sim->qc_host.empty()) {
         // Fast/Encoder.hs:42-63 word by word: res[col] = XOR_row mulWord(v'[row], g[row][col]), mulWord = rotate-and-xor
         // over the set bits of the message word

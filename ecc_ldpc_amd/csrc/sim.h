@@ -10,10 +10,21 @@ struct SimDev {
     //   qc_rot[cg][r][b][16]: for column group cg (16/W block columns, W = sz/32 words per circulant), block row r and bit
     //   rotation b = 0..31, the W words of rotl(g[r][c], b) for each column c of the group (missing columns: zero)
     const uint32_t *qc_rot;
-    int qc_w, qc_brows, qc_bcols, qc_ncg, pwords;   // pwords = qc_bcols * qc_w: packed parity words per frame
+    int qc_w, qc_brows, qc_bcols, qc_ncg, pwords;   // pwords: packed parity words per frame (qc_bcols * qc_w; encoder from H: ceil(M / 32))
 };
-// parw: scratch for the packed parity words [batch][pwords] (quasi-cyclic encoder only)
-int sim_generate(const SimDev &s, uint32_t *msgw, uint32_t *parw, hipStream_t st, uint64_t seed, uint64_t first_frame, int batch,
+// encoder from H (sim_sparse.hip): the rows of H in the order of ldpc_csr_triangular_order, row j ending in column K + j
+struct SimSparse {
+    int M, K;
+    const int32_t *a_ptr, *a_col;    // [M + 1], [..]: the message columns (< K) of row j
+    const int32_t *b_meta, *b_far;   // [M + 1], [..]: bit 31 of b_meta[j] = the row holds parity bit j - 1; its low bits = where the row's
+                                     // other earlier parity bits (as parity indices < j - 1) start in b_far
+    uint32_t *x;                     // bit-sliced scratch [N][fw_cap]: word fw of position n = that bit of frames 32 fw .. 32 fw + 31
+    int fw_cap;                      // frame words the scratch holds per position
+};
+int sim_sparse_parity(const SimSparse &sp, const uint32_t *msgw, int kwords, uint32_t *parw, int pwords, hipStream_t st, int batch);
+// parw: scratch for the packed parity words [batch][pwords] (quasi-cyclic encoder, encoder from H; null otherwise); sp: null
+// unless the source encodes from H
+int sim_generate(const SimDev &s, const SimSparse *sp, uint32_t *msgw, uint32_t *parw, hipStream_t st, uint64_t seed, uint64_t first_frame, int batch,
                  double ebn0_db, void *d_out, int out_fmt, uint8_t *d_msg);   // out_fmt: 0 = f32 LLRs [batch][N], 1 = fp16 LLRs, 2 = codeword bytes [batch][n_tx]
 int sim_tally(const SimDev &s, const uint32_t *msgw, hipStream_t st, int batch, const uint8_t *d_bits, const int32_t *d_iters,
               unsigned long long *d_tally);

@@ -4,7 +4,10 @@
 // message generation, encode, BPSK + AWGN, BER statistics; its source is not vendored, SURVEY.md
 // section 8c), so the channel model is this build's own stated one:
 //   message bits uniform; systematic encode  codeword = msg ++ take (c_length - k) (msg * G)
-//   (src/ECC/Code/LDPC/Utils.hs:61, Reference/Orig.hs:25-26, Fast/Encoder.hs:26-63);
+//   (src/ECC/Code/LDPC/Utils.hs:61, Reference/Orig.hs:25-26, Fast/Encoder.hs:26-63) -- G dense (sim_frame_kernel), quasi-cyclic
+//   (sim_parity_qc_kernel), or none at all: all-zero codewords, or, for an H whose parity part is triangular after a row
+//   permutation, the same codeword by back-substitution FROM H (sim_sparse.hip; no counterpart in the reference).  The last two
+//   hand sim_frame_kernel packed parity words parw[frame][pwords];
 //   BPSK bit b -> 2b-1 (LLR > 0 <=> bit 1, `hard x = x > 0`); noise N(0, sigma^2),
 //   sigma^2 = 1/(2 R 10^(EbN0/10)), R = k/n_tx; LLR = 2y/sigma^2; punctured tail LLR = 0
 //   (Utils.hs:55 `unpuncture`).
@@ -159,7 +162,7 @@ __global__ __launch_bounds__(256) void sim_frame_kernel(SimDev s, const uint32_t
     // parity bits of the group: bit j = <msg, column j of G> over GF(2); a group that lies inside the parity part
     // on a 4-aligned column reads its four columns with one 16-byte load per message word
     uint32_t pacc[4] = {0u, 0u, 0u, 0u};
-    if (s.gt && !s.qc_rot && n0 + 3 >= s.k && n0 < s.n_tx) {
+    if (s.gt && !parw && n0 + 3 >= s.k && n0 < s.n_tx) {
         const int j0 = n0 - s.k;
         if (j0 >= 0 && (j0 & 3) == 0) {
             const uint4 *col = reinterpret_cast<const uint4 *>(s.gt + j0);
@@ -190,8 +193,8 @@ __global__ __launch_bounds__(256) void sim_frame_kernel(SimDev s, const uint32_t
             if (n < s.k) {
                 bit = (mw[n >> 5] >> (n & 31)) & 1u;
                 if (msg_bytes) msg_bytes[(size_t)f * s.k + n] = (uint8_t)bit;
-            } else if (s.qc_rot) {
-                const int j = n - s.k;         // packed by sim_parity_qc_kernel
+            } else if (parw) {
+                const int j = n - s.k;         // packed by sim_parity_qc_kernel or sim_sparse_parity
                 bit = (parw[(size_t)f * s.pwords + (j >> 5)] >> (j & 31)) & 1u;
             } else {
                 bit = __popc(pacc[i]) & 1u;   // (no generator: pacc = 0, the all-zero codeword)
@@ -248,13 +251,16 @@ __global__ __launch_bounds__(256) void sim_tally_kernel(SimDev s, const uint32_t
     }
 }
 
-int sim_generate(const SimDev &s, uint32_t *msgw, uint32_t *parw, hipStream_t st, uint64_t seed, uint64_t first_frame, int batch,
+int sim_generate(const SimDev &s, const SimSparse *sp, uint32_t *msgw, uint32_t *parw, hipStream_t st, uint64_t seed, uint64_t first_frame, int batch,
                  double ebn0_db, void *d_out, int out_fmt, uint8_t *d_msg) {
     const double R = (double)s.k / (double)s.n_tx;
     const double sigma2 = 1.0 / (2.0 * R * pow(10.0, ebn0_db / 10.0));
     size_t nw = (size_t)batch * s.kwords;
-    hipLaunchKernelGGL(sim_msg_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, msgw, s.kwords, s.k, seed, first_frame, batch, (s.gt || s.qc_rot) ? 0 : 1);
-    if (s.qc_rot) {
+    hipLaunchKernelGGL(sim_msg_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, msgw, s.kwords, s.k, seed, first_frame, batch, (s.gt || parw) ? 0 : 1);
+    if (sp) {
+        const int rc = sim_sparse_parity(*sp, msgw, s.kwords, parw, s.pwords, st, batch);
+        if (rc != LDPC_OK) return rc;
+    } else if (s.qc_rot) {
         const dim3 pg((batch + 63) / 64, s.qc_ncg);
 #define LDPC_QC_PARITY(W_) hipLaunchKernelGGL((sim_parity_qc_kernel<W_>), pg, dim3(64 * kQcRowSplit), 0, st, s.qc_rot, s.qc_brows, s.qc_bcols, msgw, parw, s.kwords, s.pwords, batch)
         switch (s.qc_w) {

@@ -181,6 +181,15 @@ int ldpc_qc_layer_order(int block_rows, int block_cols, const int32_t *offsets, 
  * Pure host code, needs no GPU.  Returns n (the number of layers), < 0 on error.  No counterpart in the reference. */
 int ldpc_csr_layer_order(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int max_rows,
                          int32_t *perm /* M */, int32_t *layer_ptr /* M + 1 */);
+/* Does H (M x N as CSR, 0 < M < N, K = N - M) encode by back-substitution?  Columns 0..K-1 carry the message, K..N-1 the parity
+ * bits; last(i) = the largest column of row i.  H QUALIFIES iff no row is empty, last(i) >= K for every row, and i -> last(i) - K
+ * is a bijection onto 0..M-1.  Then order[j] = the row with last = K + j: taken in that order the rows have a unit lower-triangular
+ * parity part, and  c[0..K) = msg;  c[K+j] = XOR of c[col] over the OTHER columns of row order[j]  (all < K + j)  for j = 0..M-1
+ * is the codeword of msg -- the one any systematic generator of the code gives, whatever order the rows are stored in.  DVB-S2-shaped
+ * accumulator codes qualify (they are defined this way and ship no generator), codes/moon.7.13 does.  Pure host code, needs no
+ * GPU.  LDPC_OK; LDPC_EINVAL for a malformed CSR; LDPC_EUNSUPPORTED when the rule fails, the message naming the first offending
+ * row (for two rows that end in one column: both rows and the column).  No counterpart in the reference. */
+int ldpc_csr_triangular_order(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int32_t *order /* M */);
 int ldpc_code_layers(const ldpc_code *code, int *n_layers, int32_t *layer_ptr /* may be NULL; n_layers+1 entries */);
 
 /* ---- decoder replica -------------------------------------------------------------------------
@@ -378,8 +387,15 @@ void ldpc_sim_destroy(ldpc_sim *sim);
  * (block_rows * block_cols * sz words), never the expanded k x p matrix. */
 ldpc_sim *ldpc_sim_create_qc_on(const ldpc_code *code, int device, int k, int n_tx, int sz, int block_rows, int block_cols,
                                 const uint32_t *circ, int max_batch);
-enum { LDPC_ENCODER_NONE = 0, LDPC_ENCODER_DENSE = 1, LDPC_ENCODER_QC = 2 };
-int ldpc_sim_encoder(const ldpc_sim *sim);    /* which of the three this frame source encodes with */
+/* The encoder FROM H, for codes that have no generator file because they are defined by their parity-check matrix: k = N - M,
+ * k <= n_tx <= N, positions n_tx..N-1 punctured as above; a quasi-cyclic code is taken as its CSR form.  H must qualify under
+ * the rule of ldpc_csr_triangular_order: NULL with LDPC_EUNSUPPORTED and that function's reason otherwise.  Messages are random
+ * (the same (seed, frame) -> message words as every other source); the parity bits are solved on the device, 32 frames to a
+ * machine word.  Device scratch besides the packed messages and parity bits: at most 4 * N * ceil(max_batch / 32) bytes, and
+ * never more than 2048 * N (larger batches pass through it in chunks of 16 384 frames). */
+ldpc_sim *ldpc_sim_create_sparse_on(const ldpc_code *code, int device, int n_tx, int max_batch);
+enum { LDPC_ENCODER_NONE = 0, LDPC_ENCODER_DENSE = 1, LDPC_ENCODER_QC = 2, LDPC_ENCODER_SPARSE = 3 };
+int ldpc_sim_encoder(const ldpc_sim *sim);    /* which of these this frame source encodes with */
 /* the encoder alone: codewords [batch][n_tx] bytes (device) of the same messages ldpc_sim_generate would use (message
  * bits of frame f depend on (seed, f) only); d_msg [batch][k] may be NULL.  Enqueued on `stream`. */
 int ldpc_sim_encode_batch(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, uint8_t *d_codewords, uint8_t *d_msg, void *stream);
@@ -398,7 +414,7 @@ int ldpc_sim_generate_f16(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, in
  * for the frames of the last ldpc_sim_generate call; d_iters may be NULL. */
 int ldpc_sim_tally(ldpc_sim *sim, int batch, const uint8_t *d_bits, const int32_t *d_iters,
                    uint64_t *d_tally, void *stream);
-/* host-side encode of one message with the same rule (parity only, p bytes) -- used by tests */
+/* host-side encode of one message with the same rule (parity only, p bytes; M bytes for the encoder from H) -- used by tests */
 int ldpc_sim_encode_host(const ldpc_sim *sim, const uint8_t *msg, uint8_t *parity);
 
 /* ---- matrix ingest --------------------------------------------------------------------------------

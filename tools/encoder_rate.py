@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
-"""tools/encoder_rate.py [frames] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63, sim.hip
-sim_parity_qc_kernel) against the dense packed GF(2) mat-vec of the expanded generator (Orig.hs:25-26), on the shipped AR4JA
+"""tools/encoder_rate.py [frames] [--sparse-only] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
+sim.hip sim_parity_qc_kernel) against the dense packed GF(2) mat-vec of the expanded generator (Orig.hs:25-26), on the shipped AR4JA
 codes: the encoder alone (ldpc_sim_encode_batch: messages + parity -> codeword bytes) and the whole frame source
-(ldpc_sim_generate: + BPSK, AWGN, LLRs).  HIP events on the launch stream, median of 7."""
+(ldpc_sim_generate: + BPSK, AWGN, LLRs).  HIP events on the launch stream, median of 7.
+Then the encoder FROM H (sim_sparse.hip) on the DVB-S2 structures of tests/dvbs2_short.py and tests/dvbs2_natural.py, in helper order:
+the encoder alone, the whole generate, the encoder-less generate (all-zero codewords) of the same shape, and -- the yardstick: a BER
+loop is at most doubled while generate costs no more than it -- the fp16-lam layered decode of that batch at 2 dB.  One warm-up,
+median of 5.  --sparse-only: only that part."""
 import os
 import sys
 
@@ -22,12 +26,62 @@ def timed(fn, stream, reps=7):
     return sorted(ts)[len(ts) // 2]
 
 
+def sparse_leg(B, dev, st):
+    import statistics
+    from tests import dvbs2_natural, dvbs2_short
+    for label, mod in (("dvbs2-short", dvbs2_short), ("dvbs2-natural", dvbs2_natural)):
+        rp, ci = mod.csr()
+        N, K = mod.N, mod.K
+        perm, lp = E.Code.csr_layer_order(rp, ci, N)
+        code = E.Code.from_csr(*E.Code.permute_rows(rp, ci, perm), N)
+        code.set_layers(lp)
+        sim = E.Sim(code, K, N, from_H=True, max_batch=B)
+        plain = E.Sim(code, K, N, max_batch=B)
+        assert (sim.encoder, plain.encoder) == ("sparse", "none")
+        cw = torch.empty((B, N), dtype=torch.uint8, device=dev)
+        llr = torch.empty((B, N), dtype=torch.float32, device=dev)
+        t_enc = timed(lambda: sim.encode_batch(1, 0, B, cw.data_ptr(), None, st.cuda_stream), st, 5)
+        t_zero = timed(lambda: plain.generate(1, 0, B, 2.0, llr.data_ptr(), None, st.cuda_stream), st, 5)
+        t_gen = timed(lambda: sim.generate(1, 0, B, 2.0, llr.data_ptr(), None, st.cuda_stream), st, 5)
+        ones = float(cw[:, K:].float().mean())
+        del cw
+        dec = E.Decoder(code, "min", "f16", B, schedule="layered")
+        bits = torch.empty((B, N), dtype=torch.uint8, device=dev)
+        its = torch.empty(B, dtype=torch.int32, device=dev)
+        conv = torch.empty(B, dtype=torch.uint8, device=dev)
+        dec.set_timing(True)
+        ts = []
+        for r in range(6):                                           # the first launch warms up
+            dec.decode_batch_dev(llr.data_ptr(), bits.data_ptr(), B, 50, its.data_ptr(), conv.data_ptr(), st.cuda_stream)
+            dec.synchronize(); torch.cuda.synchronize()
+            n, ms = dec.kernel_time()
+            if r:
+                ts.append(ms / max(n, 1))
+        t_dec = statistics.median(ts)
+        tally = torch.zeros(4, dtype=torch.int64, device=dev)
+        sim.tally(B, bits.data_ptr(), its.data_ptr(), tally.data_ptr(), st.cuda_stream)
+        torch.cuda.synchronize()
+        fr, fe, be, _ = tally.cpu().tolist()
+        print(f"{label:14s} N={N} K={K} sparse encoder (from H, helper order): {B} frames  encode_batch {t_enc:7.3f} ms = {B * K / t_enc / 1e6:8.1f} Gbit/s info"
+              f" | generate {t_gen:7.3f} ms | encoder-less generate {t_zero:7.3f} ms | parity ones {ones:.4f}", flush=True)
+        print(f"{'':14s} fp16-lam layered decode of that batch at 2 dB ({dec.kernel_name}): {t_dec:7.3f} ms, sweeps {float(its.float().mean()):.2f}, "
+              f"converged {float(conv.float().mean()):.4f}, tally {fr} frames {fe} frame errors {be} message-bit errors"
+              f" | generate / decode = {t_gen / t_dec:.3f} ({'within' if t_gen <= t_dec else 'MISSES'} the bar generate <= decode)", flush=True)
+        dec.close(); sim.close(); plain.close(); code.close()
+        del llr, bits
+        torch.cuda.empty_cache()
+
+
 def main():
-    B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    B = int(args[0]) if args else 65536
     E.init(0)
     dev = torch.device("cuda", 0)
     st = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(st)
+    if "--sparse-only" in sys.argv:
+        sparse_leg(B, dev, st)
+        return
     for name in ("ldpc/hip-minsum/jpl.1024.4.5/50/4/5", "ldpc/hip-minsum/jpl.4096.4.5/50/4/5"):
         rows = {}
         for enc in ("qc", "dense"):
@@ -49,6 +103,7 @@ def main():
             del cw, llr
         assert (rows["qc"][2] == rows["dense"][2]).all(), "encoders disagree"
         print(f"{'':42s} codewords identical; qc/dense time: encode {rows['qc'][0] / rows['dense'][0]:.2f}, generate {rows['qc'][1] / rows['dense'][1]:.2f}")
+    sparse_leg(B, dev, st)
 
 
 if __name__ == "__main__":

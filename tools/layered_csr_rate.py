@@ -16,13 +16,19 @@
   one list goes with every value of the other; 0.75 / 0 is the default rule): fp16 and int8 lam under each rule on identical frames and
   layers, same method, on tests/dvbs2_short.py and tests/dvbs2_natural.py at 1.5 / 2.0 / 2.5 dB -- rate, mean sweeps, converged share,
   frame and bit error rate per leg.  Nothing else is run.
+  --codewords zero|random (the --lam i8 and --cn-scale / --cn-offset comparisons, which report error rates): zero, the default, transmits
+  the all-zero codeword; random takes the codewords of random messages from the frame source's encoder from H (Sim(from_H=True).encode_batch)
+  on the structures that qualify (the DVB-S2 ones; 1920.1280.3.303 does not and stays all-zero) and mirrors the SAME torch noise onto
+  them, y = (2c - 1) + noise with the same generator and seed: a zero leg and a random leg differ only in the codeword.  FER / BER are
+  counted against the transmitted codeword.
 Decoded-information Gbit/s = frames x k / kernel time (HIP events around the decode kernel, the median of the timed launches);
-frames: the all-zero codeword + AWGN, f32 LLRs generated on the device.
+frames: the all-zero codeword + AWGN unless --codewords random, f32 LLRs generated on the device.
 
 usage: python tools/layered_csr_rate.py [--frames 16384] [--reps 3] [--quick] [--lam f32|f16|both|i8 [--lam-only]] [--asm FILE]
-                                        [--cn-scale A [A ...]] [--cn-offset B [B ...]]
+                                        [--cn-scale A [A ...]] [--cn-offset B [B ...]] [--codewords zero|random] [--codes NAME [NAME ...]]
 (profiles/r07_layered_csr_f32_rate.txt: --lam both --lam-only --reps 5; profiles/r09_layered_csr_i8_rate.txt: --lam i8 --lam-only --reps 5;
-profiles/r10_layered_rule_ber.txt: --cn-scale 0.75 0.8125 0.875 1 1 --cn-offset 0 0 0 0.25 0.5 --reps 5)"""
+profiles/r10_layered_rule_ber.txt: --cn-scale 0.75 0.8125 0.875 1 1 --cn-offset 0 0 0 0.25 0.5 --reps 5;
+profiles/r11_sparse_encoder.txt: --lam i8 --lam-only --codes dvbs2-short --codewords zero, then the same with --codewords random)"""
 from __future__ import annotations
 
 import argparse
@@ -61,13 +67,40 @@ def kernel_resources(dclass, lam="f16", rule=False):
     return int(f.get("vgpr_count", -1)), int(f.get("private_segment_fixed_size", -1))
 
 
-def device_frames(F, N, k, db, seed):
+def device_frames(F, N, k, db, seed, cw=None):
+    """cw: the transmitted codewords [F][N] (uint8, device), None = all-zero; the noise depends on (seed, shape) only"""
     s2 = channel.sigma2(db, k, N)
     g = torch.Generator(device="cuda").manual_seed(seed)
-    y = -1.0 + torch.randn((F, N), generator=g, device="cuda", dtype=torch.float32) * float(np.sqrt(s2))
+    x = -1.0 if cw is None else 2.0 * cw.to(torch.float32) - 1.0
+    y = x + torch.randn((F, N), generator=g, device="cuda", dtype=torch.float32) * float(np.sqrt(s2))
     llr = (2.0 / s2) * y
     torch.cuda.synchronize()     # the decoders run on their own stream: the frames are complete before the first launch reads them
     return llr
+
+
+def transmitted(a, code, rp, ci, N, k, F, out):
+    """--codewords random: the codewords [F][N] of random messages, from the encoder from H of `code` (rows rp, ci); None (all-zero)
+    for --codewords zero and for an H that encoder refuses"""
+    if a.codewords != "random":
+        return None
+    try:
+        E.Code.csr_triangular_order(rp, ci, N)
+        sim = E.Sim(code, k, N, from_H=True, max_batch=F)
+    except E.LdpcError as e:
+        out(f"  all-zero codewords here: {e}")
+        return None
+    cw = torch.empty((F, N), dtype=torch.uint8, device="cuda")
+    sim.encode_batch(0xC0DE, 0, F, cw.data_ptr(), None, None)
+    torch.cuda.synchronize()
+    sim.close()
+    out(f"  codewords of random messages (encoder from H), parity ones {float(cw[:, k:].float().mean()):.4f}")
+    return cw
+
+
+def error_rates(bits, cw):
+    """-> (FER, BER) over the N codeword bits against the transmitted codeword"""
+    err = bits if cw is None else bits ^ cw
+    return float(err.any(dim=1).float().mean()), float(err.sum(dtype=torch.int64)) / err.numel()
 
 
 def rate(dec, llr, k, max_iters, reps):
@@ -135,7 +168,7 @@ def i8_comparison(a, out):
     rps, cis = dvbs2_short.csr()
     rpn, cin = dvbs2_natural.csr()
     out(f"# int8 lam (LDPC_I8, qscale 4) next to fp16 lam (--lam i8): {F} frames, {MI} sweeps at most, {a.reps} timed launches per leg "
-        "(median [min..max]), legs alternating, f32 LLRs on the device (all-zero codeword + AWGN), helper order; "
+        f"(median [min..max]), legs alternating, f32 LLRs on the device ({'all-zero codeword' if a.codewords == 'zero' else 'codewords of random messages'} + AWGN), helper order; "
         "FER / BER over the N codeword bits of the last launch")
     for d in (8, 20, 32):
         for lam in ("f16", "i8"):
@@ -143,6 +176,8 @@ def i8_comparison(a, out):
             out(f"#   layered_csr_kernel<{d}{', signed char' if lam == 'i8' else ''}>: VGPRs={v} scratch={sc} B")
     for label, rp, ci, N, k, seed in (("1920.1280.3.303", rp3, ci3, H.shape[1], 640, 23), ("dvbs2-short", rps, cis, dvbs2_short.N, dvbs2_short.K, 29),
                                       ("dvbs2-natural", rpn, cin, dvbs2_natural.N, dvbs2_natural.K, 17)):
+        if a.codes and label not in a.codes:
+            continue
         M = len(rp) - 1
         perm, lp = E.Code.csr_layer_order(rp, ci, N)
         prp, pci = E.Code.permute_rows(rp, ci, perm)
@@ -162,11 +197,12 @@ def i8_comparison(a, out):
             m = re.search(r"layered_csr_kernel<(\d+)(, signed char)?>", dec.kernel_name)
             v, _ = kernel_resources(int(m.group(1)), "i8" if m.group(2) else "f16")
             out(f"  {name}: {describe(dec, lds)} workgroups/CU={workgroups_per_cu(dec.kernel_geometry[0], lds, v)} record bytes/sweep={rb}")
+        cw = transmitted(a, code, prp, pci, N, k, F, out)
         for db in (1.5, 2.0, 2.5):
-            llr = device_frames(F, N, k, db, seed)
+            llr = device_frames(F, N, k, db, seed, cw)
             res = rates_in_turn([d for _, d, _, _ in legs], llr, k, MI, a.reps)
             for (name, _, _, _), r in zip(legs, res):
-                fer, ber = float(r["bits"].any(dim=1).float().mean()), float(r["bits"].sum(dtype=torch.int64)) / r["bits"].numel()
+                fer, ber = error_rates(r["bits"], cw)
                 out(f"  {db:.1f} dB {name}: {r['gbps']:.2f} Gbit/s  {r['ms']:.2f} ms [{r['min']:.2f}..{r['max']:.2f}]  sweeps {r['sweeps']:.2f}  "
                     f"converged {r['conv']:.4f}  FER {fer:.4e}  BER {ber:.4e}")
             out(f"  {db:.1f} dB int8 / fp16 rate: {res[1]['gbps'] / res[0]['gbps']:.2f}x" +
@@ -185,12 +221,13 @@ def rule_comparison(a, out):
     rules = list(zip(a.cn_scale * (n if len(a.cn_scale) == 1 else 1), a.cn_offset * (n if len(a.cn_offset) == 1 else 1)))
     assert len(rules) == n, "--cn-scale and --cn-offset: lists of one length, or one of them a single value"
     out(f"# check-node rules (--cn-scale / --cn-offset), |msg'| = max(scale * min - offset, 0): {F} frames, {MI} sweeps at most, {a.reps} timed "
-        "launches per leg (median [min..max]), legs alternating, f32 LLRs on the device (all-zero codeword + AWGN), identical for every leg of "
+        f"launches per leg (median [min..max]), legs alternating, f32 LLRs on the device ({'all-zero codeword' if a.codewords == 'zero' else 'codewords of random messages'} + AWGN), identical for every leg of "
         "a point, helper order; int8 lam at qscale 4; FER / BER over the N codeword bits of the last launch")
-    out("# CAVEAT: the tool transmits the all-zero codeword and hard(0) = 0, so an LLR that is exactly zero -- common in int8, rare in fp16 -- "
-        "is decided in that codeword's favour.  On a toy (720, 360) code, mirroring the same noise onto random codewords raised the int8 bit "
-        "error count at 2 dB by 10 % at qscale 4 (23 % at qscale 2) and barely moved the frame error count: the BERs below flatter int8 "
-        "relative to fp16 by about that much.")
+    if a.codewords == "zero":
+            out("# CAVEAT: the tool transmits the all-zero codeword and hard(0) = 0, so an LLR that is exactly zero -- common in int8, rare in fp16 -- "
+            "is decided in that codeword's favour.  On a toy (720, 360) code, mirroring the same noise onto random codewords raised the int8 bit "
+            "error count at 2 dB by 10 % at qscale 4 (23 % at qscale 2) and barely moved the frame error count: the BERs below flatter int8 "
+            "relative to fp16 by about that much (--codewords random removes the bias).")
     for d in (8, 20, 32):
         for lam in ("f16", "i8"):
             (v0, s0), (v1, s1) = kernel_resources(d, lam), kernel_resources(d, lam, rule=True)
@@ -199,6 +236,8 @@ def rule_comparison(a, out):
     rps, cis = dvbs2_short.csr()
     rpn, cin = dvbs2_natural.csr()
     for label, rp, ci, N, k, seed in (("dvbs2-short", rps, cis, dvbs2_short.N, dvbs2_short.K, 29), ("dvbs2-natural", rpn, cin, dvbs2_natural.N, dvbs2_natural.K, 17)):
+        if a.codes and label not in a.codes:
+            continue
         perm, lp = E.Code.csr_layer_order(rp, ci, N)
         prp, pci = E.Code.permute_rows(rp, ci, perm)
         code = E.Code.from_csr(prp, pci, N)
@@ -212,11 +251,12 @@ def rule_comparison(a, out):
         out(f"{label} N={N} M={len(rp) - 1} E={len(ci)} k={k} layers (helper order)={len(lp) - 1}")
         for name, dec in legs:
             out(f"  {name:<22s}: {dec.kernel_name} threads/wg={dec.kernel_geometry[0]}")
+        cw = transmitted(a, code, prp, pci, N, k, F, out)
         for db in (1.5, 2.0, 2.5):
-            llr = device_frames(F, N, k, db, seed)
+            llr = device_frames(F, N, k, db, seed, cw)
             res = rates_in_turn([d for _, d in legs], llr, k, MI, a.reps)
             for (name, _), r in zip(legs, res):
-                fer, ber = float(r["bits"].any(dim=1).float().mean()), float(r["bits"].sum(dtype=torch.int64)) / r["bits"].numel()
+                fer, ber = error_rates(r["bits"], cw)
                 out(f"  {db:.1f} dB {name:<22s}: {r['gbps']:.2f} Gbit/s  {r['ms']:.2f} ms [{r['min']:.2f}..{r['max']:.2f}]  sweeps {r['sweeps']:.2f}  "
                     f"converged {r['conv']:.4f}  FER {fer:.4e}  BER {ber:.4e}")
             del llr, res
@@ -273,6 +313,10 @@ def main():
     ap.add_argument("--lam-only", action="store_true", help="only the --lam comparison")
     ap.add_argument("--cn-scale", type=float, nargs="+", help="check-node rule comparison: the scales (0.75: the default)")
     ap.add_argument("--cn-offset", type=float, nargs="+", help="check-node rule comparison: the offsets, in LLR units (0: none)")
+    ap.add_argument("--codewords", choices=("zero", "random"), default="zero",
+                    help="what the error-rate comparisons transmit: the all-zero codeword, or codewords of random messages (encoder from H) under the same noise")
+    ap.add_argument("--codes", nargs="+", choices=("1920.1280.3.303", "dvbs2-short", "dvbs2-natural"),
+                    help="the --lam i8 and check-node rule comparisons on these codes only (default: all of theirs)")
     ap.add_argument("--asm", help="the device assembly of layered_csr.hip, where the build directory's copy is not at hand")
     a = ap.parse_args()
     if a.asm:
