@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "ldpc_sim_create", "ldpc_sim_destroy", "ldpc_sim_generate", "ldpc_sim_tally", "ldpc_sim_encode_host",
     "ldpc_sim_create_qc_on", "ldpc_sim_encoder", "ldpc_sim_encode_batch", "ldpc_matrix_qc_words", "ldpc_matrix_rank",
     "ldpc_csr_triangular_order", "ldpc_sim_create_sparse_on",
+    "ldpc_csr_systematic_form", "ldpc_sim_create_systematic_on", "ldpc_sim_message_length", "ldpc_sim_positions",
     "ldpc_matrix_load", "ldpc_matrix_load_mackay", "ldpc_matrix_destroy", "ldpc_matrix_info", "ldpc_matrix_dense",
     "ldpc_matrix_qc_offsets", "ldpc_code_from_matrix",
     "ldpc_ecc_create", "ldpc_ecc_destroy", "ldpc_ecc_name", "ldpc_ecc_message_length", "ldpc_ecc_codeword_length",
@@ -221,6 +222,11 @@ def lib():
     L.ldpc_csr_triangular_order.argtypes = [C.c_int, C.c_int, i32p, i32p, i32p]
     L.ldpc_sim_create_sparse_on.restype = vp
     L.ldpc_sim_create_sparse_on.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.ldpc_csr_systematic_form.argtypes = [C.c_int, C.c_int, i32p, i32p, i32p, i32p, ip, ip, u8p]
+    L.ldpc_sim_create_systematic_on.restype = vp
+    L.ldpc_sim_create_systematic_on.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.ldpc_sim_message_length.argtypes = [vp]
+    L.ldpc_sim_positions.argtypes = [vp, i32p, i32p]
     L.ldpc_sim_encode_batch.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp, vp]
     L.ldpc_matrix_qc_words.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.ldpc_matrix_rank.argtypes = [vp]
@@ -382,6 +388,24 @@ class Code:
         order = np.zeros(max(M, 1), np.int32)
         check(lib().ldpc_csr_triangular_order(M, int(N), ptr(rp, C.c_int32), ptr(ci, C.c_int32), ptr(order, C.c_int32)))
         return order[:M]
+
+    @staticmethod
+    def csr_systematic_form(row_ptr, col_idx, N, want_P=True):
+        """-> (msg_pos [K], par_pos [rank], P [K][rank] uint8 or None): the systematic form of any H (ldpc_csr_systematic_form) --
+        columns taken from the right, a column is a parity position iff it is independent of the parity positions after it;
+        c[msg_pos[i]] = m[i], c[par_pos[j]] = XOR_i m[i] P[i][j].  LdpcError -5 for M * N > 2^28 and for a code without message bits"""
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        ci = np.ascontiguousarray(col_idx, dtype=np.int32)
+        M, N = max(len(rp) - 1, 0), int(N)
+        mp, pp = np.zeros(max(N, 1), np.int32), np.zeros(max(N, 1), np.int32)
+        K, r = C.c_int(0), C.c_int(0)
+        check(lib().ldpc_csr_systematic_form(M, N, ptr(rp, C.c_int32), ptr(ci, C.c_int32), ptr(mp, C.c_int32), ptr(pp, C.c_int32), C.byref(K), C.byref(r), None))
+        P = None
+        if want_P:
+            P = np.zeros((K.value, r.value), np.uint8)
+            check(lib().ldpc_csr_systematic_form(M, N, ptr(rp, C.c_int32), ptr(ci, C.c_int32), ptr(mp, C.c_int32), ptr(pp, C.c_int32), C.byref(K), C.byref(r),
+                                                 ptr(P, C.c_uint8)))
+        return mp[:K.value].copy(), pp[:r.value].copy(), P
 
     @staticmethod
     def permute_rows(row_ptr, col_idx, perm):
@@ -715,17 +739,23 @@ class Matrix:
 class Sim:
     """Device-side frame source + error tally (ldpc_sim)."""
 
-    def __init__(self, code: Code, k, n_tx, G=None, max_batch=64, _handle=None, device=None, G_qc=None, from_H=False):
+    def __init__(self, code: Code, k, n_tx, G=None, max_batch=64, _handle=None, device=None, G_qc=None, from_H=False, systematic=False):
         """G: dense generator [k][p] bytes; G_qc = (sz, words [block_rows][block_cols][sz/32] uint32): the quasi-cyclic form
         (Matrix.qc_words), encoded by rotate-and-xor like Fast/Encoder.hs; from_H: the code's own parity-check matrix, by
-        back-substitution (k must be N - M; Code.csr_triangular_order says whether H qualifies); none of them: all-zero codewords"""
-        self.code, self.k, self.n_tx = code, int(k), int(n_tx)
+        back-substitution (k must be N - M; Code.csr_triangular_order says whether H qualifies); systematic: ANY parity-check matrix,
+        through Code.csr_systematic_form (k must be None: the library fills it, K = N - rank H; see positions()); none of them:
+        all-zero codewords"""
+        self.code, self.k, self.n_tx = code, (None if k is None else int(k)), int(n_tx)
         self._owned = _handle is None
         if _handle is None:
             dev = int(device) if device is not None else lib().ldpc_current_device()
             if dev < 0:
                 raise LdpcError(ENODEVICE, "ldpc_init() has not succeeded")
-            if from_H:
+            if systematic:
+                if G is not None or G_qc is not None or from_H or k is not None:
+                    raise LdpcError(EINVAL, "Sim(systematic=True): no generator is taken and k must be None (it is N - rank H)")
+                _handle = lib().ldpc_sim_create_systematic_on(code._h, dev, int(n_tx), int(max_batch))
+            elif from_H:
                 if G is not None or G_qc is not None or int(k) != code.N - code.M:
                     raise LdpcError(EINVAL, f"Sim(from_H=True): no generator is taken and k must be N - M = {code.N - code.M}")
                 _handle = lib().ldpc_sim_create_sparse_on(code._h, dev, int(n_tx), int(max_batch))
@@ -742,7 +772,17 @@ class Sim:
         if not _handle:
             raise LdpcError(lib().ldpc_last_error_code(), last_error())
         self._h = _handle
+        if self.k is None:
+            self.k = int(lib().ldpc_sim_message_length(_handle))
         _register(self)
+
+    def positions(self):
+        """-> (msg_pos [k], par_pos): where the message and the parity bits sit in the codeword (ldpc_sim_positions)"""
+        mp, pp = np.zeros(max(self.k, 1), np.int32), np.zeros(max(self.code.N, 1), np.int32)
+        n = lib().ldpc_sim_positions(self._h, ptr(mp, C.c_int32), ptr(pp, C.c_int32))
+        if n < 0:
+            raise LdpcError(n, last_error())
+        return mp[:self.k].copy(), pp[:n].copy()
 
     def generate(self, seed, first_frame, batch, ebn0_db, d_llr_ptr, d_msg_ptr=None, stream=None, llr_f16=False):
         fn = lib().ldpc_sim_generate_f16 if llr_f16 else lib().ldpc_sim_generate
@@ -750,7 +790,7 @@ class Sim:
 
     @property
     def encoder(self):
-        return {0: "none", 1: "dense", 2: "qc", 3: "sparse"}[lib().ldpc_sim_encoder(self._h)]
+        return {0: "none", 1: "dense", 2: "qc", 3: "sparse", 4: "systematic"}[lib().ldpc_sim_encoder(self._h)]
 
     def encode_batch(self, seed, first_frame, batch, d_codewords_ptr, d_msg_ptr=None, stream=None):
         """the encoder alone: codewords [batch][n_tx] bytes on the device"""

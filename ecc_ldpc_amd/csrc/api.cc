@@ -14,6 +14,7 @@
 #include "backend.h"
 #include "jit.h"
 #include "sim.h"
+#include "systematic.h"
 
 namespace ldpc {
 static thread_local char g_err[512] = "";
@@ -377,6 +378,21 @@ int ldpc_csr_triangular_order(int M, int N, const int32_t *row_ptr, const int32_
                 return set_error(LDPC_EINVAL, "ldpc_csr_triangular_order: row %d: columns not strictly ascending inside [0, %d)", m, N);
     }
     return triangular_order("ldpc_csr_triangular_order", M, N, row_ptr, col_idx, order);
+}
+
+int ldpc_csr_systematic_form(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int32_t *msg_pos, int32_t *par_pos, int *K, int *rank, uint8_t *P) {
+    if (!msg_pos || !par_pos || !K || !rank) return set_error(LDPC_EINVAL, "ldpc_csr_systematic_form: bad arguments (M=%d N=%d)", M, N);
+    ldpc::SystematicForm sf;
+    std::string err;
+    const int rc = ldpc::systematic_form("ldpc_csr_systematic_form", M, N, row_ptr, col_idx, sf, err);
+    if (rc != LDPC_OK) return set_error(rc, "%s", err.c_str());
+    *K = sf.K; *rank = sf.rank;
+    memcpy(msg_pos, sf.msg_pos.data(), sizeof(int32_t) * (size_t)sf.K);
+    memcpy(par_pos, sf.par_pos.data(), sizeof(int32_t) * (size_t)sf.rank);
+    if (P)
+        for (int i = 0; i < sf.K; i++)
+            for (int j = 0; j < sf.rank; j++) P[(size_t)i * sf.rank + j] = (uint8_t)((sf.P[(size_t)i * sf.pw64 + (j >> 6)] >> (j & 63)) & 1ull);
+    return LDPC_OK;
 }
 
 int ldpc_code_set_layers(ldpc_code *code, int n_layers, const int32_t *layer_ptr) {
@@ -1004,6 +1020,13 @@ struct ldpc_sim {
     std::vector<int32_t> sp_ptr, sp_col;
     int32_t *d_sp = nullptr;
     uint32_t *d_x = nullptr;
+    // systematic form of any H (csrc/systematic.cc, csrc/sim_systematic.hip): positions and P (host encode), the window generator and
+    // msg_pos on the device; d_parw holds the packed codewords
+    bool systematic = false;
+    ldpc::SimSys sy{};
+    ldpc::SystematicForm sf;
+    uint32_t *d_gwin = nullptr;
+    int32_t *d_msg_pos = nullptr;
 };
 extern "C" {
 
@@ -1016,6 +1039,8 @@ void ldpc_sim_destroy(ldpc_sim *sim) {
     hipFree(sim->d_msgw);
     hipFree(sim->d_sp);
     hipFree(sim->d_x);
+    hipFree(sim->d_gwin);
+    hipFree(sim->d_msg_pos);
     delete sim;
 }
 
@@ -1161,8 +1186,70 @@ ldpc_sim *ldpc_sim_create_sparse_on(const ldpc_code *code, int device, int n_tx,
     return s;
 }
 
+// The encoder from any H (csrc/sim_systematic.hip).  Device memory: the window generator, 64 * 32 * ceil(K / 32) bytes per 512
+// codeword positions from the first parity position on, and 4 * ceil(N / 32) * max_batch bytes of packed codewords.
+ldpc_sim *ldpc_sim_create_systematic_on(const ldpc_code *code, int device, int n_tx, int max_batch) {
+    if (!code || max_batch <= 0) {
+        set_error(LDPC_EINVAL, "ldpc_sim_create_systematic: bad arguments (n_tx=%d max_batch=%d N=%d)", n_tx, max_batch, code ? code->N : -1);
+        return nullptr;
+    }
+    const int N = code->N;
+    ldpc::SystematicForm sf;
+    std::string err;
+    const int rc = ldpc::systematic_form("ldpc_sim_create_systematic", code->M, N, code->row_ptr.data(), code->col_idx.data(), sf, err);
+    if (rc != LDPC_OK) { set_error(rc, "%s", err.c_str()); return nullptr; }
+    const int K = sf.K, r = sf.rank;
+    if (n_tx < K || n_tx > N) {
+        set_error(LDPC_EINVAL, "ldpc_sim_create_systematic: bad arguments (k=%d n_tx=%d N=%d)", K, n_tx, N);
+        return nullptr;
+    }
+    ldpc_sim *s = sim_new(code, device, K, n_tx, max_batch);
+    if (!s) return nullptr;
+    s->p = r;
+    s->systematic = true;
+    const int kwords = s->dev.kwords, cww = (N + 31) / 32;
+    const int w0 = std::min(r ? sf.par_pos[0] / 32 : cww - 1, cww - 1), ncg = (cww - w0 + 15) / 16;
+    s->dev.pwords = cww;
+    // gwin[cg][i][c]: word w0 + 16 cg + c of the codeword of the unit message e_i
+    std::vector<uint32_t> gwin((size_t)ncg * kwords * 32 * 16, 0u);
+    auto put = [&](int i, int n) {
+        const int w = n / 32 - w0;
+        if (w >= 0) gwin[((size_t)(w / 16) * kwords * 32 + i) * 16 + w % 16] |= 1u << (n & 31);
+    };
+    for (int i = 0; i < K; i++) {
+        put(i, sf.msg_pos[i]);
+        for (int j = 0; j < r; j++)
+            if ((sf.P[(size_t)i * sf.pw64 + (j >> 6)] >> (j & 63)) & 1ull) put(i, sf.par_pos[j]);
+    }
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_gwin, gwin.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(s->d_gwin, gwin.data(), gwin.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_msg_pos, (size_t)K * 4);
+    if (e == hipSuccess) e = hipMemcpy(s->d_msg_pos, sf.msg_pos.data(), (size_t)K * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_parw, (size_t)max_batch * cww * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_msgw, (size_t)max_batch * kwords * 4);
+    if (e != hipSuccess) { set_error(LDPC_EHIP, "ldpc_sim_create_systematic: %s", hipGetErrorString(e)); ldpc_sim_destroy(s); return nullptr; }
+    s->sy.gwin = s->d_gwin; s->sy.ncg = ncg; s->sy.w0 = w0; s->sy.cww = cww; s->sy.msg_pos = s->d_msg_pos;
+    s->sf = std::move(sf);
+    return s;
+}
+
+int ldpc_sim_message_length(const ldpc_sim *sim) {
+    if (!sim) return set_error(LDPC_EINVAL, "null sim");
+    return sim->dev.k;
+}
+
+int ldpc_sim_positions(const ldpc_sim *sim, int32_t *msg_pos, int32_t *par_pos) {
+    if (!sim) return set_error(LDPC_EINVAL, "null sim");
+    const int k = sim->dev.k, np = sim->systematic ? sim->p : std::max(0, std::min(sim->p, sim->dev.N - k));
+    for (int i = 0; msg_pos && i < k; i++) msg_pos[i] = sim->systematic ? sim->sf.msg_pos[i] : i;
+    for (int j = 0; par_pos && j < np; j++) par_pos[j] = sim->systematic ? sim->sf.par_pos[j] : k + j;
+    return np;
+}
+
 int ldpc_sim_encoder(const ldpc_sim *sim) {
     if (!sim) return set_error(LDPC_EINVAL, "null sim");
+    if (sim->systematic) return LDPC_ENCODER_SYSTEMATIC;
     if (sim->sparse) return LDPC_ENCODER_SPARSE;
     return sim->dev.qc_rot ? LDPC_ENCODER_QC : (sim->dev.gt ? LDPC_ENCODER_DENSE : LDPC_ENCODER_NONE);
 }
@@ -1172,7 +1259,7 @@ static int sim_generate_any(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, 
     if (!sim || !d_out || batch < 0 || batch > sim->max_batch) return set_error(LDPC_EINVAL, "ldpc_sim_generate: bad arguments");
     if (batch == 0) return LDPC_OK;
     HIPCHK(hipSetDevice(sim->device));
-    return ldpc::sim_generate(sim->dev, sim->sparse ? &sim->sp : nullptr, sim->d_msgw, sim->d_parw, (hipStream_t)stream, seed, first_frame, batch, ebn0_db, d_out, out_fmt, d_msg);
+    return ldpc::sim_generate(sim->dev, sim->sparse ? &sim->sp : nullptr, sim->systematic ? &sim->sy : nullptr, sim->d_msgw, sim->d_parw, (hipStream_t)stream, seed, first_frame, batch, ebn0_db, d_out, out_fmt, d_msg);
 }
 
 int ldpc_sim_generate(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, float *d_llr,
@@ -1193,11 +1280,23 @@ int ldpc_sim_tally(ldpc_sim *sim, int batch, const uint8_t *d_bits, const int32_
     if (!sim || !d_bits || !d_tally || batch < 0 || batch > sim->max_batch) return set_error(LDPC_EINVAL, "ldpc_sim_tally: bad arguments");
     if (batch == 0) return LDPC_OK;
     HIPCHK(hipSetDevice(sim->device));
+    if (sim->systematic)
+        return ldpc::sim_systematic_tally(sim->sy, sim->dev.N, sim->dev.k, sim->dev.kwords, sim->d_msgw, (hipStream_t)stream, batch, d_bits, d_iters,
+                                          (unsigned long long *)d_tally);
     return ldpc::sim_tally(sim->dev, sim->d_msgw, (hipStream_t)stream, batch, d_bits, d_iters, (unsigned long long *)d_tally);
 }
 
 int ldpc_sim_encode_host(const ldpc_sim *sim, const uint8_t *msg, uint8_t *parity) {
     if (!sim || !msg || !parity) return set_error(LDPC_EINVAL, "null argument");
+    if (sim->systematic) {   // parity bit j (at par_pos[j]) = XOR over the set message bits i of P[i][j]
+        const ldpc::SystematicForm &sf = sim->sf;
+        std::vector<uint64_t> acc((size_t)sf.pw64, 0ull);
+        for (int i = 0; i < sf.K; i++)
+            if (msg[i])
+                for (int w = 0; w < sf.pw64; w++) acc[w] ^= sf.P[(size_t)i * sf.pw64 + w];
+        for (int j = 0; j < sf.rank; j++) parity[j] = (uint8_t)((acc[j >> 6] >> (j & 63)) & 1ull);
+        return LDPC_OK;
+    }
     const int kw = sim->dev.kwords;
     std::vector<uint32_t> mw((size_t)kw, 0u);
     for (int r = 0; r < sim->dev.k; r++) if (msg[r]) mw[r >> 5] |= 1u << (r & 31);

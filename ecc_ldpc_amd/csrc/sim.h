@@ -22,9 +22,23 @@ struct SimSparse {
     int fw_cap;                      // frame words the scratch holds per position
 };
 int sim_sparse_parity(const SimSparse &sp, const uint32_t *msgw, int kwords, uint32_t *parw, int pwords, hipStream_t st, int batch);
-// parw: scratch for the packed parity words [batch][pwords] (quasi-cyclic encoder, encoder from H; null otherwise); sp: null
-// unless the source encodes from H
-int sim_generate(const SimDev &s, const SimSparse *sp, uint32_t *msgw, uint32_t *parw, hipStream_t st, uint64_t seed, uint64_t first_frame, int batch,
+// systematic form of any H (sim_systematic.hip): the codeword packed in H's column order, cww = ceil(N / 32) words per frame.
+// Words 0..w0-1 hold message positions only and ARE the message words (every column before the first parity position is a message
+// position, in order); words w0..cww-1 are the GF(2) product of the message with the window generator
+//   gwin[cg][i][16]: for column group cg (16 codeword words from w0 + 16 cg) and message bit i < 32 kwords, those words of the
+//   codeword of the unit message e_i (its own position and its parity bits; zero beyond the codeword and for i >= K)
+struct SimSys {
+    const uint32_t *gwin;
+    int ncg, w0, cww;
+    const int32_t *msg_pos;          // [K] ascending: where message bit i sits in the codeword
+};
+int sim_systematic_codeword(const SimSys &sy, const uint32_t *msgw, int kwords, uint32_t *cw, hipStream_t st, int batch);
+int sim_systematic_msg_bytes(const uint32_t *msgw, int kwords, int K, uint8_t *d_msg, hipStream_t st, int batch);
+int sim_systematic_tally(const SimSys &sy, int N, int K, int kwords, const uint32_t *msgw, hipStream_t st, int batch, const uint8_t *d_bits,
+                         const int32_t *d_iters, unsigned long long *d_tally);
+// parw: scratch for the packed parity words [batch][pwords] (quasi-cyclic encoder, encoder from H) or the packed codewords
+// [batch][cww] (systematic form); null otherwise.  sp / sy: null unless the source encodes from H that way
+int sim_generate(const SimDev &s, const SimSparse *sp, const SimSys *sy, uint32_t *msgw, uint32_t *parw, hipStream_t st, uint64_t seed, uint64_t first_frame, int batch,
                  double ebn0_db, void *d_out, int out_fmt, uint8_t *d_msg);   // out_fmt: 0 = f32 LLRs [batch][N], 1 = fp16 LLRs, 2 = codeword bytes [batch][n_tx]
 int sim_tally(const SimDev &s, const uint32_t *msgw, hipStream_t st, int batch, const uint8_t *d_bits, const int32_t *d_iters,
               unsigned long long *d_tally);

@@ -7,7 +7,8 @@
 //   (src/ECC/Code/LDPC/Utils.hs:61, Reference/Orig.hs:25-26, Fast/Encoder.hs:26-63) -- G dense (sim_frame_kernel), quasi-cyclic
 //   (sim_parity_qc_kernel), or none at all: all-zero codewords, or, for an H whose parity part is triangular after a row
 //   permutation, the same codeword by back-substitution FROM H (sim_sparse.hip; no counterpart in the reference).  The last two
-//   hand sim_frame_kernel packed parity words parw[frame][pwords];
+//   hand sim_frame_kernel packed parity words parw[frame][pwords].  ANY other H: a systematic form by GF(2) elimination, whose
+//   message and parity positions may interleave (sim_systematic.hip) -- it hands over whole packed codewords, read with k = 0;
 //   BPSK bit b -> 2b-1 (LLR > 0 <=> bit 1, `hard x = x > 0`); noise N(0, sigma^2),
 //   sigma^2 = 1/(2 R 10^(EbN0/10)), R = k/n_tx; LLR = 2y/sigma^2; punctured tail LLR = 0
 //   (Utils.hs:55 `unpuncture`).
@@ -251,13 +252,22 @@ __global__ __launch_bounds__(256) void sim_tally_kernel(SimDev s, const uint32_t
     }
 }
 
-int sim_generate(const SimDev &s, const SimSparse *sp, uint32_t *msgw, uint32_t *parw, hipStream_t st, uint64_t seed, uint64_t first_frame, int batch,
-                 double ebn0_db, void *d_out, int out_fmt, uint8_t *d_msg) {
-    const double R = (double)s.k / (double)s.n_tx;
+int sim_generate(const SimDev &s0, const SimSparse *sp, const SimSys *sy, uint32_t *msgw, uint32_t *parw, hipStream_t st, uint64_t seed, uint64_t first_frame,
+                 int batch, double ebn0_db, void *d_out, int out_fmt, uint8_t *d_msg0) {
+    // systematic form of any H: parw holds whole codewords in H's column order, so the frame kernel runs with k = 0 -- every position
+    // takes its parw branch -- and the message bytes come from sim_systematic_msg_bytes
+    SimDev s = s0;
+    uint8_t *d_msg = d_msg0;
+    if (sy) { s.k = 0; s.pwords = sy->cww; d_msg = nullptr; }
+    const double R = (double)s0.k / (double)s0.n_tx;
     const double sigma2 = 1.0 / (2.0 * R * pow(10.0, ebn0_db / 10.0));
     size_t nw = (size_t)batch * s.kwords;
-    hipLaunchKernelGGL(sim_msg_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, msgw, s.kwords, s.k, seed, first_frame, batch, (s.gt || parw) ? 0 : 1);
-    if (sp) {
+    hipLaunchKernelGGL(sim_msg_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, msgw, s.kwords, s0.k, seed, first_frame, batch, (s.gt || parw) ? 0 : 1);
+    if (sy) {
+        int rc = sim_systematic_codeword(*sy, msgw, s.kwords, parw, st, batch);
+        if (rc == LDPC_OK && d_msg0) rc = sim_systematic_msg_bytes(msgw, s.kwords, s0.k, d_msg0, st, batch);
+        if (rc != LDPC_OK) return rc;
+    } else if (sp) {
         const int rc = sim_sparse_parity(*sp, msgw, s.kwords, parw, s.pwords, st, batch);
         if (rc != LDPC_OK) return rc;
     } else if (s.qc_rot) {

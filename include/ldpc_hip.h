@@ -190,6 +190,20 @@ int ldpc_csr_layer_order(int M, int N, const int32_t *row_ptr, const int32_t *co
  * GPU.  LDPC_OK; LDPC_EINVAL for a malformed CSR; LDPC_EUNSUPPORTED when the rule fails, the message naming the first offending
  * row (for two rows that end in one column: both rows and the column).  No counterpart in the reference. */
 int ldpc_csr_triangular_order(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int32_t *order /* M */);
+/* A systematic form of ANY H (M x N as CSR; rows may be redundant or empty) by GF(2) elimination.  Visit the columns from N - 1
+ * down to 0: column c is a PARITY position iff it is not in the span of the parity positions already chosen (all > c).  The parity
+ * positions are par_pos[0..rank) ascending, rank = rank H; every other column is a MESSAGE position, msg_pos[0..K) ascending,
+ * K = N - rank.  The codeword of a message m has c[msg_pos[i]] = m[i], and c[par_pos[.]] the unique solution of H c = 0:
+ *   c[par_pos[j]] = XOR_i m[i] P[i][j],   P [K][rank] bytes 0/1 (may be NULL; K * rank <= N * N / 4, or call twice).
+ * The rule depends on the code only, not on how its rows are stored or how the elimination runs.  Whenever the last rank columns
+ * are independent it gives msg ++ parity, the reference's convention (Utils.hs:61) and that of every H
+ * ldpc_csr_triangular_order accepts; a zero column is a message position.  Pure host code (bit-packed elimination on 64-bit
+ * words), needs no GPU.  LIMIT: M * N <= 2^28 (about 3e10 word operations, tens of seconds, at the limit) -- LDPC_EUNSUPPORTED
+ * above it, before any elimination; DVB-S2-shaped matrices of that size encode through ldpc_sim_create_sparse_on.
+ * LDPC_EINVAL for a malformed CSR (the checks of ldpc_csr_triangular_order), LDPC_EUNSUPPORTED for K = 0 ("no message bits").
+ * msg_pos and par_pos are caller arrays of N entries.  No counterpart in the reference. */
+int ldpc_csr_systematic_form(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int32_t *msg_pos /* N */,
+                             int32_t *par_pos /* N */, int *K, int *rank, uint8_t *P /* may be NULL; [K][rank] */);
 int ldpc_code_layers(const ldpc_code *code, int *n_layers, int32_t *layer_ptr /* may be NULL; n_layers+1 entries */);
 
 /* ---- decoder replica -------------------------------------------------------------------------
@@ -394,8 +408,22 @@ ldpc_sim *ldpc_sim_create_qc_on(const ldpc_code *code, int device, int k, int n_
  * machine word.  Device scratch besides the packed messages and parity bits: at most 4 * N * ceil(max_batch / 32) bytes, and
  * never more than 2048 * N (larger batches pass through it in chunks of 16 384 frames). */
 ldpc_sim *ldpc_sim_create_sparse_on(const ldpc_code *code, int device, int n_tx, int max_batch);
-enum { LDPC_ENCODER_NONE = 0, LDPC_ENCODER_DENSE = 1, LDPC_ENCODER_QC = 2, LDPC_ENCODER_SPARSE = 3 };
+/* The encoder from ANY H, through the systematic form of ldpc_csr_systematic_form (its limit and refusals apply: NULL with that
+ * function's code and reason): k = K = N - rank H, K <= n_tx <= N (LDPC_EINVAL otherwise), R = K / n_tx, positions n_tx..N-1
+ * punctured as above whatever they carry; a quasi-cyclic code is taken as its CSR form.  Message bit i of the usual
+ * (seed, frame) -> message words sits at codeword position msg_pos[i] (ldpc_sim_positions): d_msg is [batch][K] in msg_pos order,
+ * ldpc_sim_encode_host returns the rank parity bits in par_pos order, ldpc_sim_tally counts message-bit errors at msg_pos.
+ * Device memory besides the packed messages: 4 * ceil(N / 32) * max_batch bytes of packed codewords (no further scratch, so no
+ * chunking: any batch <= max_batch is one pass) and a generator of 2048 * ceil(K / 32) bytes per 512 codeword positions from the
+ * first parity position on. */
+ldpc_sim *ldpc_sim_create_systematic_on(const ldpc_code *code, int device, int n_tx, int max_batch);
+enum { LDPC_ENCODER_NONE = 0, LDPC_ENCODER_DENSE = 1, LDPC_ENCODER_QC = 2, LDPC_ENCODER_SPARSE = 3, LDPC_ENCODER_SYSTEMATIC = 4 };
 int ldpc_sim_encoder(const ldpc_sim *sim);    /* which of these this frame source encodes with */
+int ldpc_sim_message_length(const ldpc_sim *sim);     /* k of any source; K = N - rank H for LDPC_ENCODER_SYSTEMATIC */
+/* where the message bits (msg_pos [k], may be NULL) and the parity bits (par_pos, may be NULL; N entries suffice) sit in the
+ * codeword.  Returns the number of parity positions (< 0 on error).  LDPC_ENCODER_SYSTEMATIC: those of ldpc_csr_systematic_form;
+ * every other source: 0..k-1 and k.. */
+int ldpc_sim_positions(const ldpc_sim *sim, int32_t *msg_pos, int32_t *par_pos);
 /* the encoder alone: codewords [batch][n_tx] bytes (device) of the same messages ldpc_sim_generate would use (message
  * bits of frame f depend on (seed, f) only); d_msg [batch][k] may be NULL.  Enqueued on `stream`. */
 int ldpc_sim_encode_batch(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, uint8_t *d_codewords, uint8_t *d_msg, void *stream);

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
-"""tools/encoder_rate.py [frames] [--sparse-only] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
+"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
 sim.hip sim_parity_qc_kernel) against the dense packed GF(2) mat-vec of the expanded generator (Orig.hs:25-26), on the shipped AR4JA
 codes: the encoder alone (ldpc_sim_encode_batch: messages + parity -> codeword bytes) and the whole frame source
 (ldpc_sim_generate: + BPSK, AWGN, LLRs).  HIP events on the launch stream, median of 7.
 Then the encoder FROM H (sim_sparse.hip) on the DVB-S2 structures of tests/dvbs2_short.py and tests/dvbs2_natural.py, in helper order:
 the encoder alone, the whole generate, the encoder-less generate (all-zero codewords) of the same shape, and -- the yardstick: a BER
 loop is at most doubled while generate costs no more than it -- the fp16-lam layered decode of that batch at 2 dB.  One warm-up,
-median of 5.  --sparse-only: only that part."""
+median of 5.  --sparse-only: only that part.
+--systematic-only: the encoder from ANY H (sim_systematic.hip, Sim(systematic=True)): on jpl.4096.4.5 next to the dense encoder of the
+expanded generator (the same K x r product) and the quasi-cyclic one, codewords compared on the device and their SHA-256 printed; then on
+codes/1920.1280.3.303 (no generator, not accumulator-shaped) generate against the fp16-lam layered decode of the same frames at 2 dB."""
 import os
 import sys
 
@@ -72,6 +75,95 @@ def sparse_leg(B, dev, st):
         torch.cuda.empty_cache()
 
 
+def decode_time(code, llr, B, N, dev, st):
+    """-> (median kernel ms of five fp16-lam layered decodes after a warm-up, decoder, bits, its, conv)"""
+    import statistics
+    dec = E.Decoder(code, "min", "f16", B, schedule="layered")
+    bits = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    its = torch.empty(B, dtype=torch.int32, device=dev)
+    conv = torch.empty(B, dtype=torch.uint8, device=dev)
+    dec.set_timing(True)
+    ts = []
+    for r in range(6):                                           # the first launch warms up
+        dec.decode_batch_dev(llr.data_ptr(), bits.data_ptr(), B, 50, its.data_ptr(), conv.data_ptr(), st.cuda_stream)
+        dec.synchronize(); torch.cuda.synchronize()
+        n, ms = dec.kernel_time()
+        if r:
+            ts.append(ms / max(n, 1))
+    return statistics.median(ts), dec, bits, its, conv
+
+
+def sha(t):
+    import hashlib
+    return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()[:16]
+
+
+def systematic_leg(B, dev, st):
+    from tests.helpers import load
+    name = "ldpc/hip-minsum/jpl.4096.4.5/50/4/5"
+    c = load("jpl.4096.4.5")
+    cws = {}
+    for enc in ("dense", "qc", "systematic", "dense", "systematic"):     # the two compared legs twice, alternating: their spread
+        ecc = None
+        if enc == "systematic":
+            code = c.hip_code(E)
+            sim = E.Sim(code, None, c.n_tx, systematic=True, max_batch=B)
+            k, n_tx, N = sim.k, c.n_tx, c.N
+        else:
+            if enc == "dense":
+                os.environ["LDPC_SIM_ENCODER"] = "dense"
+            else:
+                os.environ.pop("LDPC_SIM_ENCODER", None)
+            ecc = E.ECC(os.path.join(ROOT, "codes"), name, max_batch=B)
+            sim, k, n_tx, N = ecc.sim, ecc.message_length, ecc.codeword_length, ecc.unpunctured_length
+        assert sim.encoder == enc and (k, n_tx, N) == (c.k, c.n_tx, c.N)
+        cw = torch.empty((B, n_tx), dtype=torch.uint8, device=dev)
+        llr = torch.empty((B, N), dtype=torch.float32, device=dev)
+        t_enc = timed(lambda: sim.encode_batch(1, 0, B, cw.data_ptr(), None, st.cuda_stream), st)
+        t_gen = timed(lambda: sim.generate(1, 0, B, 2.0, llr.data_ptr(), None, st.cuda_stream), st)
+        print(f"jpl.4096.4.5 {enc:10s} encoder: {B} frames  encode_batch {t_enc:7.3f} ms = {B * k / t_enc / 1e6:8.1f} Gbit/s info"
+              f" | generate (encode + AWGN + LLR) {t_gen:7.3f} ms | codewords sha256 {sha(cw)} LLRs sha256 {sha(llr)}", flush=True)
+        if enc in cws:
+            assert torch.equal(cws[enc], cw)
+        cws[enc] = cw
+        (ecc or sim).close()
+        if ecc is None:
+            code.close()
+        del llr
+    assert torch.equal(cws["dense"], cws["systematic"]) and torch.equal(cws["qc"], cws["systematic"]), "encoders disagree"
+    print("             codewords of the dense, quasi-cyclic and systematic encoders identical", flush=True)
+    cws.clear()
+    torch.cuda.empty_cache()
+    m = load("1920.1280.3.303")
+    rp, ci, N = m.graph.row_ptr, m.graph.col_idx, m.N
+    perm, lp = E.Code.csr_layer_order(rp, ci, N)
+    code = E.Code.from_csr(*E.Code.permute_rows(rp, ci, perm), N)
+    code.set_layers(lp)
+    sim = E.Sim(code, None, N, systematic=True, max_batch=B)
+    K = sim.k
+    plain = E.Sim(code, K, N, max_batch=B)
+    assert (sim.encoder, plain.encoder) == ("systematic", "none")
+    cw = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    llr = torch.empty((B, N), dtype=torch.float32, device=dev)
+    t_enc = timed(lambda: sim.encode_batch(1, 0, B, cw.data_ptr(), None, st.cuda_stream), st, 5)
+    t_zero = timed(lambda: plain.generate(1, 0, B, 2.0, llr.data_ptr(), None, st.cuda_stream), st, 5)
+    t_gen = timed(lambda: sim.generate(1, 0, B, 2.0, llr.data_ptr(), None, st.cuda_stream), st, 5)
+    par = torch.from_numpy(sim.positions()[1].astype("int64")).to(dev)
+    ones = float(cw[:, par].float().mean())
+    del cw
+    t_dec, dec, bits, its, conv = decode_time(code, llr, B, N, dev, st)
+    tally = torch.zeros(4, dtype=torch.int64, device=dev)
+    sim.tally(B, bits.data_ptr(), its.data_ptr(), tally.data_ptr(), st.cuda_stream)
+    torch.cuda.synchronize()
+    fr, fe, be, _ = tally.cpu().tolist()
+    print(f"1920.1280.3.303 N={N} K={K} systematic encoder (from H, helper order): {B} frames  encode_batch {t_enc:7.3f} ms = {B * K / t_enc / 1e6:8.1f} Gbit/s info"
+          f" | generate {t_gen:7.3f} ms | encoder-less generate {t_zero:7.3f} ms | parity ones {ones:.4f}", flush=True)
+    print(f"{'':15s} fp16-lam layered decode of that batch at 2 dB ({dec.kernel_name}): {t_dec:7.3f} ms, sweeps {float(its.float().mean()):.2f}, "
+          f"converged {float(conv.float().mean()):.4f}, tally {fr} frames {fe} frame errors {be} message-bit errors"
+          f" | generate / decode = {t_gen / t_dec:.3f} ({'within' if t_gen <= t_dec else 'MISSES'} the bar generate <= decode)", flush=True)
+    dec.close(); sim.close(); plain.close(); code.close()
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     B = int(args[0]) if args else 65536
@@ -79,6 +171,9 @@ def main():
     dev = torch.device("cuda", 0)
     st = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(st)
+    if "--systematic-only" in sys.argv:
+        systematic_leg(B, dev, st)
+        return
     if "--sparse-only" in sys.argv:
         sparse_leg(B, dev, st)
         return

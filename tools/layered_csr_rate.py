@@ -18,7 +18,7 @@
   frame and bit error rate per leg.  Nothing else is run.
   --codewords zero|random (the --lam i8 and --cn-scale / --cn-offset comparisons, which report error rates): zero, the default, transmits
   the all-zero codeword; random takes the codewords of random messages from the frame source's encoder from H (Sim(from_H=True).encode_batch)
-  on the structures that qualify (the DVB-S2 ones; 1920.1280.3.303 does not and stays all-zero) and mirrors the SAME torch noise onto
+  on the structures that qualify (the DVB-S2 ones), from its systematic form (Sim(systematic=True)) otherwise (1920.1280.3.303), and mirrors the SAME torch noise onto
   them, y = (2c - 1) + noise with the same generator and seed: a zero leg and a random leg differ only in the codeword.  FER / BER are
   counted against the transmitted codeword.
 Decoded-information Gbit/s = frames x k / kernel time (HIP events around the decode kernel, the median of the timed launches);
@@ -87,13 +87,18 @@ def transmitted(a, code, rp, ci, N, k, F, out):
         E.Code.csr_triangular_order(rp, ci, N)
         sim = E.Sim(code, k, N, from_H=True, max_batch=F)
     except E.LdpcError as e:
-        out(f"  all-zero codewords here: {e}")
-        return None
+        try:                                                          # not accumulator-shaped: the systematic form of H
+            sim = E.Sim(code, None, N, systematic=True, max_batch=F)
+            assert sim.k == k, (sim.k, k)
+        except E.LdpcError as e2:
+            out(f"  all-zero codewords here: {e}; {e2}")
+            return None
     cw = torch.empty((F, N), dtype=torch.uint8, device="cuda")
     sim.encode_batch(0xC0DE, 0, F, cw.data_ptr(), None, None)
     torch.cuda.synchronize()
+    par = torch.from_numpy(sim.positions()[1].astype("int64")).cuda()
+    out(f"  codewords of random messages ({sim.encoder} encoder from H), parity ones {float(cw[:, par].float().mean()):.4f}")
     sim.close()
-    out(f"  codewords of random messages (encoder from H), parity ones {float(cw[:, k:].float().mean()):.4f}")
     return cw
 
 
