@@ -19,6 +19,7 @@ F32, F64, F16, F16PK, I8 = 0, 1, 2, 3, 4
 PATH_AUTO, PATH_FLOOD, PATH_FUSED = 0, 1, 2
 SCHED_FLOODING, SCHED_LAYERED = 0, 1
 SUM_REFERENCE, SUM_ARRAYLET, SUM_SPARSE = 0, 1, 2
+BITS_BYTES, BITS_PACKED = 0, 1   # ldpc_bit_format
 
 
 class CtxConfig(C.Structure):   # ldpc_ctx_config
@@ -42,6 +43,7 @@ ABI_SYMBOLS = [
     "ldpc_sim_create_qc_on", "ldpc_sim_encoder", "ldpc_sim_encode_batch", "ldpc_matrix_qc_words", "ldpc_matrix_rank",
     "ldpc_csr_triangular_order", "ldpc_sim_create_sparse_on",
     "ldpc_csr_systematic_form", "ldpc_sim_create_systematic_on", "ldpc_sim_message_length", "ldpc_sim_positions",
+    "ldpc_sim_encode_messages", "ldpc_sim_generate_from", "ldpc_sim_extract_messages",
     "ldpc_matrix_load", "ldpc_matrix_load_mackay", "ldpc_matrix_destroy", "ldpc_matrix_info", "ldpc_matrix_dense",
     "ldpc_matrix_qc_offsets", "ldpc_code_from_matrix",
     "ldpc_ecc_create", "ldpc_ecc_destroy", "ldpc_ecc_name", "ldpc_ecc_message_length", "ldpc_ecc_codeword_length",
@@ -228,6 +230,9 @@ def lib():
     L.ldpc_sim_message_length.argtypes = [vp]
     L.ldpc_sim_positions.argtypes = [vp, i32p, i32p]
     L.ldpc_sim_encode_batch.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp, vp]
+    L.ldpc_sim_encode_messages.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]
+    L.ldpc_sim_generate_from.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, vp]
+    L.ldpc_sim_extract_messages.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
     L.ldpc_matrix_qc_words.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.ldpc_matrix_rank.argtypes = [vp]
     L.ldpc_matrix_load.restype = vp
@@ -795,6 +800,26 @@ class Sim:
     def encode_batch(self, seed, first_frame, batch, d_codewords_ptr, d_msg_ptr=None, stream=None):
         """the encoder alone: codewords [batch][n_tx] bytes on the device"""
         check(lib().ldpc_sim_encode_batch(self._h, int(seed), int(first_frame), int(batch), d_codewords_ptr, d_msg_ptr, stream))
+
+    @staticmethod
+    def _bits_fmt(fmt):
+        """"bytes" / "packed" (or the integer of ldpc_bit_format, passed through for the library to judge)"""
+        return {"bytes": BITS_BYTES, "packed": BITS_PACKED}[fmt] if isinstance(fmt, str) else int(fmt)
+
+    def encode_messages(self, batch, d_msg_ptr, d_cw_ptr, msg_fmt="bytes", cw_fmt="bytes", stream=None):
+        """the encoder alone on the caller's messages (device pointers).  "bytes": messages [batch][k], codewords [batch][n_tx], one
+        byte per bit; "packed": message rows of 4 * ceil(k / 32) bytes, codeword rows of ceil(n_tx / 8) bytes, bit i in byte i / 8 at
+        bit i % 8.  Messages are in the order of positions()[0]."""
+        check(lib().ldpc_sim_encode_messages(self._h, int(batch), d_msg_ptr, self._bits_fmt(msg_fmt), d_cw_ptr, self._bits_fmt(cw_fmt), stream))
+
+    def generate_from(self, seed, first_frame, batch, ebn0_db, d_msg_ptr, d_llr_ptr, msg_fmt="bytes", stream=None, llr_f16=False):
+        """generate() with the caller's messages in place of the drawn ones: the same noise, LLRs [batch][N] float32 or fp16"""
+        check(lib().ldpc_sim_generate_from(self._h, int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_ptr, self._bits_fmt(msg_fmt),
+                                           d_llr_ptr, int(llr_f16), stream))
+
+    def extract_messages(self, batch, d_bits_ptr, d_msg_ptr, msg_fmt="bytes", stream=None):
+        """decoded bytes [batch][N] -> the messages (bit i = decoded bit positions()[0][i]) in msg_fmt"""
+        check(lib().ldpc_sim_extract_messages(self._h, int(batch), d_bits_ptr, d_msg_ptr, self._bits_fmt(msg_fmt), stream))
 
     def tally(self, batch, d_bits_ptr, d_iters_ptr, d_tally_ptr, stream=None):
         check(lib().ldpc_sim_tally(self._h, int(batch), d_bits_ptr, d_iters_ptr, d_tally_ptr, stream))

@@ -1027,6 +1027,8 @@ struct ldpc_sim {
     ldpc::SystematicForm sf;
     uint32_t *d_gwin = nullptr;
     int32_t *d_msg_pos = nullptr;
+    // dense source, packed codewords (ldpc_sim_encode_messages): codeword bytes [max_batch][n_tx] for pack_bits, allocated on first use
+    uint8_t *d_stage = nullptr;
 };
 extern "C" {
 
@@ -1041,6 +1043,7 @@ void ldpc_sim_destroy(ldpc_sim *sim) {
     hipFree(sim->d_x);
     hipFree(sim->d_gwin);
     hipFree(sim->d_msg_pos);
+    hipFree(sim->d_stage);
     delete sim;
 }
 
@@ -1274,6 +1277,61 @@ int ldpc_sim_generate_f16(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, in
 
 int ldpc_sim_encode_batch(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, uint8_t *d_codewords, uint8_t *d_msg, void *stream) {
     return sim_generate_any(sim, seed, first_frame, batch, 0.0, d_codewords, 2, d_msg, stream);
+}
+
+// caller-supplied messages: the checks the three entry points share, then the message words
+static int sim_check_messages(const char *what, const ldpc_sim *sim, int batch, const void *a, const void *b, int fmt_a, int fmt_b, bool encodes) {
+    if (!sim || !a || !b) return set_error(LDPC_EINVAL, "%s: null argument", what);
+    if (batch <= 0 || batch > sim->max_batch) return set_error(LDPC_EINVAL, "%s: batch %d outside 1..%d", what, batch, sim->max_batch);
+    if ((fmt_a != LDPC_BITS_BYTES && fmt_a != LDPC_BITS_PACKED) || (fmt_b != LDPC_BITS_BYTES && fmt_b != LDPC_BITS_PACKED))
+        return set_error(LDPC_EINVAL, "%s: unknown bit format (LDPC_BITS_BYTES = 0, LDPC_BITS_PACKED = 1)", what);
+    if (encodes && ldpc_sim_encoder(sim) == LDPC_ENCODER_NONE)
+        return set_error(LDPC_EUNSUPPORTED, "%s: this frame source has no encoder (msg ++ zeros is not a codeword); create it with a generator or from H", what);
+    return LDPC_OK;
+}
+
+static int sim_load(const char *what, ldpc_sim *sim, int batch, const void *d_msg, int msg_fmt, void *stream) {
+    if (msg_fmt == LDPC_BITS_PACKED && (uintptr_t)d_msg % 4 != 0) return set_error(LDPC_EINVAL, "%s: packed message rows must be 4-byte aligned", what);
+    return ldpc::sim_load_messages((hipStream_t)stream, d_msg, msg_fmt, sim->d_msgw, sim->dev.kwords, sim->dev.k, batch);
+}
+
+int ldpc_sim_encode_messages(ldpc_sim *sim, int batch, const void *d_msg, int msg_fmt, void *d_codewords, int cw_fmt, void *stream) {
+    int rc = sim_check_messages("ldpc_sim_encode_messages", sim, batch, d_msg, d_codewords, msg_fmt, cw_fmt, true);
+    if (rc != LDPC_OK) return rc;
+    HIPCHK(hipSetDevice(sim->device));
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = sim_load("ldpc_sim_encode_messages", sim, batch, d_msg, msg_fmt, stream)) != LDPC_OK) return rc;
+    const ldpc::SimSparse *sp = sim->sparse ? &sim->sp : nullptr;
+    const ldpc::SimSys *sy = sim->systematic ? &sim->sy : nullptr;
+    if (cw_fmt == LDPC_BITS_BYTES || sim->d_parw)
+        return ldpc::sim_generate(sim->dev, sp, sy, sim->d_msgw, sim->d_parw, st, 0, 0, batch, 0.0, d_codewords, cw_fmt == LDPC_BITS_BYTES ? 2 : 3, nullptr, true);
+    // dense generator: the product lives inside the frame kernel, which writes bytes; pack those
+    if (!sim->d_stage) {
+        hipError_t e = hipMalloc((void **)&sim->d_stage, (size_t)sim->max_batch * sim->dev.n_tx);
+        if (e != hipSuccess) { sim->d_stage = nullptr; return set_error(LDPC_EHIP, "ldpc_sim_encode_messages: staging buffer: %s", hipGetErrorString(e)); }
+    }
+    rc = ldpc::sim_generate(sim->dev, sp, sy, sim->d_msgw, sim->d_parw, st, 0, 0, batch, 0.0, sim->d_stage, 2, nullptr, true);
+    if (rc != LDPC_OK) return rc;
+    return ldpc::pack_bits(st, sim->d_stage, (uint8_t *)d_codewords, batch, sim->dev.n_tx);
+}
+
+int ldpc_sim_generate_from(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg, int msg_fmt, void *d_llr,
+                           int llr_f16, void *stream) {
+    int rc = sim_check_messages("ldpc_sim_generate_from", sim, batch, d_msg, d_llr, msg_fmt, LDPC_BITS_BYTES, true);
+    if (rc != LDPC_OK) return rc;
+    if (llr_f16 != 0 && llr_f16 != 1) return set_error(LDPC_EINVAL, "ldpc_sim_generate_from: llr_f16 must be 0 (float32) or 1 (fp16)");
+    HIPCHK(hipSetDevice(sim->device));
+    if ((rc = sim_load("ldpc_sim_generate_from", sim, batch, d_msg, msg_fmt, stream)) != LDPC_OK) return rc;
+    return ldpc::sim_generate(sim->dev, sim->sparse ? &sim->sp : nullptr, sim->systematic ? &sim->sy : nullptr, sim->d_msgw, sim->d_parw, (hipStream_t)stream, seed,
+                              first_frame, batch, ebn0_db, d_llr, llr_f16, nullptr, true);
+}
+
+int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream) {
+    const int rc = sim_check_messages("ldpc_sim_extract_messages", sim, batch, d_bits, d_msg, msg_fmt, LDPC_BITS_BYTES, false);
+    if (rc != LDPC_OK) return rc;
+    if (msg_fmt == LDPC_BITS_PACKED && (uintptr_t)d_msg % 4 != 0) return set_error(LDPC_EINVAL, "ldpc_sim_extract_messages: packed message rows must be 4-byte aligned");
+    HIPCHK(hipSetDevice(sim->device));
+    return ldpc::sim_extract_messages((hipStream_t)stream, d_bits, sim->dev.N, sim->systematic ? sim->sy.msg_pos : nullptr, d_msg, msg_fmt, sim->dev.kwords, sim->dev.k, batch);
 }
 
 int ldpc_sim_tally(ldpc_sim *sim, int batch, const uint8_t *d_bits, const int32_t *d_iters, uint64_t *d_tally, void *stream) {

@@ -38,8 +38,14 @@ int sim_systematic_tally(const SimSys &sy, int N, int K, int kwords, const uint3
                          const int32_t *d_iters, unsigned long long *d_tally);
 // parw: scratch for the packed parity words [batch][pwords] (quasi-cyclic encoder, encoder from H) or the packed codewords
 // [batch][cww] (systematic form); null otherwise.  sp / sy: null unless the source encodes from H that way
+// msgw_ready: the message words are already in msgw (sim_load_messages): no message is drawn, seed and first_frame key the noise only
 int sim_generate(const SimDev &s, const SimSparse *sp, const SimSys *sy, uint32_t *msgw, uint32_t *parw, hipStream_t st, uint64_t seed, uint64_t first_frame, int batch,
-                 double ebn0_db, void *d_out, int out_fmt, uint8_t *d_msg);   // out_fmt: 0 = f32 LLRs [batch][N], 1 = fp16 LLRs, 2 = codeword bytes [batch][n_tx]
+                 double ebn0_db, void *d_out, int out_fmt, uint8_t *d_msg,    // out_fmt: 0 = f32 LLRs [batch][N], 1 = fp16 LLRs, 2 = codeword bytes [batch][n_tx],
+                 bool msgw_ready = false);                                    // 3 = packed codewords [batch][ceil(n_tx / 8)] (sources with parw only)
+// caller-supplied messages (include/ldpc_hip.h ldpc_bit_format; fmt 0: bytes [batch][k], 1: packed rows of kwords words) -> msgw, bits >= k zero
+int sim_load_messages(hipStream_t st, const void *d_msg, int fmt, uint32_t *msgw, int kwords, int k, int batch);
+// d_msg (same two formats) <- bits[frame][msg_pos[i]] of decoded bytes [batch][N]; msg_pos null = positions 0..k-1
+int sim_extract_messages(hipStream_t st, const uint8_t *d_bits, int N, const int32_t *msg_pos, void *d_msg, int fmt, int kwords, int k, int batch);
 int sim_tally(const SimDev &s, const uint32_t *msgw, hipStream_t st, int batch, const uint8_t *d_bits, const int32_t *d_iters,
               unsigned long long *d_tally);
 // hard bits, one byte each [batch][N] -> packed [batch][ceil(N/8)], bit i of a frame in byte i / 8 at bit i % 8

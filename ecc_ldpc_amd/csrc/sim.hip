@@ -15,9 +15,12 @@
 // Randomness: Philox4x32-10 keyed by the 64-bit seed, counter = (global frame id, index / 4, stream),
 // so a frame's content depends only on (seed, frame id): ranks generate disjoint frame ranges
 // with no scatter.
+// The message words may also come from the caller (sim_load_messages: bytes or packed bits -> msgw; sim_generate then skips the draw and
+// Philox keys the noise alone), and the codewords may leave packed (sim_pack_codeword_kernel); sim_extract_messages is the way back.
 #include "internal.h"
 #include "sim.h"
 #include <hip/hip_fp16.h>
+#include <algorithm>
 
 namespace ldpc {
 
@@ -252,8 +255,122 @@ __global__ __launch_bounds__(256) void sim_tally_kernel(SimDev s, const uint32_t
     }
 }
 
+// ---- caller-supplied messages (ldpc_sim_encode_messages, ldpc_sim_generate_from, ldpc_sim_extract_messages).  The three kernels
+// index (frame, word) through one flat grid-stride loop over blockIdx.x: no batch limit of their own.
+static unsigned sim_grid(size_t total) { return (unsigned)std::min<size_t>((total + 255) / 256, (size_t)1 << 20); }
+// bit 0 of the four bytes of a word, LSB first
+static __device__ __forceinline__ uint32_t bits4(uint32_t w) { return (w & 1u) | ((w >> 7) & 2u) | ((w >> 14) & 4u) | ((w >> 21) & 8u); }
+static __device__ __forceinline__ uint32_t bits16(uint4 a) { return bits4(a.x) | (bits4(a.y) << 4) | (bits4(a.z) << 8) | (bits4(a.w) << 12); }
+
+// message bytes [batch][k] (bit 0 of each) -> msgw[frame][w]: a lane makes one whole word from 32 consecutive bytes.  VEC: k % 16 == 0 and
+// a 16-byte aligned buffer, so every word starts on a 16-byte boundary and holds 16 or 32 bits: one or two 16-byte loads
+template <bool VEC>
+__global__ __launch_bounds__(256) void sim_load_bytes_kernel(const uint8_t *__restrict__ src, uint32_t *__restrict__ msgw, int kwords, int k, size_t total) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t f = i / kwords;
+        const int w = (int)(i - f * kwords);
+        const uint8_t *row = src + f * k + 32 * w;
+        const int rem = min(32, k - 32 * w);   // bits of this word, >= 1; the others stay 0
+        uint32_t v = 0u;
+        if constexpr (VEC) {
+            v = bits16(*reinterpret_cast<const uint4 *>(row));
+            if (rem == 32) v |= bits16(*reinterpret_cast<const uint4 *>(row + 16)) << 16;
+        } else {
+            for (int b = 0; b < rem; b++) v |= (uint32_t)(row[b] & 1u) << b;
+        }
+        msgw[i] = v;
+    }
+}
+
+// packed message rows of kwords little-endian words ARE the message words, but for the bits >= k of the last one
+__global__ __launch_bounds__(256) void sim_load_packed_kernel(const uint32_t *__restrict__ src, uint32_t *__restrict__ msgw, int kwords, int k, size_t total) {
+    const uint32_t tail = (k & 31) ? ((1u << (k & 31)) - 1u) : 0xffffffffu;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        msgw[i] = src[i] & ((int)(i % kwords) == kwords - 1 ? tail : 0xffffffffu);
+}
+
+// packed codewords [batch][PB = ceil(n_tx / 8)] bytes: one lane = output word j of a frame, codeword bits 32 j .. 32 j + 31 =
+// message bits below k, parity bits (parw, from bit 0) above: a message word, a parity word pair funnel-shifted by k % 32, or,
+// for the one word that straddles k, both.  Cut at n_tx, pad bits 0.  k = 0: parw holds whole codewords.  words_ok: PB % 4 == 0 and a
+// 4-byte aligned buffer, word stores; otherwise the bytes of the word one by one (rows need not start on a word then)
+__global__ __launch_bounds__(256) void sim_pack_codeword_kernel(const uint32_t *__restrict__ msgw, const uint32_t *__restrict__ parw, uint8_t *__restrict__ out, int k,
+                                                                int n_tx, int kwords, int pwords, int cwords, int PB, int words_ok, size_t total) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t f = i / cwords;
+        const int j = (int)(i - f * cwords), n0 = 32 * j;
+        uint32_t v;
+        if (n0 + 32 <= k) {
+            v = msgw[f * kwords + j];
+        } else {
+            const uint32_t *pw = parw + f * pwords;
+            if (n0 >= k) {                       // (n0 < n_tx <= k + 32 pwords: q < pwords)
+                const int q = (n0 - k) >> 5, sh = (n0 - k) & 31;
+                const uint32_t lo = pw[q], hi = (sh && q + 1 < pwords) ? pw[q + 1] : 0u;
+                v = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+            } else {
+                const int r = k - n0;            // 1 .. 31 message bits, then parity bits from bit 0
+                v = (msgw[f * kwords + j] & ((1u << r) - 1u)) | (pw[0] << r);
+            }
+        }
+        const int rem = n_tx - n0;               // >= 1
+        if (rem < 32) v &= (1u << rem) - 1u;
+        if (words_ok) {
+            reinterpret_cast<uint32_t *>(out)[i] = v;
+        } else {
+            uint8_t *dst = out + f * PB + 4 * j;
+#pragma unroll
+            for (int b = 0; b < 4; b++)
+                if (4 * j + b < PB) dst[b] = (uint8_t)(v >> (8 * b));
+        }
+    }
+}
+
+// decoded bytes [batch][N] -> the message in msg_pos order: PACKED = words of 32 bits (rows of kwords words, bits >= k zero), else bytes [batch][k]
+template <bool PACKED>
+__global__ __launch_bounds__(256) void sim_extract_kernel(const uint8_t *__restrict__ bits, int N, const int32_t *__restrict__ msg_pos, void *__restrict__ out, int kwords,
+                                                          int k, size_t total) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        if constexpr (PACKED) {
+            const size_t f = i / kwords;
+            const int w = (int)(i - f * kwords), rem = min(32, k - 32 * w);
+            const uint8_t *row = bits + f * N;
+            uint32_t v = 0u;
+            for (int b = 0; b < rem; b++) v |= (uint32_t)(row[msg_pos ? msg_pos[32 * w + b] : 32 * w + b] & 1u) << b;
+            static_cast<uint32_t *>(out)[i] = v;
+        } else {
+            const size_t f = i / k;
+            const int m = (int)(i - f * k);
+            static_cast<uint8_t *>(out)[i] = bits[f * N + (msg_pos ? msg_pos[m] : m)] & 1u;
+        }
+    }
+}
+
+int sim_load_messages(hipStream_t st, const void *d_msg, int fmt, uint32_t *msgw, int kwords, int k, int batch) {
+    const size_t total = (size_t)batch * kwords;
+    const dim3 grid(sim_grid(total));
+    if (fmt == 1) hipLaunchKernelGGL(sim_load_packed_kernel, grid, dim3(256), 0, st, (const uint32_t *)d_msg, msgw, kwords, k, total);
+    else if (k % 16 == 0 && (uintptr_t)d_msg % 16 == 0) hipLaunchKernelGGL((sim_load_bytes_kernel<true>), grid, dim3(256), 0, st, (const uint8_t *)d_msg, msgw, kwords, k, total);
+    else hipLaunchKernelGGL((sim_load_bytes_kernel<false>), grid, dim3(256), 0, st, (const uint8_t *)d_msg, msgw, kwords, k, total);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(LDPC_EHIP, "sim_load_messages: %s", hipGetErrorString(e));
+    return LDPC_OK;
+}
+
+int sim_extract_messages(hipStream_t st, const uint8_t *d_bits, int N, const int32_t *msg_pos, void *d_msg, int fmt, int kwords, int k, int batch) {
+    if (fmt == 1) {
+        const size_t total = (size_t)batch * kwords;
+        hipLaunchKernelGGL((sim_extract_kernel<true>), dim3(sim_grid(total)), dim3(256), 0, st, d_bits, N, msg_pos, d_msg, kwords, k, total);
+    } else {
+        const size_t total = (size_t)batch * k;
+        hipLaunchKernelGGL((sim_extract_kernel<false>), dim3(sim_grid(total)), dim3(256), 0, st, d_bits, N, msg_pos, d_msg, kwords, k, total);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(LDPC_EHIP, "sim_extract_messages: %s", hipGetErrorString(e));
+    return LDPC_OK;
+}
+
 int sim_generate(const SimDev &s0, const SimSparse *sp, const SimSys *sy, uint32_t *msgw, uint32_t *parw, hipStream_t st, uint64_t seed, uint64_t first_frame,
-                 int batch, double ebn0_db, void *d_out, int out_fmt, uint8_t *d_msg0) {
+                 int batch, double ebn0_db, void *d_out, int out_fmt, uint8_t *d_msg0, bool msgw_ready) {
     // systematic form of any H: parw holds whole codewords in H's column order, so the frame kernel runs with k = 0 -- every position
     // takes its parw branch -- and the message bytes come from sim_systematic_msg_bytes
     SimDev s = s0;
@@ -262,7 +379,8 @@ int sim_generate(const SimDev &s0, const SimSparse *sp, const SimSys *sy, uint32
     const double R = (double)s0.k / (double)s0.n_tx;
     const double sigma2 = 1.0 / (2.0 * R * pow(10.0, ebn0_db / 10.0));
     size_t nw = (size_t)batch * s.kwords;
-    hipLaunchKernelGGL(sim_msg_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, msgw, s.kwords, s0.k, seed, first_frame, batch, (s.gt || parw) ? 0 : 1);
+    if (!msgw_ready)
+        hipLaunchKernelGGL(sim_msg_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, msgw, s.kwords, s0.k, seed, first_frame, batch, (s.gt || parw) ? 0 : 1);
     if (sy) {
         int rc = sim_systematic_codeword(*sy, msgw, s.kwords, parw, st, batch);
         if (rc == LDPC_OK && d_msg0) rc = sim_systematic_msg_bytes(msgw, s.kwords, s0.k, d_msg0, st, batch);
@@ -281,6 +399,17 @@ int sim_generate(const SimDev &s0, const SimSparse *sp, const SimSys *sy, uint32
             default: return set_error(LDPC_EUNSUPPORTED, "quasi-cyclic encoder: circulant size %d", 32 * s.qc_w);
         }
 #undef LDPC_QC_PARITY
+    }
+    if (out_fmt == 3) {   // packed codewords straight from the packed message and parity words (k = 0, systematic form: from the codeword words)
+        if (!parw) return set_error(LDPC_EUNSUPPORTED, "sim_generate: packed codewords need packed parity words");
+        const int cwords = (s.n_tx + 31) / 32, PB = (s.n_tx + 7) / 8;
+        const size_t total = (size_t)batch * cwords;
+        const int words_ok = (PB % 4 == 0) && ((uintptr_t)d_out % 4 == 0);
+        hipLaunchKernelGGL(sim_pack_codeword_kernel, dim3(sim_grid(total)), dim3(256), 0, st, msgw, parw, (uint8_t *)d_out, s.k, s.n_tx, s.kwords, s.pwords, cwords, PB,
+                           words_ok, total);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return set_error(LDPC_EHIP, "sim_generate: %s", hipGetErrorString(e));
+        return LDPC_OK;
     }
     const int groups = ((out_fmt == 2 ? s.n_tx : s.N) + 3) / 4;
     const dim3 grid((groups + 255) / 256, batch);

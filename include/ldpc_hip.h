@@ -438,6 +438,33 @@ int ldpc_sim_generate(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int ba
  * to nearest even) for ldpc_decode_batch_dev_f16 */
 int ldpc_sim_generate_f16(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db,
                           uint16_t *d_llr, uint8_t *d_msg, void *stream);
+/* ---- the caller's own messages.  Two layouts of bits in device memory:
+ *   LDPC_BITS_BYTES   one byte per bit.  Input: only bit 0 of a byte is read; output: bytes are 0 or 1.  Messages [batch][k],
+ *                     codewords [batch][n_tx] (what ldpc_sim_encode_batch writes).
+ *   LDPC_BITS_PACKED  bit i of a row in byte i / 8 at bit i % 8 (the layout of ldpc_decode_batch_packed; read as little-endian
+ *                     32-bit words, the library's own message words).  Message rows are 4 * ceil(k / 32) bytes -- whole words,
+ *                     4-byte aligned (LDPC_EINVAL otherwise); bits >= k of the last word are ignored on input and 0 on output.
+ *                     Codeword rows are ceil(n_tx / 8) bytes, any alignment; the pad bits of the last byte are written as 0.
+ * Messages are in msg_pos order (ldpc_sim_positions): positions 0..k-1, but for LDPC_ENCODER_SYSTEMATIC.  All three functions take
+ * device pointers, enqueue on `stream` and do not synchronise; inputs and outputs must not overlap; 1 <= batch <= max_batch.
+ * LDPC_EINVAL: a null pointer, such a batch, an unknown format.  No counterpart in the reference. */
+enum ldpc_bit_format { LDPC_BITS_BYTES = 0, LDPC_BITS_PACKED = 1 };
+/* the encoder alone on the caller's messages: the codewords, cut at n_tx, that ldpc_sim_encode_batch would write had it drawn
+ * these messages.  LDPC_EUNSUPPORTED on a source with LDPC_ENCODER_NONE (msg ++ zeros is not a codeword).  Packed codewords
+ * come straight from the packed message and parity words for LDPC_ENCODER_QC, _SPARSE and _SYSTEMATIC; LDPC_ENCODER_DENSE writes
+ * bytes into a staging buffer of max_batch * n_tx bytes inside `sim`, allocated by the first such call (a device allocation: that one
+ * call may wait for the device), and a second kernel packs them: n_tx bytes written and read again per frame. */
+int ldpc_sim_encode_messages(ldpc_sim *sim, int batch, const void *d_msg, int msg_fmt, void *d_codewords, int cw_fmt, void *stream);
+/* the frames of ldpc_sim_generate (llr_f16 = 0: float32 LLRs [batch][N]) or ldpc_sim_generate_f16 (llr_f16 = 1) with the caller's
+ * messages in place of the drawn ones: the noise of frame first_frame + f is the same stream of (seed, frame) -- it never
+ * depended on the message -- sigma comes from R = k / n_tx, positions >= n_tx get LLR 0.  Given exactly the messages
+ * ldpc_sim_generate would draw, the LLRs are bit for bit those of ldpc_sim_generate.  LDPC_EUNSUPPORTED as above.  After this
+ * call, and after ldpc_sim_encode_messages, the caller's messages are what ldpc_sim_tally compares against. */
+int ldpc_sim_generate_from(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg, int msg_fmt,
+                           void *d_llr, int llr_f16, void *stream);
+/* the receive side: message bit i of a frame = decoded bit msg_pos[i] of d_bits [batch][N] bytes (bit 0 of each), written in
+ * msg_fmt.  With the systematic form message and parity bits interleave; any source qualifies, LDPC_ENCODER_NONE included. */
+int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream);
 /* d_tally[4] (device, uint64) += {frames, frame errors, message-bit errors, sum of iterations}
  * for the frames of the last ldpc_sim_generate call; d_iters may be NULL. */
 int ldpc_sim_tally(ldpc_sim *sim, int batch, const uint8_t *d_bits, const int32_t *d_iters,

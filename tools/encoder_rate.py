@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
+"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only | --messages caller] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
 sim.hip sim_parity_qc_kernel) against the dense packed GF(2) mat-vec of the expanded generator (Orig.hs:25-26), on the shipped AR4JA
 codes: the encoder alone (ldpc_sim_encode_batch: messages + parity -> codeword bytes) and the whole frame source
 (ldpc_sim_generate: + BPSK, AWGN, LLRs).  HIP events on the launch stream, median of 7.
@@ -9,7 +9,11 @@ loop is at most doubled while generate costs no more than it -- the fp16-lam lay
 median of 5.  --sparse-only: only that part.
 --systematic-only: the encoder from ANY H (sim_systematic.hip, Sim(systematic=True)): on jpl.4096.4.5 next to the dense encoder of the
 expanded generator (the same K x r product) and the quasi-cyclic one, codewords compared on the device and their SHA-256 printed; then on
-codes/1920.1280.3.303 (no generator, not accumulator-shaped) generate against the fp16-lam layered decode of the same frames at 2 dB."""
+codes/1920.1280.3.303 (no generator, not accumulator-shaped) generate against the fp16-lam layered decode of the same frames at 2 dB.
+--messages caller: the caller's own messages (ldpc_sim_encode_messages) on the quasi-cyclic source of jpl.4096.4.5, the systematic form of
+codes/1920.1280.3.303 (both [frames], default 65 536) and the encoder from H of tests/dvbs2_short.py (a quarter of that): bytes -> bytes and
+packed -> packed next to ldpc_sim_encode_batch on the same source and batch and a device-to-device copy of batch * k bytes.  One warm-up,
+median of 5.  The bar: bytes -> bytes <= encode_batch + 2 x that copy."""
 import os
 import sys
 
@@ -164,13 +168,75 @@ def systematic_leg(B, dev, st):
     dec.close(); sim.close(); plain.close(); code.close()
 
 
+def caller_leg(B, dev, st):
+    from tests import dvbs2_short
+    from tests.helpers import load
+
+    def qc():
+        ecc = E.ECC(os.path.join(ROOT, "codes"), "ldpc/hip-minsum/jpl.4096.4.5/50/4/5", max_batch=B)
+        return ecc.sim, ecc.codeword_length, B, [ecc]
+
+    def systematic():
+        m = load("1920.1280.3.303")
+        code = E.Code.from_csr(m.graph.row_ptr, m.graph.col_idx, m.N)
+        return E.Sim(code, None, m.N, systematic=True, max_batch=B), m.N, B, [code]
+
+    def sparse():
+        Bs = max(1, B // 4)
+        code = E.Code.from_csr(*dvbs2_short.csr(), dvbs2_short.N)
+        return E.Sim(code, dvbs2_short.K, dvbs2_short.N, from_H=True, max_batch=Bs), dvbs2_short.N, Bs, [code]
+
+    print(f"{'source':34s} {'frames':>7s} {'bytes->bytes':>13s} {'packed->packed':>15s} {'encode_batch':>13s} {'copy batch*k B':>15s} {'bar':>9s}  (ms, median of 5)")
+    for label, make in (("qc jpl.4096.4.5", qc), ("systematic 1920.1280.3.303", systematic), ("sparse dvbs2-short", sparse)):
+        sim, n_tx, b, owners = make()
+        k = sim.k
+        kb, pb = 4 * ((k + 31) // 32), (n_tx + 7) // 8
+        msg = torch.empty((b, k), dtype=torch.uint8, device=dev)
+        cw = torch.empty((b, n_tx), dtype=torch.uint8, device=dev)
+        cw2 = torch.empty((b, n_tx), dtype=torch.uint8, device=dev)
+        sim.encode_batch(1, 0, b, cw.data_ptr(), msg.data_ptr(), st.cuda_stream)      # the messages it draws: the same work for every leg
+        w = torch.arange(8, device=dev, dtype=torch.int32)
+        pmsg = torch.zeros((b, kb), dtype=torch.uint8, device=dev)
+        bits = torch.nn.functional.pad(msg, (0, 8 * kb - k)).view(b, kb, 8).to(torch.int32)
+        pmsg.copy_((bits << w).sum(-1).to(torch.uint8))
+        pcw = torch.empty((b, pb), dtype=torch.uint8, device=dev)
+        dst = torch.empty_like(msg)
+        torch.cuda.synchronize()
+        t_bb = timed(lambda: sim.encode_messages(b, msg.data_ptr(), cw2.data_ptr(), "bytes", "bytes", st.cuda_stream), st, 5)
+        t_pp = timed(lambda: sim.encode_messages(b, pmsg.data_ptr(), pcw.data_ptr(), "packed", "packed", st.cuda_stream), st, 5)
+        t_enc = timed(lambda: sim.encode_batch(1, 0, b, cw.data_ptr(), None, st.cuda_stream), st, 5)
+        t_cp = timed(lambda: dst.copy_(msg), st, 5)
+        assert torch.equal(cw, cw2), "encode_messages and encode_batch disagree on the same messages"
+        cbits = torch.nn.functional.pad(cw, (0, 8 * pb - n_tx)).view(b, pb, 8).to(torch.int32)
+        assert torch.equal(pcw, (cbits << w).sum(-1).to(torch.uint8)), "packed codewords differ from the packed bytes"
+        bar = t_enc + 2 * t_cp
+        print(f"{label:34s} {b:7d} {t_bb:13.3f} {t_pp:15.3f} {t_enc:13.3f} {t_cp:15.3f} {bar:9.3f}  bytes->bytes {'within' if t_bb <= bar else 'MISSES'} the bar"
+              f" (encode_batch + 2 copies); packed->packed / bytes->bytes = {t_pp / t_bb:.3f}", flush=True)
+        sim.close()
+        for o in owners:
+            o.close()
+        del msg, cw, cw2, pmsg, pcw, dst, bits, cbits
+        torch.cuda.empty_cache()
+
+
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    argv = sys.argv[1:]
+    messages = None
+    if "--messages" in argv:
+        i = argv.index("--messages")
+        messages = argv[i + 1] if i + 1 < len(argv) else ""
+        del argv[i:i + 2]
+        if messages != "caller":
+            sys.exit("--messages takes one value: caller")
+    args = [a for a in argv if not a.startswith("--")]
     B = int(args[0]) if args else 65536
     E.init(0)
     dev = torch.device("cuda", 0)
     st = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(st)
+    if messages:
+        caller_leg(B, dev, st)
+        return
     if "--systematic-only" in sys.argv:
         systematic_leg(B, dev, st)
         return
