@@ -20,6 +20,8 @@ PATH_AUTO, PATH_FLOOD, PATH_FUSED = 0, 1, 2
 SCHED_FLOODING, SCHED_LAYERED = 0, 1
 SUM_REFERENCE, SUM_ARRAYLET, SUM_SPARSE = 0, 1, 2
 BITS_BYTES, BITS_PACKED = 0, 1   # ldpc_bit_format
+MOD_BPSK, MOD_QPSK, MOD_8PSK, MOD_16QAM = 1, 2, 3, 4
+LLR_F32, LLR_F16, LLR_I8 = 0, 1, 2   # LDPC_LLR_*: the output formats of the demapper
 
 
 class CtxConfig(C.Structure):   # ldpc_ctx_config
@@ -44,6 +46,8 @@ ABI_SYMBOLS = [
     "ldpc_csr_triangular_order", "ldpc_sim_create_sparse_on",
     "ldpc_csr_systematic_form", "ldpc_sim_create_systematic_on", "ldpc_sim_message_length", "ldpc_sim_positions",
     "ldpc_sim_encode_messages", "ldpc_sim_generate_from", "ldpc_sim_extract_messages",
+    "ldpc_modulation_create", "ldpc_modulation_create_builtin", "ldpc_modulation_destroy", "ldpc_modulation_bits", "ldpc_modulation_points", "ldpc_modulation_energy",
+    "ldpc_modulation_symbols", "ldpc_demap_dev", "ldpc_sim_noise_var", "ldpc_sim_transmit", "ldpc_sim_generate_mod",
     "ldpc_matrix_load", "ldpc_matrix_load_mackay", "ldpc_matrix_destroy", "ldpc_matrix_info", "ldpc_matrix_dense",
     "ldpc_matrix_qc_offsets", "ldpc_code_from_matrix",
     "ldpc_ecc_create", "ldpc_ecc_destroy", "ldpc_ecc_name", "ldpc_ecc_message_length", "ldpc_ecc_codeword_length",
@@ -66,7 +70,7 @@ _lib = None
 # the interpreter is finalising, __del__ does nothing: no hipFree / hipStreamDestroy ever runs from a finaliser during
 # shutdown, when the order against the HIP runtime's own exit handlers is not defined.
 _live = weakref.WeakSet()
-_CLOSE_ORDER = {"ECC": 0, "Batcher": 1, "Decoder": 2, "Sim": 3, "Code": 4, "Matrix": 5, "PinnedArray": 6}
+_CLOSE_ORDER = {"ECC": 0, "Batcher": 1, "Decoder": 2, "Sim": 3, "Code": 4, "Matrix": 5, "PinnedArray": 6, "Modulation": 7}
 _closed_all = False
 
 
@@ -233,6 +237,22 @@ def lib():
     L.ldpc_sim_encode_messages.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]
     L.ldpc_sim_generate_from.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, vp]
     L.ldpc_sim_extract_messages.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
+    L.ldpc_modulation_create.restype = vp
+    L.ldpc_modulation_create.argtypes = [C.c_int, C.POINTER(C.c_float)]
+    L.ldpc_modulation_create_builtin.restype = vp
+    L.ldpc_modulation_create_builtin.argtypes = [C.c_int]
+    L.ldpc_modulation_destroy.restype = None
+    L.ldpc_modulation_destroy.argtypes = [vp]
+    L.ldpc_modulation_bits.argtypes = [vp]
+    L.ldpc_modulation_points.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ldpc_modulation_energy.restype = C.c_double
+    L.ldpc_modulation_energy.argtypes = [vp]
+    L.ldpc_modulation_symbols.argtypes = [vp, C.c_int]
+    L.ldpc_demap_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, C.c_int, C.c_float, vp]
+    L.ldpc_sim_noise_var.restype = C.c_double
+    L.ldpc_sim_noise_var.argtypes = [vp, vp, C.c_double]
+    L.ldpc_sim_transmit.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp]
+    L.ldpc_sim_generate_mod.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, C.c_float, vp, vp]
     L.ldpc_matrix_qc_words.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.ldpc_matrix_rank.argtypes = [vp]
     L.ldpc_matrix_load.restype = vp
@@ -741,6 +761,72 @@ class Matrix:
             pass
 
 
+def _llr_fmt(fmt):
+    """"f32" / "f16" / "i8" (or the integer LDPC_LLR_*, passed through for the library to judge)"""
+    return {"f32": LLR_F32, "f16": LLR_F16, "i8": LLR_I8}[fmt] if isinstance(fmt, str) else int(fmt)
+
+
+class Modulation:
+    """A labelled constellation (ldpc_modulation): points [2^m][2] float32 (I, Q), m = 1..6, or a built-in by name.  Symbol s of a
+    frame carries codeword bits m s .. m s + m - 1, the first one the MSB of the label = the index into the table."""
+
+    BUILTIN = {"bpsk": MOD_BPSK, "qpsk": MOD_QPSK, "8psk": MOD_8PSK, "16qam": MOD_16QAM}
+
+    def __init__(self, points):
+        if isinstance(points, str):
+            h = lib().ldpc_modulation_create_builtin(self.BUILTIN.get(points.lower(), -1))
+        elif isinstance(points, int):
+            h = lib().ldpc_modulation_create_builtin(points)
+        else:
+            pts = np.ascontiguousarray(points, np.float32)
+            n = pts.shape[0] if pts.ndim == 2 and pts.shape[1] == 2 else 0
+            m = n.bit_length() - 1
+            if n < 2 or n != 1 << m:
+                raise LdpcError(EINVAL, "Modulation: points must be [2^m][2]")
+            h = lib().ldpc_modulation_create(m, ptr(pts, C.c_float))
+        if not h:
+            raise LdpcError(lib().ldpc_last_error_code(), last_error())
+        self._h = h
+        self.bits = int(lib().ldpc_modulation_bits(h))
+        _register(self)
+
+    @property
+    def points(self):
+        out = np.zeros((1 << self.bits, 2), np.float32)
+        assert lib().ldpc_modulation_points(self._h, ptr(out, C.c_float)) == 1 << self.bits
+        return out
+
+    @property
+    def energy(self):
+        return float(lib().ldpc_modulation_energy(self._h))
+
+    def symbols(self, n_tx):
+        n = lib().ldpc_modulation_symbols(self._h, int(n_tx))
+        if n < 0:
+            raise LdpcError(n, last_error())
+        return n
+
+    def close(self):
+        if self._h:
+            lib().ldpc_modulation_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        if _finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def demap(mod: Modulation, batch, n_tx, N, d_sym_ptr, noise_var, d_llr_ptr, llr_fmt="f32", qscale=0.0, stream=None):
+    """ldpc_demap_dev: samples [batch][ceil(n_tx / m)][2] float32 -> max-log LLRs [batch][N] in llr_fmt ("f32", "f16", "i8"), on the
+    calling thread's device"""
+    check(lib().ldpc_demap_dev(mod._h if mod is not None else None, int(batch), int(n_tx), int(N), d_sym_ptr, float(noise_var), d_llr_ptr, _llr_fmt(llr_fmt),
+                               float(qscale), stream))
+
+
 class Sim:
     """Device-side frame source + error tally (ldpc_sim)."""
 
@@ -820,6 +906,21 @@ class Sim:
     def extract_messages(self, batch, d_bits_ptr, d_msg_ptr, msg_fmt="bytes", stream=None):
         """decoded bytes [batch][N] -> the messages (bit i = decoded bit positions()[0][i]) in msg_fmt"""
         check(lib().ldpc_sim_extract_messages(self._h, int(batch), d_bits_ptr, d_msg_ptr, self._bits_fmt(msg_fmt), stream))
+
+    def noise_var(self, mod: "Modulation", ebn0_db):
+        """sigma^2 per real dimension at Eb/N0 (dB) for this source's rate and that constellation (ldpc_sim_noise_var)"""
+        return float(lib().ldpc_sim_noise_var(self._h, mod._h if mod is not None else None, float(ebn0_db)))
+
+    def transmit(self, mod: "Modulation", seed, first_frame, batch, ebn0_db, d_sym_ptr, d_msg_in_ptr=None, msg_fmt="bytes", d_msg_ptr=None, stream=None):
+        """the noisy symbols [batch][mod.symbols(n_tx)][2] float32 of the drawn messages (d_msg_in_ptr None) or the caller's"""
+        check(lib().ldpc_sim_transmit(self._h, mod._h if mod is not None else None, int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_in_ptr,
+                                      self._bits_fmt(msg_fmt), d_sym_ptr, d_msg_ptr, stream))
+
+    def generate_mod(self, mod: "Modulation", seed, first_frame, batch, ebn0_db, d_llr_ptr, llr_fmt="f32", qscale=0.0, d_msg_in_ptr=None, msg_fmt="bytes", d_msg_ptr=None,
+                     stream=None):
+        """transmit() and demap() in one kernel: LLRs [batch][N] in llr_fmt ("f32", "f16", "i8")"""
+        check(lib().ldpc_sim_generate_mod(self._h, mod._h if mod is not None else None, int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_in_ptr,
+                                          self._bits_fmt(msg_fmt), d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), d_msg_ptr, stream))
 
     def tally(self, batch, d_bits_ptr, d_iters_ptr, d_tally_ptr, stream=None):
         check(lib().ldpc_sim_tally(self._h, int(batch), d_bits_ptr, d_iters_ptr, d_tally_ptr, stream))

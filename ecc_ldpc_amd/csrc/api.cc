@@ -12,6 +12,7 @@
 #include <set>
 
 #include "backend.h"
+#include "demap.h"
 #include "jit.h"
 #include "sim.h"
 #include "systematic.h"
@@ -1029,6 +1030,8 @@ struct ldpc_sim {
     int32_t *d_msg_pos = nullptr;
     // dense source, packed codewords (ldpc_sim_encode_messages): codeword bytes [max_batch][n_tx] for pack_bits, allocated on first use
     uint8_t *d_stage = nullptr;
+    // modulated path (ldpc_sim_transmit, ldpc_sim_generate_mod): packed codewords [max_batch][ceil(n_tx / 8)], allocated on first use
+    uint8_t *d_cw = nullptr;
 };
 extern "C" {
 
@@ -1044,6 +1047,7 @@ void ldpc_sim_destroy(ldpc_sim *sim) {
     hipFree(sim->d_gwin);
     hipFree(sim->d_msg_pos);
     hipFree(sim->d_stage);
+    hipFree(sim->d_cw);
     delete sim;
 }
 
@@ -1324,6 +1328,103 @@ int ldpc_sim_generate_from(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, i
     if ((rc = sim_load("ldpc_sim_generate_from", sim, batch, d_msg, msg_fmt, stream)) != LDPC_OK) return rc;
     return ldpc::sim_generate(sim->dev, sim->sparse ? &sim->sp : nullptr, sim->systematic ? &sim->sy : nullptr, sim->d_msgw, sim->d_parw, (hipStream_t)stream, seed,
                               first_frame, batch, ebn0_db, d_llr, llr_f16, nullptr, true);
+}
+
+// ---- higher-order modulation: the stand-alone demapper and the frame source's modulated path (csrc/demap.hip, csrc/sim_mod.hip)
+static int check_llr_out(const char *what, int llr_fmt, float qscale) {
+    if (llr_fmt != LDPC_LLR_F32 && llr_fmt != LDPC_LLR_F16 && llr_fmt != LDPC_LLR_I8)
+        return set_error(LDPC_EINVAL, "%s: unknown LLR format %d (LDPC_LLR_F32 = 0, LDPC_LLR_F16 = 1, LDPC_LLR_I8 = 2)", what, llr_fmt);
+    if (!(qscale >= 0.f) || !std::isfinite(qscale)) return set_error(LDPC_EINVAL, "%s: qscale must be finite and >= 0 (0 = 4.0)", what);
+    return LDPC_OK;
+}
+
+int ldpc_demap_dev(const ldpc_modulation *mod, int batch, int n_tx, int N, const float *d_sym, double noise_var, void *d_llr, int llr_fmt, float qscale, void *stream) {
+    if (!mod || !d_sym || !d_llr) return set_error(LDPC_EINVAL, "ldpc_demap_dev: null argument");
+    if (batch <= 0 || n_tx <= 0 || n_tx > N) return set_error(LDPC_EINVAL, "ldpc_demap_dev: bad dimensions (batch=%d n_tx=%d N=%d)", batch, n_tx, N);
+    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "ldpc_demap_dev: noise_var must be finite and > 0");
+    const int rc = check_llr_out("ldpc_demap_dev", llr_fmt, qscale);
+    if (rc != LDPC_OK) return rc;
+    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_llr % (llr_fmt == LDPC_LLR_F32 ? 4 : llr_fmt == LDPC_LLR_F16 ? 2 : 1) != 0)
+        return set_error(LDPC_EINVAL, "ldpc_demap_dev: samples must be 8-byte aligned and LLRs aligned to their element");
+    const float inv = (float)(1.0 / (2.0 * noise_var));
+    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
+    const int device = current_device();
+    if (device < 0) return set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded");
+    HIPCHK(hipSetDevice(device));
+    return ldpc::demap_launch((hipStream_t)stream, mod->tab, mod->m, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+}
+
+double ldpc_sim_noise_var(const ldpc_sim *sim, const ldpc_modulation *mod, double ebn0_db) {
+    if (!sim || !mod) { set_error(LDPC_EINVAL, "ldpc_sim_noise_var: null argument"); return 0.0; }
+    const double R = (double)sim->dev.k / (double)sim->dev.n_tx;
+    return mod->es / (2.0 * R * (double)mod->m * pow(10.0, ebn0_db / 10.0));
+}
+
+// the codewords of the batch, packed, in sim->d_cw: the drawn messages (d_msg_in null) or the caller's
+static int sim_mod_codewords(const char *what, ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, const void *d_msg_in, int msg_fmt, uint8_t *d_msg, hipStream_t st) {
+    const int n_tx = sim->dev.n_tx, PB = (n_tx + 7) / 8;
+    if (!sim->d_cw) {
+        hipError_t e = hipMalloc((void **)&sim->d_cw, (size_t)sim->max_batch * PB);
+        if (e != hipSuccess) { sim->d_cw = nullptr; return set_error(LDPC_EHIP, "%s: codeword buffer: %s", what, hipGetErrorString(e)); }
+    }
+    int rc;
+    if (d_msg_in && (rc = sim_load(what, sim, batch, d_msg_in, msg_fmt, st)) != LDPC_OK) return rc;
+    const ldpc::SimSparse *sp = sim->sparse ? &sim->sp : nullptr;
+    const ldpc::SimSys *sy = sim->systematic ? &sim->sy : nullptr;
+    if (sim->d_parw) {   // quasi-cyclic, from H, systematic form: packed straight from the message and parity words
+        rc = ldpc::sim_generate(sim->dev, sp, sy, sim->d_msgw, sim->d_parw, st, seed, first_frame, batch, 0.0, sim->d_cw, 3, d_msg, d_msg_in != nullptr);
+        if (rc == LDPC_OK && d_msg && !sy) rc = ldpc::sim_systematic_msg_bytes(sim->d_msgw, sim->dev.kwords, sim->dev.k, d_msg, st, batch);   // (the message words unpacked)
+        return rc;
+    }
+    // dense generator, or none (all-zero codewords): the frame kernel writes bytes; pack those
+    if (!sim->d_stage) {
+        hipError_t e = hipMalloc((void **)&sim->d_stage, (size_t)sim->max_batch * n_tx);
+        if (e != hipSuccess) { sim->d_stage = nullptr; return set_error(LDPC_EHIP, "%s: staging buffer: %s", what, hipGetErrorString(e)); }
+    }
+    rc = ldpc::sim_generate(sim->dev, sp, sy, sim->d_msgw, sim->d_parw, st, seed, first_frame, batch, 0.0, sim->d_stage, 2, d_msg, d_msg_in != nullptr);
+    if (rc != LDPC_OK) return rc;
+    return ldpc::pack_bits(st, sim->d_stage, sim->d_cw, batch, n_tx);
+}
+
+static int sim_mod_check(const char *what, const ldpc_sim *sim, const ldpc_modulation *mod, int batch, const void *d_msg_in, int msg_fmt, const void *d_out) {
+    if (!sim || !mod || !d_out) return set_error(LDPC_EINVAL, "%s: null argument", what);
+    if (batch <= 0 || batch > sim->max_batch) return set_error(LDPC_EINVAL, "%s: batch %d outside 1..%d", what, batch, sim->max_batch);
+    if (d_msg_in) {
+        if (msg_fmt != LDPC_BITS_BYTES && msg_fmt != LDPC_BITS_PACKED) return set_error(LDPC_EINVAL, "%s: unknown bit format (LDPC_BITS_BYTES = 0, LDPC_BITS_PACKED = 1)", what);
+        if (ldpc_sim_encoder(sim) == LDPC_ENCODER_NONE)
+            return set_error(LDPC_EUNSUPPORTED, "%s: this frame source has no encoder (msg ++ zeros is not a codeword); create it with a generator or from H", what);
+    }
+    return LDPC_OK;
+}
+
+int ldpc_sim_transmit(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg_in, int msg_fmt,
+                      float *d_sym, uint8_t *d_msg, void *stream) {
+    int rc = sim_mod_check("ldpc_sim_transmit", sim, mod, batch, d_msg_in, msg_fmt, d_sym);
+    if (rc != LDPC_OK) return rc;
+    if ((uintptr_t)d_sym % 8 != 0) return set_error(LDPC_EINVAL, "ldpc_sim_transmit: samples must be 8-byte aligned");
+    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
+    if (!(nv >= 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_transmit: Eb/N0 gives no finite noise variance");
+    HIPCHK(hipSetDevice(sim->device));
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = sim_mod_codewords("ldpc_sim_transmit", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
+    return ldpc::mod_transmit_launch(st, mod->tab, mod->m, batch, sim->dev.n_tx, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv), d_sym);
+}
+
+int ldpc_sim_generate_mod(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg_in, int msg_fmt,
+                          void *d_llr, int llr_fmt, float qscale, uint8_t *d_msg, void *stream) {
+    int rc = sim_mod_check("ldpc_sim_generate_mod", sim, mod, batch, d_msg_in, msg_fmt, d_llr);
+    if (rc != LDPC_OK) return rc;
+    if ((rc = check_llr_out("ldpc_sim_generate_mod", llr_fmt, qscale)) != LDPC_OK) return rc;
+    if ((uintptr_t)d_llr % (llr_fmt == LDPC_LLR_F32 ? 4 : llr_fmt == LDPC_LLR_F16 ? 2 : 1) != 0) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod: LLRs must be aligned to their element");
+    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
+    if (!(nv > 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod: Eb/N0 gives no finite noise variance > 0");
+    const float inv = (float)(1.0 / (2.0 * nv));
+    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod: 1 / (2 sigma^2) does not fit a float32 at %g dB", ebn0_db);
+    HIPCHK(hipSetDevice(sim->device));
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = sim_mod_codewords("ldpc_sim_generate_mod", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
+    return ldpc::mod_generate_launch(st, mod->tab, mod->m, batch, sim->dev.n_tx, sim->dev.N, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv),
+                                     inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
 }
 
 int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream) {

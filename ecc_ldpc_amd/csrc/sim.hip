@@ -14,36 +14,17 @@
 //   (Utils.hs:55 `unpuncture`).
 // Randomness: Philox4x32-10 keyed by the 64-bit seed, counter = (global frame id, index / 4, stream),
 // so a frame's content depends only on (seed, frame id): ranks generate disjoint frame ranges
-// with no scatter.
+// with no scatter.  Philox and the Box-Muller step live in sim_noise.h, shared with the modulated path (sim_mod.hip: any
+// constellation of 2..64 points, complex AWGN on stream 2, max-log LLRs).
 // The message words may also come from the caller (sim_load_messages: bytes or packed bits -> msgw; sim_generate then skips the draw and
 // Philox keys the noise alone), and the codewords may leave packed (sim_pack_codeword_kernel); sim_extract_messages is the way back.
 #include "internal.h"
 #include "sim.h"
+#include "sim_noise.h"
 #include <hip/hip_fp16.h>
 #include <algorithm>
 
 namespace ldpc {
-
-struct Philox {
-    static __device__ __forceinline__ void round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-        const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-        uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-        uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-        uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    }
-    static __device__ __forceinline__ void gen(uint64_t seed, uint64_t frame, uint32_t idx, uint32_t stream, uint32_t (&out)[4]) {
-        uint32_t c[4] = {(uint32_t)frame, (uint32_t)(frame >> 32), idx, stream};
-        uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-        for (int r = 0; r < 10; r++) {
-            round(c, k0, k1);
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
-    }
-};
 
 // message words: msgw[frame][w], bit i of word w = message bit 32*w + i
 __global__ void sim_msg_kernel(uint32_t *msgw, int kwords, int k, uint64_t seed, uint64_t first_frame, int batch, int zero_msg) {
@@ -154,14 +135,7 @@ __global__ __launch_bounds__(256) void sim_frame_kernel(SimDev s, const uint32_t
     if (!kBytes && n0 < s.n_tx) {
         uint32_t r[4];
         Philox::gen(seed, first_frame + f, (uint32_t)g, 1u, r);
-        // Box-Muller on two 32-bit uniforms (u1 in (0,1]); both branches of each pair are used
-        const float ua = ((float)r[0] + 1.0f) * 2.3283064365386963e-10f, ub = (float)r[1] * 2.3283064365386963e-10f;
-        const float uc = ((float)r[2] + 1.0f) * 2.3283064365386963e-10f, ud = (float)r[3] * 2.3283064365386963e-10f;
-        const float ra = sqrtf(-2.0f * logf(ua)), rc = sqrtf(-2.0f * logf(uc));
-        float sa, ca, sc, cc;
-        sincospif(2.0f * ub, &sa, &ca);
-        sincospif(2.0f * ud, &sc, &cc);
-        z[0] = ra * ca; z[1] = ra * sa; z[2] = rc * cc; z[3] = rc * sc;
+        box_muller4(r, z);   // (sim_noise.h)
     }
     // parity bits of the group: bit j = <msg, column j of G> over GF(2); a group that lies inside the parity part
     // on a 4-aligned column reads its four columns with one 16-byte load per message word

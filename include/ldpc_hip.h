@@ -462,6 +462,64 @@ int ldpc_sim_encode_messages(ldpc_sim *sim, int batch, const void *d_msg, int ms
  * call, and after ldpc_sim_encode_messages, the caller's messages are what ldpc_sim_tally compares against. */
 int ldpc_sim_generate_from(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg, int msg_fmt,
                            void *d_llr, int llr_f16, void *stream);
+/* ---- higher-order modulation: a labelled constellation, a max-log soft demapper, and the frame source's modulated path.
+ * Modulation object (host only): 2^m points (I, Q), m = 1..6 bits per symbol.  LABELLING: symbol s of a frame carries codeword bits
+ * m s .. m s + m - 1; its label is sum_j bit(m s + j) << (m - 1 - j) -- the first bit is the MSB -- and the label is the index into
+ * `points`.  Bits at positions >= n_tx pad as 0.  There is no bit interleaver: a caller permutes.  Two equal points are allowed.
+ * LDPC_EINVAL and NULL for m outside 1..6, a null table or a non-finite point.
+ * Built-ins, by formula (NO claim is made that these are any standard's labellings or, for APSK, ring ratios -- a caller who needs a
+ * standard's constellation passes its own table):
+ *   LDPC_MOD_BPSK   bit b -> (2b - 1, 0): LLR > 0 <=> bit 1, as everywhere in this library
+ *   LDPC_MOD_QPSK   (b0, b1) -> ((2 b0 - 1), (2 b1 - 1)) / sqrt 2: Gray
+ *   LDPC_MOD_8PSK   unit circle, the point at angle k pi / 4 carries label k ^ (k >> 1): Gray around the circle
+ *   LDPC_MOD_16QAM  (b0 b1 | b2 b3) -> (L[b0 b1], L[b2 b3]) / sqrt 10, L: 00 01 11 10 -> -3 -1 +1 +3: Gray per axis, unit energy */
+typedef struct ldpc_modulation ldpc_modulation;
+enum { LDPC_MOD_BPSK = 1, LDPC_MOD_QPSK = 2, LDPC_MOD_8PSK = 3, LDPC_MOD_16QAM = 4 };
+ldpc_modulation *ldpc_modulation_create(int bits_per_symbol /* m, 1..6 */, const float *points /* [2^m][2]: I, Q */);
+ldpc_modulation *ldpc_modulation_create_builtin(int kind);
+void ldpc_modulation_destroy(ldpc_modulation *mod);
+int ldpc_modulation_bits(const ldpc_modulation *mod);                /* m */
+int ldpc_modulation_points(const ldpc_modulation *mod, float *out);  /* [2^m][2] (out may be NULL); returns 2^m */
+double ldpc_modulation_energy(const ldpc_modulation *mod);           /* Es = mean |c|^2, accumulated in double in index order */
+int ldpc_modulation_symbols(const ldpc_modulation *mod, int n_tx);   /* symbols per frame: ceil(n_tx / m) */
+/* Max-log soft demapper on the device: d_sym [batch][n_sym][2] float32 I/Q samples (8-byte aligned), n_sym = ceil(n_tx / m) ->
+ * d_llr [batch][N] in one of the decoders' input formats, one pass.  For a sample y and every point c_p:
+ *   d_p = |y - c_p|^2;  LLR_j = (min over labels with bit j = 0 of d_p  -  min over labels with bit j = 1 of d_p) / (2 noise_var)
+ * in float32, operation by operation as tests/modulation_spec.py states it (the kernel reproduces that bit for bit).  noise_var is
+ * sigma^2 per real dimension, finite and > 0, and 1 / (2 noise_var) must fit a float32 (noise_var above about 1.5e-39; LDPC_EINVAL
+ * otherwise).  Positions n_tx .. N-1 are written as 0; LLRs of pad bits are not written.
+ *   LDPC_LLR_F32  the value;  LDPC_LLR_F16  clamped to +-65504, rounded to nearest even (what ldpc_sim_generate_f16 does);
+ *   LDPC_LLR_I8   clip(rint(LLR * qscale), -127, 127), NaN -> 0: the quantiser of an LDPC_I8 context with llr_qscale = qscale, so
+ *                 ldpc_decode_batch_dev_i8 decodes these bytes as ldpc_decode_batch_dev would have quantised the floats.  qscale is
+ *                 read for LDPC_LLR_I8 only; 0 = 4.0; negative or non-finite: LDPC_EINVAL.
+ * A NaN sample gives NaN LLRs (int8: 0, an erasure).  Runs on the calling thread's device, enqueued on `stream`, not synchronised.
+ * LDPC_EINVAL: a null pointer, batch <= 0, n_tx <= 0 or > N, an unknown format, such a noise_var or qscale, a misaligned buffer.
+ * Exact log-MAP, interleavers and fp16 samples are not provided. */
+enum { LDPC_LLR_F32 = 0, LDPC_LLR_F16 = 1, LDPC_LLR_I8 = 2 };   /* the values llr_f16 takes in the packed entry points */
+int ldpc_demap_dev(const ldpc_modulation *mod, int batch, int n_tx, int N, const float *d_sym, double noise_var, void *d_llr, int llr_fmt,
+                   float qscale, void *stream);
+/* The frame source's modulated path.  sigma^2 per real dimension = Es / (2 R m 10^(dB/10)), R = k / n_tx, in double (for
+ * LDPC_MOD_BPSK: the formula of ldpc_sim_generate). */
+double ldpc_sim_noise_var(const ldpc_sim *sim, const ldpc_modulation *mod, double ebn0_db);
+/* frames [first_frame, first_frame + batch): the codewords of the drawn messages (d_msg_in NULL; those of ldpc_sim_generate) or of
+ * the caller's (d_msg_in, msg_fmt: as ldpc_sim_generate_from; LDPC_EUNSUPPORTED on LDPC_ENCODER_NONE), mapped to symbols and sent
+ * through complex AWGN: d_sym [batch][n_sym][2] float32, 8-byte aligned, y = c + sigma z per coordinate.  NOISE: symbol pair g =
+ * symbols 2g and 2g + 1 takes one Philox call with counter (frame lo, frame hi, g, stream 2) and the Box-Muller of
+ * ldpc_sim_generate: (r0, r1) -> I, Q of symbol 2g, (r2, r3) -> I, Q of symbol 2g + 1.  Streams 0 (messages) and 1 (the BPSK
+ * source's noise) are untouched.  d_msg [batch][k] bytes may be NULL.  The codewords are encoded into a packed buffer of
+ * max_batch * ceil(n_tx / 8) bytes inside `sim`, allocated by the first such call (LDPC_ENCODER_DENSE and _NONE also use the staging
+ * buffer of ldpc_sim_encode_messages).  1 <= batch <= max_batch.  The message words stay inside `sim` for ldpc_sim_tally.
+ * An Eb/N0 so high that sigma^2 underflows to 0 is accepted here (the symbols are then the constellation points); a NaN Eb/N0 is
+ * LDPC_EINVAL. */
+int ldpc_sim_transmit(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db,
+                      const void *d_msg_in, int msg_fmt, float *d_sym, uint8_t *d_msg, void *stream);
+/* ldpc_sim_transmit and ldpc_demap_dev(.., ldpc_sim_noise_var(..), ..) in ONE kernel: the samples never reach memory, and the LLRs
+ * d_llr [batch][N] (llr_fmt, qscale: as ldpc_demap_dev) are bit for bit those of the two calls.  Unlike ldpc_sim_transmit it needs
+ * sigma^2 > 0 with 1 / (2 sigma^2) inside a float32 (Eb/N0 below about 380 dB): LDPC_EINVAL otherwise.
+ * NOTE on LDPC_MOD_BPSK: this path computes ((y + 1)^2 - (y - 1)^2) / (2 sigma^2), which is not bitwise ldpc_sim_generate's
+ * (2 / sigma^2) (x + sigma z), and it draws its noise from stream 2.  It is not a replacement for ldpc_sim_generate. */
+int ldpc_sim_generate_mod(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db,
+                          const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt, float qscale, uint8_t *d_msg, void *stream);
 /* the receive side: message bit i of a frame = decoded bit msg_pos[i] of d_bits [batch][N] bytes (bit 0 of each), written in
  * msg_fmt.  With the systematic form message and parity bits interleave; any source qualifies, LDPC_ENCODER_NONE included. */
 int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream);

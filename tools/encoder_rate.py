@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only | --messages caller] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
+"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only | --messages caller | --modulation qpsk|8psk|table32] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
 sim.hip sim_parity_qc_kernel) against the dense packed GF(2) mat-vec of the expanded generator (Orig.hs:25-26), on the shipped AR4JA
 codes: the encoder alone (ldpc_sim_encode_batch: messages + parity -> codeword bytes) and the whole frame source
 (ldpc_sim_generate: + BPSK, AWGN, LLRs).  HIP events on the launch stream, median of 7.
@@ -13,7 +13,13 @@ codes/1920.1280.3.303 (no generator, not accumulator-shaped) generate against th
 --messages caller: the caller's own messages (ldpc_sim_encode_messages) on the quasi-cyclic source of jpl.4096.4.5, the systematic form of
 codes/1920.1280.3.303 (both [frames], default 65 536) and the encoder from H of tests/dvbs2_short.py (a quarter of that): bytes -> bytes and
 packed -> packed next to ldpc_sim_encode_batch on the same source and batch and a device-to-device copy of batch * k bytes.  One warm-up,
-median of 5.  The bar: bytes -> bytes <= encode_batch + 2 x that copy."""
+median of 5.  The bar: bytes -> bytes <= encode_batch + 2 x that copy.
+--modulation qpsk|8psk|table32: the modulated path (csrc/sim_mod.hip, csrc/demap.hip) on the quasi-cyclic source of jpl.4096.4.5: ldpc_sim_generate_mod
+(float32 and int8 LLRs) next to ldpc_sim_generate of the same source and batch in the same run, ldpc_sim_transmit alone, and ldpc_demap_dev alone
+into float32 and into int8 with the bytes it moves next to a device-to-device copy of as many bytes.  table32: a 4 + 12 + 16 ring table.  One
+warm-up, median of 5; run each modulation as its own process under its own time limit.  The bar (qpsk only): generate_mod <= 1.25 x generate.
+Where a lane's m LLRs fit no vector store (8psk, table32) the demapper stores them one by one; the LDS-transpose alternative lost the A/B
+recorded in profiles/r14_modulation.txt and is not in the library."""
 import os
 import sys
 
@@ -219,9 +225,61 @@ def caller_leg(B, dev, st):
         torch.cuda.empty_cache()
 
 
+def modulation_leg(which, B, dev, st):
+    import numpy as np
+    from tests import modulation_spec as ms
+    pts = {"qpsk": lambda: ms.builtin(ms.QPSK), "8psk": lambda: ms.builtin(ms.PSK8),
+           "table32": lambda: ms.rings((1.0, 2.84, 5.27), (4, 12, 16), (np.pi / 4, np.pi / 12, 0.0))}[which]()
+    mod = E.Modulation(pts)
+    m = mod.bits
+    ecc = E.ECC(os.path.join(ROOT, "codes"), "ldpc/hip-minsum/jpl.4096.4.5/50/4/5", max_batch=B)
+    sim, k, n_tx, N = ecc.sim, ecc.message_length, ecc.codeword_length, ecc.unpunctured_length
+    ns = mod.symbols(n_tx)
+    s_ = st.cuda_stream
+    llr = torch.empty((B, N), dtype=torch.float32, device=dev)
+    q = torch.empty((B, N), dtype=torch.int8, device=dev)
+    sym = torch.empty((B, ns, 2), dtype=torch.float32, device=dev)
+    nv = sim.noise_var(mod, 2.0)
+    t_gen = timed(lambda: sim.generate(1, 0, B, 2.0, llr.data_ptr(), None, s_), st, 5)
+    t_mod = timed(lambda: sim.generate_mod(mod, 1, 0, B, 2.0, llr.data_ptr(), "f32", 0.0, None, "bytes", None, s_), st, 5)
+    t_gen2 = timed(lambda: sim.generate(1, 0, B, 2.0, llr.data_ptr(), None, s_), st, 5)           # again, after: the spread of the yardstick
+    t_mod8 = timed(lambda: sim.generate_mod(mod, 1, 0, B, 2.0, q.data_ptr(), "i8", 4.0, None, "bytes", None, s_), st, 5)
+    t_tx = timed(lambda: sim.transmit(mod, 1, 0, B, 2.0, sym.data_ptr(), None, "bytes", None, s_), st, 5)
+    print(f"jpl.4096.4.5 qc source, {which} (m = {m}, {ns} symbols a frame), {B} frames, 2 dB, median of 5 (ms):", flush=True)
+    gen = min(t_gen, t_gen2)
+    bar = f" ({'within' if t_mod <= 1.25 * gen else 'MISSES'} the bar 1.25)" if which == "qpsk" else " (no bar)"
+    print(f"  ldpc_sim_generate f32 {t_gen:8.3f} (again {t_gen2:8.3f}) | ldpc_sim_generate_mod f32 {t_mod:8.3f} = {t_mod / gen:.3f} x generate"
+          f"{bar} | generate_mod int8 {t_mod8:8.3f} | ldpc_sim_transmit {t_tx:8.3f}", flush=True)
+    for fmt, out, size in (("f32", llr, 4), ("i8", q, 1)):
+        nbytes = B * (ns * 8 + N * size)
+        src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
+        dst = torch.empty_like(src)
+        t_dm = timed(lambda: E.demap(mod, B, n_tx, N, sym.data_ptr(), nv, out.data_ptr(), fmt, 4.0, s_), st, 5)
+        t_cp = timed(lambda: dst.copy_(src), st, 5)            # reads nbytes / 2 and writes nbytes / 2: the same bytes moved
+        print(f"  ldpc_demap_dev -> {fmt:3s} {t_dm:8.3f} ms, {nbytes / 1e6:9.1f} MB moved = {nbytes / t_dm / 1e9:7.2f} TB/s | device copy of as many bytes {t_cp:8.3f} ms"
+              f" = {nbytes / t_cp / 1e9:7.2f} TB/s | demap / copy = {t_dm / t_cp:.2f}", flush=True)
+        del src, dst
+    # the fused kernel against its two halves on this run's data
+    two = torch.empty((B, N), dtype=torch.float32, device=dev)
+    sim.generate_mod(mod, 1, 0, B, 2.0, llr.data_ptr(), "f32", 0.0, None, "bytes", None, s_)
+    sim.transmit(mod, 1, 0, B, 2.0, sym.data_ptr(), None, "bytes", None, s_)
+    E.demap(mod, B, n_tx, N, sym.data_ptr(), nv, two.data_ptr(), "f32", 0.0, s_)
+    torch.cuda.synchronize()
+    assert torch.equal(llr.view(torch.int32), two.view(torch.int32)), "generate_mod differs from transmit + demap"
+    print(f"  generate_mod = transmit + demap bit for bit; LLRs sha256 {sha(llr[:256])}", flush=True)
+    mod.close(); ecc.close()
+
+
 def main():
     argv = sys.argv[1:]
     messages = None
+    modulation = None
+    if "--modulation" in argv:
+        i = argv.index("--modulation")
+        modulation = argv[i + 1] if i + 1 < len(argv) else ""
+        del argv[i:i + 2]
+        if modulation not in ("qpsk", "8psk", "table32"):
+            sys.exit("--modulation takes one value: qpsk, 8psk or table32")
     if "--messages" in argv:
         i = argv.index("--messages")
         messages = argv[i + 1] if i + 1 < len(argv) else ""
@@ -234,6 +292,9 @@ def main():
     dev = torch.device("cuda", 0)
     st = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(st)
+    if modulation:
+        modulation_leg(modulation, B, dev, st)
+        return
     if messages:
         caller_leg(B, dev, st)
         return
