@@ -61,11 +61,14 @@ def _csr(g):
 def _rows(g):
     """the rows in ascending order, as groups of consecutive rows of one weight that share no column: (cols [R, d], first edge).  The
     rows of a group touch distinct lam cells and distinct messages, so updating them together IS updating them one after the other
-    (what the kernel's barrier steps rest on as well); it only spares numpy calls"""
+    (what the kernel's barrier steps rest on as well); it only spares numpy calls.  A row without edges is skipped: its parity is even,
+    it has no message and it writes no lam"""
     rp, ci = _csr(g)
     groups, cur, e0, seen = [], [], 0, set()
     for m in range(len(rp) - 1):
         cols = ci[rp[m]:rp[m + 1]]
+        if not len(cols):
+            continue
         if cur and (len(cols) != len(cur[0]) or not seen.isdisjoint(cols.tolist())):
             groups.append((np.stack(cur), e0))
             cur, seen = [], set()

@@ -132,6 +132,22 @@ def test_scale_one_is_the_plain_minimum():
     assert spec.float_rule(np.float32(0.25), 1.0, 0.5) == 0 and not np.signbit(spec.float_rule(np.float32(0.25), 1.0, 0.5))
 
 
+@pytest.mark.parametrize("cell", ["f16", "f32", "i8"])
+def test_a_row_without_edges_changes_nothing(cell):
+    """rows of weight 0 (even parity, no message, no lam write) are skipped: the same arrays with them and without"""
+    G, llr = _float_frames("moon.7.13", (1.0, 3.0), "oracle")
+    rp = np.asarray(G.rp).tolist()
+    M = len(rp) - 1
+    for at in (M, M // 2, 0):                                       # a last, a middle and a first row
+        rp.insert(at, rp[at])
+    H = f32spec.Graph(rp, G.ci, G.N)
+    assert H.M == M + 3 and (np.diff(H.rp) == 0).sum() == 3 and np.diff(H.rp)[[0, -1]].tolist() == [0, 0]
+    for alpha, beta in ((0.75, 0.0), (1.0, 0.5)):
+        ref = spec.decode(cell, G, llr, 25, alpha, beta)
+        assert ref[2].any() and (ref[1] > 1).any()
+        assert _equal(spec.decode(cell, H, llr, 25, alpha, beta), ref)
+
+
 # ---- 6. the build's rule instances
 def test_rule_instances_exist_and_use_no_scratch():
     path = os.path.join(os.path.dirname(B.__file__), "build", "layered_csr-hip-amdgcn-amd-amdhsa-gfx950.s")
