@@ -21,6 +21,7 @@ SCHED_FLOODING, SCHED_LAYERED = 0, 1
 SUM_REFERENCE, SUM_ARRAYLET, SUM_SPARSE = 0, 1, 2
 BITS_BYTES, BITS_PACKED = 0, 1   # ldpc_bit_format
 MOD_BPSK, MOD_QPSK, MOD_8PSK, MOD_16QAM = 1, 2, 3, 4
+MOD_64QAM, MOD_256QAM, MOD_1024QAM, MOD_4096QAM = 6, 8, 10, 12   # product constellations: the kind number is m
 LLR_F32, LLR_F16, LLR_I8 = 0, 1, 2   # LDPC_LLR_*: the output formats of the demapper
 
 
@@ -47,7 +48,7 @@ ABI_SYMBOLS = [
     "ldpc_csr_systematic_form", "ldpc_sim_create_systematic_on", "ldpc_sim_message_length", "ldpc_sim_positions",
     "ldpc_sim_encode_messages", "ldpc_sim_generate_from", "ldpc_sim_extract_messages",
     "ldpc_modulation_create", "ldpc_modulation_create_builtin", "ldpc_modulation_destroy", "ldpc_modulation_bits", "ldpc_modulation_points", "ldpc_modulation_energy",
-    "ldpc_modulation_symbols", "ldpc_demap_dev", "ldpc_sim_noise_var", "ldpc_sim_transmit", "ldpc_sim_generate_mod",
+    "ldpc_modulation_symbols", "ldpc_modulation_create_product", "ldpc_modulation_axis_levels", "ldpc_demap_dev", "ldpc_sim_noise_var", "ldpc_sim_transmit", "ldpc_sim_generate_mod",
     "ldpc_matrix_load", "ldpc_matrix_load_mackay", "ldpc_matrix_destroy", "ldpc_matrix_info", "ldpc_matrix_dense",
     "ldpc_matrix_qc_offsets", "ldpc_code_from_matrix",
     "ldpc_ecc_create", "ldpc_ecc_destroy", "ldpc_ecc_name", "ldpc_ecc_message_length", "ldpc_ecc_codeword_length",
@@ -248,6 +249,9 @@ def lib():
     L.ldpc_modulation_energy.restype = C.c_double
     L.ldpc_modulation_energy.argtypes = [vp]
     L.ldpc_modulation_symbols.argtypes = [vp, C.c_int]
+    L.ldpc_modulation_create_product.restype = vp
+    L.ldpc_modulation_create_product.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.ldpc_modulation_axis_levels.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.ldpc_demap_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, C.c_int, C.c_float, vp]
     L.ldpc_sim_noise_var.restype = C.c_double
     L.ldpc_sim_noise_var.argtypes = [vp, vp, C.c_double]
@@ -768,12 +772,17 @@ def _llr_fmt(fmt):
 
 class Modulation:
     """A labelled constellation (ldpc_modulation): points [2^m][2] float32 (I, Q), m = 1..6, or a built-in by name.  Symbol s of a
-    frame carries codeword bits m s .. m s + m - 1, the first one the MSB of the label = the index into the table."""
+    frame carries codeword bits m s .. m s + m - 1, the first one the MSB of the label = the index into the table.
+    Modulation.product(levels_i, levels_q) and the built-ins "64qam" .. "4096qam" are product constellations: 2^b levels an axis,
+    b = 1..6, m = 2 b, label = (index into levels_i) << b | (index into levels_q)."""
 
-    BUILTIN = {"bpsk": MOD_BPSK, "qpsk": MOD_QPSK, "8psk": MOD_8PSK, "16qam": MOD_16QAM}
+    BUILTIN = {"bpsk": MOD_BPSK, "qpsk": MOD_QPSK, "8psk": MOD_8PSK, "16qam": MOD_16QAM,
+               "64qam": MOD_64QAM, "256qam": MOD_256QAM, "1024qam": MOD_1024QAM, "4096qam": MOD_4096QAM}
 
-    def __init__(self, points):
-        if isinstance(points, str):
+    def __init__(self, points, _handle=None):
+        if _handle is not None:
+            h = _handle
+        elif isinstance(points, str):
             h = lib().ldpc_modulation_create_builtin(self.BUILTIN.get(points.lower(), -1))
         elif isinstance(points, int):
             h = lib().ldpc_modulation_create_builtin(points)
@@ -795,6 +804,29 @@ class Modulation:
         out = np.zeros((1 << self.bits, 2), np.float32)
         assert lib().ldpc_modulation_points(self._h, ptr(out, C.c_float)) == 1 << self.bits
         return out
+
+    @classmethod
+    def product(cls, levels_i, levels_q):
+        """ldpc_modulation_create_product: two level sets [2^b] float32, b = 1..6"""
+        li, lq = np.ascontiguousarray(levels_i, np.float32), np.ascontiguousarray(levels_q, np.float32)
+        n = li.shape[0] if li.ndim == 1 and li.shape == lq.shape else 0
+        b = n.bit_length() - 1
+        if n < 2 or n != 1 << b:
+            raise LdpcError(EINVAL, "Modulation.product: the two level sets must be [2^b] each")
+        h = lib().ldpc_modulation_create_product(b, ptr(li, C.c_float), ptr(lq, C.c_float))
+        if not h:
+            raise LdpcError(lib().ldpc_last_error_code(), last_error())
+        return cls(None, _handle=h)
+
+    @property
+    def axis_levels(self):
+        """(levels_i, levels_q), [2^b] float32 each, of a product object; None for a table object"""
+        b = int(lib().ldpc_modulation_axis_levels(self._h, None, None))
+        if b <= 0:
+            return None
+        li, lq = np.zeros(1 << b, np.float32), np.zeros(1 << b, np.float32)
+        assert lib().ldpc_modulation_axis_levels(self._h, ptr(li, C.c_float), ptr(lq, C.c_float)) == b
+        return li, lq
 
     @property
     def energy(self):

@@ -1351,6 +1351,7 @@ int ldpc_demap_dev(const ldpc_modulation *mod, int batch, int n_tx, int N, const
     const int device = current_device();
     if (device < 0) return set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded");
     HIPCHK(hipSetDevice(device));
+    if (mod->b) return ldpc::demap_product_launch((hipStream_t)stream, mod->ax, mod->b, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
     return ldpc::demap_launch((hipStream_t)stream, mod->tab, mod->m, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
 }
 
@@ -1407,6 +1408,7 @@ int ldpc_sim_transmit(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, 
     HIPCHK(hipSetDevice(sim->device));
     hipStream_t st = (hipStream_t)stream;
     if ((rc = sim_mod_codewords("ldpc_sim_transmit", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
+    if (mod->b) return ldpc::product_transmit_launch(st, mod->ax, mod->b, batch, sim->dev.n_tx, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv), d_sym);
     return ldpc::mod_transmit_launch(st, mod->tab, mod->m, batch, sim->dev.n_tx, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv), d_sym);
 }
 
@@ -1423,6 +1425,9 @@ int ldpc_sim_generate_mod(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t se
     HIPCHK(hipSetDevice(sim->device));
     hipStream_t st = (hipStream_t)stream;
     if ((rc = sim_mod_codewords("ldpc_sim_generate_mod", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
+    if (mod->b)
+        return ldpc::product_generate_launch(st, mod->ax, mod->b, batch, sim->dev.n_tx, sim->dev.N, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv),
+                                             inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
     return ldpc::mod_generate_launch(st, mod->tab, mod->m, batch, sim->dev.n_tx, sim->dev.N, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv),
                                      inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
 }

@@ -15,6 +15,13 @@ struct ModTab {
     float pt[kModMaxPoints][2];   // [label]: I, Q; entries >= 2^m are not read
 };
 enum { MOD_LLR_F32 = 0, MOD_LLR_F16 = 1, MOD_LLR_I8 = 2 };   // = LDPC_LLR_*
+// a product constellation (I-axis levels x Q-axis levels, label = I-label << b | Q-label) as a kernel argument: the two level tables,
+// 512 bytes as ModTab, for up to 6 bits an axis (4096 points).  Its device functions and kernels: demap_product.h, demap_product.hip,
+// sim_mod_product.hip
+constexpr int kAxisMaxBits = 6, kAxisMaxLevels = 1 << kAxisMaxBits;
+struct AxisTab {
+    float lev[2][kAxisMaxLevels];   // [axis: I, Q][axis label]; entries >= 2^b are not read
+};
 
 // d_llr [batch][N] <- the LLRs of d_sym [batch][n_sym][2]; inv = float32(1 / (2 sigma^2))
 int demap_launch(hipStream_t st, const ModTab &tab, int m, int batch, int n_tx, int N, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
@@ -24,6 +31,13 @@ int mod_transmit_launch(hipStream_t st, const ModTab &tab, int m, int batch, int
 // the two in one kernel: the samples stay in registers
 int mod_generate_launch(hipStream_t st, const ModTab &tab, int m, int batch, int n_tx, int N, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
                         float inv, void *d_llr, int fmt, float qscale);
+
+// the same three for a product constellation of b bits an axis (m = 2 b)
+int demap_product_launch(hipStream_t st, const AxisTab &tab, int b, int batch, int n_tx, int N, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
+int product_transmit_launch(hipStream_t st, const AxisTab &tab, int b, int batch, int n_tx, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
+                            float *d_sym);
+int product_generate_launch(hipStream_t st, const AxisTab &tab, int b, int batch, int n_tx, int N, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
+                            float sg, float inv, void *d_llr, int fmt, float qscale);
 
 #ifdef __HIPCC__
 // constellation point of a per-lane label: a binary select tree over the uniform table (2^M - 1 selects per coordinate), label bit 0
@@ -132,6 +146,8 @@ __device__ __forceinline__ void store_slot(OT *__restrict__ row, int s, int n_tx
 // (host) the object behind include/ldpc_hip.h ldpc_modulation
 struct ldpc_modulation {
     int m = 0;
-    ldpc::ModTab tab{};
+    ldpc::ModTab tab{};   // a table object (b == 0)
     double es = 0.0;
+    int b = 0;            // a product object: bits per axis, m = 2 b
+    ldpc::AxisTab ax{};
 };

@@ -463,7 +463,8 @@ int ldpc_sim_encode_messages(ldpc_sim *sim, int batch, const void *d_msg, int ms
 int ldpc_sim_generate_from(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg, int msg_fmt,
                            void *d_llr, int llr_f16, void *stream);
 /* ---- higher-order modulation: a labelled constellation, a max-log soft demapper, and the frame source's modulated path.
- * Modulation object (host only): 2^m points (I, Q), m = 1..6 bits per symbol.  LABELLING: symbol s of a frame carries codeword bits
+ * Modulation object (host only): 2^m points (I, Q), m = 1..6 bits per symbol as a table (product constellations, below, reach
+ * m = 12).  LABELLING: symbol s of a frame carries codeword bits
  * m s .. m s + m - 1; its label is sum_j bit(m s + j) << (m - 1 - j) -- the first bit is the MSB -- and the label is the index into
  * `points`.  Bits at positions >= n_tx pad as 0.  There is no bit interleaver: a caller permutes.  Two equal points are allowed.
  * LDPC_EINVAL and NULL for m outside 1..6, a null table or a non-finite point.
@@ -474,7 +475,8 @@ int ldpc_sim_generate_from(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, i
  *   LDPC_MOD_8PSK   unit circle, the point at angle k pi / 4 carries label k ^ (k >> 1): Gray around the circle
  *   LDPC_MOD_16QAM  (b0 b1 | b2 b3) -> (L[b0 b1], L[b2 b3]) / sqrt 10, L: 00 01 11 10 -> -3 -1 +1 +3: Gray per axis, unit energy */
 typedef struct ldpc_modulation ldpc_modulation;
-enum { LDPC_MOD_BPSK = 1, LDPC_MOD_QPSK = 2, LDPC_MOD_8PSK = 3, LDPC_MOD_16QAM = 4 };
+enum { LDPC_MOD_BPSK = 1, LDPC_MOD_QPSK = 2, LDPC_MOD_8PSK = 3, LDPC_MOD_16QAM = 4,
+       LDPC_MOD_64QAM = 6, LDPC_MOD_256QAM = 8, LDPC_MOD_1024QAM = 10, LDPC_MOD_4096QAM = 12 };   /* the kind number is m */
 ldpc_modulation *ldpc_modulation_create(int bits_per_symbol /* m, 1..6 */, const float *points /* [2^m][2]: I, Q */);
 ldpc_modulation *ldpc_modulation_create_builtin(int kind);
 void ldpc_modulation_destroy(ldpc_modulation *mod);
@@ -482,6 +484,32 @@ int ldpc_modulation_bits(const ldpc_modulation *mod);                /* m */
 int ldpc_modulation_points(const ldpc_modulation *mod, float *out);  /* [2^m][2] (out may be NULL); returns 2^m */
 double ldpc_modulation_energy(const ldpc_modulation *mod);           /* Es = mean |c|^2, accumulated in double in index order */
 int ldpc_modulation_symbols(const ldpc_modulation *mod, int n_tx);   /* symbols per frame: ceil(n_tx / m) */
+/* PRODUCT constellations, up to 4096 points: an I-axis level set times a Q-axis level set, b = 1..6 bits an axis, m = 2 b bits per
+ * symbol.  The labelling rule above holds; of a symbol's m bits the first b (MSB first) are the index into levels_i and the next b the
+ * index into levels_q: label = (iI << b) | iQ, and the point of that label is (levels_i[iI], levels_q[iQ]).  The two axes may hold
+ * different level sets; non-uniform levels and unequal I/Q scaling are allowed.  Different bits per axis and labellings that interleave
+ * I and Q bits are not provided: a caller permutes.  LDPC_EINVAL and NULL for b outside 1..6, a null table or a non-finite level.
+ * For such an object
+ *   ldpc_modulation_bits    returns 2 b;
+ *   ldpc_modulation_points  returns 4^b and writes the materialised table pt[(iI << b) | iQ] = (levels_i[iI], levels_q[iQ]);
+ *   ldpc_modulation_energy  is the rule above on that table (double, index order): for b <= 3 bit for bit the Es, and so the sigma, of
+ *                           the same table passed to ldpc_modulation_create;
+ *   ldpc_demap_dev          separates the max-log rule per axis: for the coordinate y of axis A with levels a_l
+ *                             e_l = (y - a_l)^2;  LLR_j = (min over axis labels with bit j = 0 of e_l - min over those with bit j = 1) / (2 noise_var)
+ *                           in float32, operation by operation as tests/product_modulation_spec.py states it (bit for bit).  Output
+ *                           element m s + j is I-bit j of symbol s, element m s + b + j its Q-bit j.  This is the max-log rule on the
+ *                           4^b points -- the other axis's smallest distance adds to both mins and cancels -- at 2 * 2^b distances a
+ *                           sample; against ldpc_demap_dev on the materialised table (b <= 3) it differs by the roundings of that
+ *                           cancelled term only.  A NaN coordinate makes the b LLRs of ITS axis NaN (int8: 0) and leaves the other
+ *                           axis's LLRs as they are (the table rule makes all m NaN);
+ *   ldpc_sim_transmit       gives bit for bit the symbols of the materialised table (b <= 3: of that table object).
+ * Built-ins LDPC_MOD_64QAM, _256QAM, _1024QAM, _4096QAM (b = 3, 4, 5, 6; product objects), both axes: position k = 0 .. 2^b - 1 has
+ * amplitude (2k - (2^b - 1)) / sqrt(2 (4^b - 1) / 3) and carries the axis label k ^ (k >> 1) (binary-reflected Gray); each level is
+ * computed in double and rounded to float32 once; unit energy.  For b = 2 that is the level set of LDPC_MOD_16QAM, which stays a table
+ * object.  As above, no claim that these are any standard's labellings. */
+ldpc_modulation *ldpc_modulation_create_product(int bits_per_axis /* b, 1..6 */, const float *levels_i /* [2^b] */, const float *levels_q /* [2^b] */);
+/* b and the two level sets of a product object ([2^b] each; either pointer may be NULL); 0, and nothing written, for a table object */
+int ldpc_modulation_axis_levels(const ldpc_modulation *mod, float *levels_i, float *levels_q);
 /* Max-log soft demapper on the device: d_sym [batch][n_sym][2] float32 I/Q samples (8-byte aligned), n_sym = ceil(n_tx / m) ->
  * d_llr [batch][N] in one of the decoders' input formats, one pass.  For a sample y and every point c_p:
  *   d_p = |y - c_p|^2;  LLR_j = (min over labels with bit j = 0 of d_p  -  min over labels with bit j = 1 of d_p) / (2 noise_var)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only | --messages caller | --modulation qpsk|8psk|table32] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
+"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only | --messages caller | --modulation qpsk|8psk|table32|64qam|256qam|1024qam|4096qam|grid64] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
 sim.hip sim_parity_qc_kernel) against the dense packed GF(2) mat-vec of the expanded generator (Orig.hs:25-26), on the shipped AR4JA
 codes: the encoder alone (ldpc_sim_encode_batch: messages + parity -> codeword bytes) and the whole frame source
 (ldpc_sim_generate: + BPSK, AWGN, LLRs).  HIP events on the launch stream, median of 7.
@@ -19,7 +19,10 @@ median of 5.  The bar: bytes -> bytes <= encode_batch + 2 x that copy.
 into float32 and into int8 with the bytes it moves next to a device-to-device copy of as many bytes.  table32: a 4 + 12 + 16 ring table.  One
 warm-up, median of 5; run each modulation as its own process under its own time limit.  The bar (qpsk only): generate_mod <= 1.25 x generate.
 Where a lane's m LLRs fit no vector store (8psk, table32) the demapper stores them one by one; the LDS-transpose alternative lost the A/B
-recorded in profiles/r14_modulation.txt and is not in the library."""
+recorded in profiles/r14_modulation.txt and is not in the library.
+--modulation 64qam|256qam|1024qam|4096qam: the same lines for the product built-ins (csrc/demap_product.hip, csrc/sim_mod_product.hip; no bar).
+grid64: the 8 x 8 grid as a 64-point table object.  64qam also runs that table in the same process, the two alternating, and prints the one
+bar of product constellations: ldpc_demap_dev -> f32 and ldpc_sim_generate_mod -> f32 on the product object no slower than on the table."""
 import os
 import sys
 
@@ -225,12 +228,18 @@ def caller_leg(B, dev, st):
         torch.cuda.empty_cache()
 
 
+PRODUCT_BUILTINS = ("64qam", "256qam", "1024qam", "4096qam")
+
+
 def modulation_leg(which, B, dev, st):
     import numpy as np
     from tests import modulation_spec as ms
-    pts = {"qpsk": lambda: ms.builtin(ms.QPSK), "8psk": lambda: ms.builtin(ms.PSK8),
-           "table32": lambda: ms.rings((1.0, 2.84, 5.27), (4, 12, 16), (np.pi / 4, np.pi / 12, 0.0))}[which]()
-    mod = E.Modulation(pts)
+    if which in PRODUCT_BUILTINS:
+        mod = E.Modulation(which)
+    else:
+        pts = {"qpsk": lambda: ms.builtin(ms.QPSK), "8psk": lambda: ms.builtin(ms.PSK8), "grid64": ms.grid64,
+               "table32": lambda: ms.rings((1.0, 2.84, 5.27), (4, 12, 16), (np.pi / 4, np.pi / 12, 0.0))}[which]()
+        mod = E.Modulation(pts)
     m = mod.bits
     ecc = E.ECC(os.path.join(ROOT, "codes"), "ldpc/hip-minsum/jpl.4096.4.5/50/4/5", max_batch=B)
     sim, k, n_tx, N = ecc.sim, ecc.message_length, ecc.codeword_length, ecc.unpunctured_length
@@ -267,6 +276,22 @@ def modulation_leg(which, B, dev, st):
     torch.cuda.synchronize()
     assert torch.equal(llr.view(torch.int32), two.view(torch.int32)), "generate_mod differs from transmit + demap"
     print(f"  generate_mod = transmit + demap bit for bit; LLRs sha256 {sha(llr[:256])}", flush=True)
+    if which == "64qam":
+        # the bar: the product object against the same 64 points as a table, alternating in this process; the samples demapped are this
+        # run's 64qam symbols for both (the two level sets are the same, only the labels differ)
+        tab = E.Modulation(ms.grid64())
+        assert tab.bits == m
+        res = {}
+        for rep in range(2):
+            for label, o in (("product", mod), ("table", tab)):
+                t_d = timed(lambda: E.demap(o, B, n_tx, N, sym.data_ptr(), nv, llr.data_ptr(), "f32", 4.0, s_), st, 5)
+                t_g = timed(lambda: sim.generate_mod(o, 1, 0, B, 2.0, llr.data_ptr(), "f32", 0.0, None, "bytes", None, s_), st, 5)
+                res.setdefault(label, []).append((t_d, t_g))
+        for i, call in enumerate(("ldpc_demap_dev -> f32", "ldpc_sim_generate_mod -> f32")):
+            p, t = [r[i] for r in res["product"]], [r[i] for r in res["table"]]
+            print(f"  {call:30s} product object {p[0]:8.3f} {p[1]:8.3f} ms | 64-point table (grid64) {t[0]:8.3f} {t[1]:8.3f} ms | product / table = {min(p) / min(t):.3f}"
+                  f" ({'within' if max(p) <= min(t) else 'MISSES'} the bar: no slower)", flush=True)
+        tab.close()
     mod.close(); ecc.close()
 
 
@@ -278,8 +303,8 @@ def main():
         i = argv.index("--modulation")
         modulation = argv[i + 1] if i + 1 < len(argv) else ""
         del argv[i:i + 2]
-        if modulation not in ("qpsk", "8psk", "table32"):
-            sys.exit("--modulation takes one value: qpsk, 8psk or table32")
+        if modulation not in ("qpsk", "8psk", "table32", "grid64") + PRODUCT_BUILTINS:
+            sys.exit("--modulation takes one value: qpsk, 8psk, table32, grid64, 64qam, 256qam, 1024qam or 4096qam")
     if "--messages" in argv:
         i = argv.index("--messages")
         messages = argv[i + 1] if i + 1 < len(argv) else ""
