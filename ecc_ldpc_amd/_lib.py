@@ -49,6 +49,8 @@ ABI_SYMBOLS = [
     "ldpc_sim_encode_messages", "ldpc_sim_generate_from", "ldpc_sim_extract_messages",
     "ldpc_modulation_create", "ldpc_modulation_create_builtin", "ldpc_modulation_destroy", "ldpc_modulation_bits", "ldpc_modulation_points", "ldpc_modulation_energy",
     "ldpc_modulation_symbols", "ldpc_modulation_create_product", "ldpc_modulation_axis_levels", "ldpc_demap_dev", "ldpc_sim_noise_var", "ldpc_sim_transmit", "ldpc_sim_generate_mod",
+    "ldpc_interleaver_create_on", "ldpc_interleaver_destroy", "ldpc_interleaver_dims", "ldpc_interleaver_positions", "ldpc_interleaver_block_positions",
+    "ldpc_demap_dev_il", "ldpc_sim_transmit_il", "ldpc_sim_generate_mod_il", "ldpc_interleave_bits_dev", "ldpc_deinterleave_llr_dev",
     "ldpc_matrix_load", "ldpc_matrix_load_mackay", "ldpc_matrix_destroy", "ldpc_matrix_info", "ldpc_matrix_dense",
     "ldpc_matrix_qc_offsets", "ldpc_code_from_matrix",
     "ldpc_ecc_create", "ldpc_ecc_destroy", "ldpc_ecc_name", "ldpc_ecc_message_length", "ldpc_ecc_codeword_length",
@@ -71,7 +73,7 @@ _lib = None
 # the interpreter is finalising, __del__ does nothing: no hipFree / hipStreamDestroy ever runs from a finaliser during
 # shutdown, when the order against the HIP runtime's own exit handlers is not defined.
 _live = weakref.WeakSet()
-_CLOSE_ORDER = {"ECC": 0, "Batcher": 1, "Decoder": 2, "Sim": 3, "Code": 4, "Matrix": 5, "PinnedArray": 6, "Modulation": 7}
+_CLOSE_ORDER = {"ECC": 0, "Batcher": 1, "Decoder": 2, "Sim": 3, "Code": 4, "Matrix": 5, "PinnedArray": 6, "Modulation": 7, "Interleaver": 8}
 _closed_all = False
 
 
@@ -257,6 +259,18 @@ def lib():
     L.ldpc_sim_noise_var.argtypes = [vp, vp, C.c_double]
     L.ldpc_sim_transmit.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp]
     L.ldpc_sim_generate_mod.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, C.c_float, vp, vp]
+    L.ldpc_interleaver_create_on.restype = vp
+    L.ldpc_interleaver_create_on.argtypes = [C.c_int, C.c_int, C.c_int, i32p]
+    L.ldpc_interleaver_destroy.restype = None
+    L.ldpc_interleaver_destroy.argtypes = [vp]
+    L.ldpc_interleaver_dims.argtypes = [vp, ip, ip]
+    L.ldpc_interleaver_positions.argtypes = [vp, i32p]
+    L.ldpc_interleaver_block_positions.argtypes = [C.c_int, C.c_int, i32p, i32p, i32p]
+    L.ldpc_demap_dev_il.argtypes = [vp, vp, C.c_int, vp, C.c_double, vp, C.c_int, C.c_float, vp]
+    L.ldpc_sim_transmit_il.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp]
+    L.ldpc_sim_generate_mod_il.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, C.c_float, vp, vp]
+    L.ldpc_interleave_bits_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]
+    L.ldpc_deinterleave_llr_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
     L.ldpc_matrix_qc_words.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.ldpc_matrix_rank.argtypes = [vp]
     L.ldpc_matrix_load.restype = vp
@@ -859,6 +873,90 @@ def demap(mod: Modulation, batch, n_tx, N, d_sym_ptr, noise_var, d_llr_ptr, llr_
                                float(qscale), stream))
 
 
+class Interleaver:
+    """A bit interleaver (ldpc_interleaver): transmitted bit t is codeword bit pos[t], pos [n_tx] injective into 0..N-1; the codeword
+    positions no entry names are punctured (LLR 0).  Interleaver.block(rows, cols, twist, order) is the block rule.  The table is
+    checked before the device is touched; it then lives on `device` (None: the calling thread's)."""
+
+    def __init__(self, pos, N, device=None):
+        a = np.asarray(pos)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31)):
+            raise LdpcError(EINVAL, "Interleaver: pos must be a one-dimensional array of 32-bit integers")
+        p = np.ascontiguousarray(a, np.int32)
+        dev = int(device) if device is not None else lib().ldpc_current_device()
+        h = lib().ldpc_interleaver_create_on(dev, p.shape[0], int(N), ptr(p, C.c_int32) if p.size else None)
+        if not h:
+            raise LdpcError(lib().ldpc_last_error_code(), last_error())
+        self._h = h
+        self.n_tx, self.N = int(p.shape[0]), int(N)
+        _register(self)
+
+    @staticmethod
+    def block_positions(rows, cols, twist=None, order=None):
+        """ldpc_interleaver_block_positions (host only): pos[r cols + j] = c rows + ((r - twist[c]) mod rows), c = order[j] -> [rows * cols] int32"""
+        rows, cols = int(rows), int(cols)
+        tw = None if twist is None else np.ascontiguousarray(twist, np.int32)
+        od = None if order is None else np.ascontiguousarray(order, np.int32)
+        if (tw is not None and tw.shape != (cols,)) or (od is not None and od.shape != (cols,)):
+            raise LdpcError(EINVAL, "Interleaver.block_positions: twist and order must be [cols]")
+        n = rows * cols if rows > 0 and cols > 0 and rows * cols < 2 ** 31 else 1
+        out = np.zeros(n, np.int32)
+        check(lib().ldpc_interleaver_block_positions(rows, cols, None if tw is None else ptr(tw, C.c_int32), None if od is None else ptr(od, C.c_int32),
+                                                     ptr(out, C.c_int32)))
+        return out
+
+    @classmethod
+    def block(cls, rows, cols, twist=None, order=None, N=None, device=None):
+        """the block interleaver of rows x cols bits; N (default rows * cols) > rows * cols punctures the tail"""
+        pos = cls.block_positions(rows, cols, twist, order)
+        return cls(pos, pos.shape[0] if N is None else N, device=device)
+
+    @property
+    def positions(self):
+        out = np.zeros(self.n_tx, np.int32)
+        assert lib().ldpc_interleaver_positions(self._h, ptr(out, C.c_int32)) == self.n_tx
+        return out
+
+    @property
+    def dims(self):
+        a, b = C.c_int(), C.c_int()
+        check(lib().ldpc_interleaver_dims(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if self._h:
+            lib().ldpc_interleaver_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        if _finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _h(o):
+    return o._h if o is not None else None
+
+
+def demap_il(mod: Modulation, il: Interleaver, batch, d_sym_ptr, noise_var, d_llr_ptr, llr_fmt="f32", qscale=0.0, stream=None):
+    """ldpc_demap_dev_il: demap() through the table: the LLR of transmitted bit t at element il.positions[t] of its row of [batch][il.N],
+    0 at the punctured positions"""
+    check(lib().ldpc_demap_dev_il(_h(mod), _h(il), int(batch), d_sym_ptr, float(noise_var), d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), stream))
+
+
+def interleave_bits(il: Interleaver, batch, d_cw_ptr, d_tx_ptr, cw_fmt="bytes", tx_fmt="bytes", stream=None):
+    """ldpc_interleave_bits_dev: codewords [batch][N] ("bytes", or "packed" rows of ceil(N / 8) bytes) -> transmitted bits [batch][n_tx]"""
+    check(lib().ldpc_interleave_bits_dev(_h(il), int(batch), d_cw_ptr, Sim._bits_fmt(cw_fmt), d_tx_ptr, Sim._bits_fmt(tx_fmt), stream))
+
+
+def deinterleave_llr(il: Interleaver, batch, d_llr_tx_ptr, d_llr_ptr, llr_fmt="f32", stream=None):
+    """ldpc_deinterleave_llr_dev: LLRs [batch][n_tx] in transmitted order -> [batch][N], 0 at the punctured positions, same element type"""
+    check(lib().ldpc_deinterleave_llr_dev(_h(il), int(batch), d_llr_tx_ptr, d_llr_ptr, _llr_fmt(llr_fmt), stream))
+
+
 class Sim:
     """Device-side frame source + error tally (ldpc_sim)."""
 
@@ -953,6 +1051,18 @@ class Sim:
         """transmit() and demap() in one kernel: LLRs [batch][N] in llr_fmt ("f32", "f16", "i8")"""
         check(lib().ldpc_sim_generate_mod(self._h, mod._h if mod is not None else None, int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_in_ptr,
                                           self._bits_fmt(msg_fmt), d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), d_msg_ptr, stream))
+
+    def transmit_il(self, mod: "Modulation", il: "Interleaver", seed, first_frame, batch, ebn0_db, d_sym_ptr, d_msg_in_ptr=None, msg_fmt="bytes", d_msg_ptr=None,
+                    stream=None):
+        """transmit() with the labels gathered through the table (ldpc_sim_transmit_il)"""
+        check(lib().ldpc_sim_transmit_il(self._h, _h(mod), _h(il), int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_in_ptr, self._bits_fmt(msg_fmt),
+                                         d_sym_ptr, d_msg_ptr, stream))
+
+    def generate_mod_il(self, mod: "Modulation", il: "Interleaver", seed, first_frame, batch, ebn0_db, d_llr_ptr, llr_fmt="f32", qscale=0.0, d_msg_in_ptr=None,
+                        msg_fmt="bytes", d_msg_ptr=None, stream=None):
+        """transmit_il() and demap_il() in one kernel (ldpc_sim_generate_mod_il)"""
+        check(lib().ldpc_sim_generate_mod_il(self._h, _h(mod), _h(il), int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_in_ptr, self._bits_fmt(msg_fmt),
+                                             d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), d_msg_ptr, stream))
 
     def tally(self, batch, d_bits_ptr, d_iters_ptr, d_tally_ptr, stream=None):
         check(lib().ldpc_sim_tally(self._h, int(batch), d_bits_ptr, d_iters_ptr, d_tally_ptr, stream))

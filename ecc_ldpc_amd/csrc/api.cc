@@ -13,6 +13,7 @@
 
 #include "backend.h"
 #include "demap.h"
+#include "interleaver.h"
 #include "jit.h"
 #include "sim.h"
 #include "systematic.h"
@@ -1430,6 +1431,135 @@ int ldpc_sim_generate_mod(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t se
                                              inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
     return ldpc::mod_generate_launch(st, mod->tab, mod->m, batch, sim->dev.n_tx, sim->dev.N, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv),
                                      inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+}
+
+// ---- the bit interleaver (csrc/interleaver.h): the object, the demapper and the modulated path through it, the table alone
+ldpc_interleaver *ldpc_interleaver_create_on(int device, int n_tx, int N, const int32_t *pos) {
+    std::vector<int32_t> holes;
+    if (ldpc::interleaver_check("ldpc_interleaver_create_on", n_tx, N, pos, holes) != LDPC_OK) return nullptr;   // before the device is touched
+    if (device < 0) { set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded"); return nullptr; }
+    if (check_device(device) != LDPC_OK) return nullptr;
+    ldpc_interleaver *il = new (std::nothrow) ldpc_interleaver();
+    if (!il) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    il->n_tx = n_tx; il->N = N; il->device = device; il->n_holes = (int)holes.size();
+    il->pos.assign(pos, pos + n_tx);
+    il->max_pos = *std::max_element(il->pos.begin(), il->pos.end());
+    // one allocation: pos | pad (0; rounded up so the hole list starts on 16 bytes) | holes
+    const size_t hole_at = ((size_t)n_tx + ldpc::kIlPad + 3) / 4 * 4;
+    std::vector<int32_t> tab(hole_at + holes.size(), 0);
+    std::copy(il->pos.begin(), il->pos.end(), tab.begin());
+    std::copy(holes.begin(), holes.end(), tab.begin() + hole_at);
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void **)&il->d_tab, tab.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(il->d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_error(LDPC_EHIP, "ldpc_interleaver_create_on: %s", hipGetErrorString(e)); ldpc_interleaver_destroy(il); return nullptr; }
+    il->tab.pos = il->d_tab; il->tab.holes = il->d_tab + hole_at; il->tab.n_tx = n_tx; il->tab.N = N; il->tab.n_holes = il->n_holes;
+    return il;
+}
+
+void ldpc_interleaver_destroy(ldpc_interleaver *il) {
+    if (!il) return;
+    if (il->d_tab) { (void)hipSetDevice(il->device); hipFree(il->d_tab); }
+    delete il;
+}
+
+static int llr_elem(int llr_fmt) { return llr_fmt == LDPC_LLR_F32 ? 4 : llr_fmt == LDPC_LLR_F16 ? 2 : 1; }
+
+// the calling thread's device, which must be the table's
+static int il_device(const char *what, const ldpc_interleaver *il) {
+    const int device = current_device();
+    if (device < 0) return set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded");
+    if (il->device != device) return set_error(LDPC_EINVAL, "%s: the interleaver lives on device %d, the calling thread's device is %d", what, il->device, device);
+    HIPCHK(hipSetDevice(device));
+    return LDPC_OK;
+}
+
+int ldpc_demap_dev_il(const ldpc_modulation *mod, const ldpc_interleaver *il, int batch, const float *d_sym, double noise_var, void *d_llr, int llr_fmt, float qscale,
+                      void *stream) {
+    if (!mod || !il || !d_sym || !d_llr) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: null argument");
+    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: bad dimensions (batch=%d)", batch);
+    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: noise_var must be finite and > 0");
+    int rc = check_llr_out("ldpc_demap_dev_il", llr_fmt, qscale);
+    if (rc != LDPC_OK) return rc;
+    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0)
+        return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: samples must be 8-byte aligned and LLRs aligned to their element");
+    const float inv = (float)(1.0 / (2.0 * noise_var));
+    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
+    if ((rc = il_device("ldpc_demap_dev_il", il)) != LDPC_OK) return rc;
+    if (mod->b) return ldpc::demap_il_product_launch((hipStream_t)stream, mod->ax, mod->b, il->tab, batch, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    return ldpc::demap_il_launch((hipStream_t)stream, mod->tab, mod->m, il->tab, batch, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+}
+
+int ldpc_interleave_bits_dev(const ldpc_interleaver *il, int batch, const void *d_codewords, int cw_fmt, void *d_tx_bits, int tx_fmt, void *stream) {
+    if (!il || !d_codewords || !d_tx_bits) return set_error(LDPC_EINVAL, "ldpc_interleave_bits_dev: null argument");
+    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_interleave_bits_dev: bad dimensions (batch=%d)", batch);
+    if ((cw_fmt != LDPC_BITS_BYTES && cw_fmt != LDPC_BITS_PACKED) || (tx_fmt != LDPC_BITS_BYTES && tx_fmt != LDPC_BITS_PACKED))
+        return set_error(LDPC_EINVAL, "ldpc_interleave_bits_dev: unknown bit format (LDPC_BITS_BYTES = 0, LDPC_BITS_PACKED = 1)");
+    const int rc = il_device("ldpc_interleave_bits_dev", il);
+    if (rc != LDPC_OK) return rc;
+    return ldpc::interleave_bits_launch((hipStream_t)stream, il->tab, batch, (const uint8_t *)d_codewords, cw_fmt == LDPC_BITS_PACKED, (uint8_t *)d_tx_bits,
+                                        tx_fmt == LDPC_BITS_PACKED);
+}
+
+int ldpc_deinterleave_llr_dev(const ldpc_interleaver *il, int batch, const void *d_llr_tx, void *d_llr, int llr_fmt, void *stream) {
+    if (!il || !d_llr_tx || !d_llr) return set_error(LDPC_EINVAL, "ldpc_deinterleave_llr_dev: null argument");
+    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_deinterleave_llr_dev: bad dimensions (batch=%d)", batch);
+    int rc = check_llr_out("ldpc_deinterleave_llr_dev", llr_fmt, 0.f);
+    if (rc != LDPC_OK) return rc;
+    if ((uintptr_t)d_llr_tx % llr_elem(llr_fmt) != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0)
+        return set_error(LDPC_EINVAL, "ldpc_deinterleave_llr_dev: LLRs must be aligned to their element");
+    if ((rc = il_device("ldpc_deinterleave_llr_dev", il)) != LDPC_OK) return rc;
+    return ldpc::deinterleave_llr_launch((hipStream_t)stream, il->tab, batch, d_llr_tx, d_llr, llr_elem(llr_fmt));
+}
+
+// what the frame source's paths ask of a table: its lengths are the source's, it lives on the source's device, and it is a permutation
+// of the transmitted prefix (the source's packed codewords are cut at n_tx)
+static int sim_il_check(const char *what, const ldpc_sim *sim, const ldpc_interleaver *il) {
+    if (!il) return set_error(LDPC_EINVAL, "%s: null interleaver", what);
+    if (il->n_tx != sim->dev.n_tx || il->N != sim->dev.N)
+        return set_error(LDPC_EINVAL, "%s: the interleaver is for n_tx = %d, N = %d, the frame source for n_tx = %d, N = %d", what, il->n_tx, il->N, sim->dev.n_tx, sim->dev.N);
+    if (il->max_pos >= sim->dev.n_tx)
+        return set_error(LDPC_EINVAL, "%s: the table reaches position %d, the frame source's codewords are cut at n_tx = %d", what, il->max_pos, sim->dev.n_tx);
+    if (il->device != sim->device) return set_error(LDPC_EINVAL, "%s: the interleaver lives on device %d, the frame source on device %d", what, il->device, sim->device);
+    return LDPC_OK;
+}
+
+int ldpc_sim_transmit_il(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db,
+                         const void *d_msg_in, int msg_fmt, float *d_sym, uint8_t *d_msg, void *stream) {
+    int rc = sim_mod_check("ldpc_sim_transmit_il", sim, mod, batch, d_msg_in, msg_fmt, d_sym);
+    if (rc != LDPC_OK) return rc;
+    if ((rc = sim_il_check("ldpc_sim_transmit_il", sim, il)) != LDPC_OK) return rc;
+    if ((uintptr_t)d_sym % 8 != 0) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il: samples must be 8-byte aligned");
+    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
+    if (!(nv >= 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il: Eb/N0 gives no finite noise variance");
+    HIPCHK(hipSetDevice(sim->device));
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = sim_mod_codewords("ldpc_sim_transmit_il", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
+    const int PB = (sim->dev.n_tx + 7) / 8;
+    if (mod->b) return ldpc::product_transmit_il_launch(st, mod->ax, mod->b, il->tab, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), d_sym);
+    return ldpc::mod_transmit_il_launch(st, mod->tab, mod->m, il->tab, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), d_sym);
+}
+
+int ldpc_sim_generate_mod_il(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db,
+                             const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt, float qscale, uint8_t *d_msg, void *stream) {
+    int rc = sim_mod_check("ldpc_sim_generate_mod_il", sim, mod, batch, d_msg_in, msg_fmt, d_llr);
+    if (rc != LDPC_OK) return rc;
+    if ((rc = sim_il_check("ldpc_sim_generate_mod_il", sim, il)) != LDPC_OK) return rc;
+    if ((rc = check_llr_out("ldpc_sim_generate_mod_il", llr_fmt, qscale)) != LDPC_OK) return rc;
+    if ((uintptr_t)d_llr % llr_elem(llr_fmt) != 0) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il: LLRs must be aligned to their element");
+    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
+    if (!(nv > 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il: Eb/N0 gives no finite noise variance > 0");
+    const float inv = (float)(1.0 / (2.0 * nv));
+    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il: 1 / (2 sigma^2) does not fit a float32 at %g dB", ebn0_db);
+    HIPCHK(hipSetDevice(sim->device));
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = sim_mod_codewords("ldpc_sim_generate_mod_il", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
+    const int PB = (sim->dev.n_tx + 7) / 8;
+    if (mod->b)
+        return ldpc::product_generate_il_launch(st, mod->ax, mod->b, il->tab, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), inv, d_llr, llr_fmt,
+                                                qscale == 0.f ? 4.0f : qscale);
+    return ldpc::mod_generate_il_launch(st, mod->tab, mod->m, il->tab, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), inv, d_llr, llr_fmt,
+                                        qscale == 0.f ? 4.0f : qscale);
 }
 
 int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream) {

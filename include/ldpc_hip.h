@@ -466,7 +466,8 @@ int ldpc_sim_generate_from(ldpc_sim *sim, uint64_t seed, uint64_t first_frame, i
  * Modulation object (host only): 2^m points (I, Q), m = 1..6 bits per symbol as a table (product constellations, below, reach
  * m = 12).  LABELLING: symbol s of a frame carries codeword bits
  * m s .. m s + m - 1; its label is sum_j bit(m s + j) << (m - 1 - j) -- the first bit is the MSB -- and the label is the index into
- * `points`.  Bits at positions >= n_tx pad as 0.  There is no bit interleaver: a caller permutes.  Two equal points are allowed.
+ * `points`.  Bits at positions >= n_tx pad as 0.  The bits are taken in codeword order; any other order is a bit interleaver
+ * (ldpc_interleaver, below) and the _il entry points.  Two equal points are allowed.
  * LDPC_EINVAL and NULL for m outside 1..6, a null table or a non-finite point.
  * Built-ins, by formula (NO claim is made that these are any standard's labellings or, for APSK, ring ratios -- a caller who needs a
  * standard's constellation passes its own table):
@@ -487,8 +488,8 @@ int ldpc_modulation_symbols(const ldpc_modulation *mod, int n_tx);   /* symbols 
 /* PRODUCT constellations, up to 4096 points: an I-axis level set times a Q-axis level set, b = 1..6 bits an axis, m = 2 b bits per
  * symbol.  The labelling rule above holds; of a symbol's m bits the first b (MSB first) are the index into levels_i and the next b the
  * index into levels_q: label = (iI << b) | iQ, and the point of that label is (levels_i[iI], levels_q[iQ]).  The two axes may hold
- * different level sets; non-uniform levels and unequal I/Q scaling are allowed.  Different bits per axis and labellings that interleave
- * I and Q bits are not provided: a caller permutes.  LDPC_EINVAL and NULL for b outside 1..6, a null table or a non-finite level.
+ * different level sets; non-uniform levels and unequal I/Q scaling are allowed.  Different bits per axis are not provided.  A labelling that
+ * interleaves I and Q bits is a bit interleaver's table (ldpc_interleaver, below).  LDPC_EINVAL and NULL for b outside 1..6, a null table or a non-finite level.
  * For such an object
  *   ldpc_modulation_bits    returns 2 b;
  *   ldpc_modulation_points  returns 4^b and writes the materialised table pt[(iI << b) | iQ] = (levels_i[iI], levels_q[iQ]);
@@ -522,7 +523,8 @@ int ldpc_modulation_axis_levels(const ldpc_modulation *mod, float *levels_i, flo
  *                 read for LDPC_LLR_I8 only; 0 = 4.0; negative or non-finite: LDPC_EINVAL.
  * A NaN sample gives NaN LLRs (int8: 0, an erasure).  Runs on the calling thread's device, enqueued on `stream`, not synchronised.
  * LDPC_EINVAL: a null pointer, batch <= 0, n_tx <= 0 or > N, an unknown format, such a noise_var or qscale, a misaligned buffer.
- * Exact log-MAP, interleavers and fp16 samples are not provided. */
+ * Exact log-MAP and fp16 samples are not provided; a bit interleaver between codeword order and transmitted order is
+ * ldpc_demap_dev_il, below. */
 enum { LDPC_LLR_F32 = 0, LDPC_LLR_F16 = 1, LDPC_LLR_I8 = 2 };   /* the values llr_f16 takes in the packed entry points */
 int ldpc_demap_dev(const ldpc_modulation *mod, int batch, int n_tx, int N, const float *d_sym, double noise_var, void *d_llr, int llr_fmt,
                    float qscale, void *stream);
@@ -548,6 +550,55 @@ int ldpc_sim_transmit(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, 
  * (2 / sigma^2) (x + sigma z), and it draws its noise from stream 2.  It is not a replacement for ldpc_sim_generate. */
 int ldpc_sim_generate_mod(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db,
                           const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt, float qscale, uint8_t *d_msg, void *stream);
+/* ---- bit interleaver: a position table between codeword order and transmitted order, fused into the mapper and the demapper.
+ * Transmitted bit t is codeword bit pos[t], t = 0 .. n_tx - 1; symbol s carries transmitted bits m s .. m s + m - 1, the first one the
+ * MSB of its label, exactly the labelling rule above (bits t >= n_tx of the last symbol pad as 0).  pos is injective into 0 .. N - 1,
+ * 1 <= n_tx <= N.  Codeword positions that no pos[t] names are PUNCTURED, anywhere in the codeword: they are not sent and their LLR
+ * is 0.  The identity table (n_tx entries) is the behaviour of the entry points without _il, bit for bit.
+ * The object holds pos, and the sorted list of the N - n_tx punctured positions, in device memory on `device`.  The arguments are
+ * checked before the device is touched: LDPC_EINVAL and NULL for a null table, n_tx < 1 or n_tx > N, an entry outside 0 .. N - 1, a
+ * repeated entry; only then LDPC_ENODEVICE (device < 0, no such device) or LDPC_EHIP.
+ * An I/Q-alternating labelling of a product constellation of b bits an axis (m = 2 b) is the table
+ *   pos'[m s + 2 j] = pos[m s + j],  pos'[m s + 2 j + 1] = pos[m s + b + j],  j = 0 .. b - 1,
+ * of any table pos with m | n_tx (the identity included). */
+typedef struct ldpc_interleaver ldpc_interleaver;
+ldpc_interleaver *ldpc_interleaver_create_on(int device, int n_tx, int N, const int32_t *pos /* [n_tx] */);
+void ldpc_interleaver_destroy(ldpc_interleaver *il);
+int ldpc_interleaver_dims(const ldpc_interleaver *il, int *n_tx, int *N);            /* either pointer may be NULL */
+int ldpc_interleaver_positions(const ldpc_interleaver *il, int32_t *pos /* [n_tx], may be NULL */);   /* returns n_tx */
+/* The block interleaver's table, by formula, on the host (no device; NO claim is made that it is any standard's table): codeword bit
+ * i = c rows + u is written into column c of a rows x cols matrix at row (u + twist[c]) mod rows, and the matrix is read row by row,
+ * taking the columns in the order order[0 .. cols - 1]:
+ *   pos[r cols + j] = c rows + ((r - twist[c]) mod rows),  c = order[j].
+ * twist NULL = no twist, order NULL = the identity.  With cols = m, symbol r takes one bit from each column.  LDPC_EINVAL for rows < 1,
+ * cols < 1, rows * cols overflowing an int, a twist outside 0 .. rows - 1, an order that is not a permutation of 0 .. cols - 1, a null pos. */
+int ldpc_interleaver_block_positions(int rows, int cols, const int32_t *twist /* [cols] or NULL */, const int32_t *order /* [cols] or NULL */,
+                                     int32_t *pos /* [rows * cols] */);
+/* ldpc_demap_dev through the table, in one kernel with no memset before it: per symbol exactly the rule of ldpc_demap_dev; the LLR of
+ * transmitted bit t goes to element pos[t] of its row of d_llr [batch][N], the punctured positions get 0, LLRs of pad bits are not
+ * written: every element is written exactly once.  n_tx and N are the table's; d_sym [batch][ceil(n_tx / m)][2].  LDPC_EINVAL as
+ * ldpc_demap_dev, and for a null `il` or one that lives on another device than the calling thread's.  A block table of m columns keeps
+ * the stores of a wave consecutive per bit index; a random table scatters single elements. */
+int ldpc_demap_dev_il(const ldpc_modulation *mod, const ldpc_interleaver *il, int batch, const float *d_sym, double noise_var, void *d_llr,
+                      int llr_fmt, float qscale, void *stream);
+/* ldpc_sim_transmit with the label of symbol s gathered from codeword bits pos[m s + j]; the noise (Philox counters, Box-Muller, stream
+ * 2), sigma (R = k / n_tx) and the symbol rule are untouched.  The table's n_tx and N must be the frame source's n_tx and its code's N,
+ * every pos[t] must be < n_tx (the source's codewords are cut at n_tx: the table is a permutation of the transmitted prefix) and it
+ * must live on the source's device: LDPC_EINVAL otherwise, and for a null `il`. */
+int ldpc_sim_transmit_il(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, uint64_t seed, uint64_t first_frame, int batch,
+                         double ebn0_db, const void *d_msg_in, int msg_fmt, float *d_sym, uint8_t *d_msg, void *stream);
+/* ldpc_sim_transmit_il and ldpc_demap_dev_il(.., ldpc_sim_noise_var(..), ..) in ONE kernel, bit for bit; otherwise as
+ * ldpc_sim_generate_mod, which it equals bit for bit with the identity table. */
+int ldpc_sim_generate_mod_il(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, uint64_t seed, uint64_t first_frame, int batch,
+                             double ebn0_db, const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt, float qscale, uint8_t *d_msg, void *stream);
+/* The table alone, for a caller's own modulator or demapper (device pointers, the calling thread's device = the table's, enqueued on
+ * `stream`, not synchronised; inputs and outputs must not overlap).
+ * ldpc_interleave_bits_dev: codewords [batch][N] as LDPC_BITS_BYTES or LDPC_BITS_PACKED (rows of ceil(N / 8) bytes) -> transmitted
+ * bits [batch][n_tx] in either format (rows of ceil(n_tx / 8) bytes, pad bits 0), bit t = codeword bit pos[t].
+ * ldpc_deinterleave_llr_dev: d_llr_tx [batch][n_tx] in transmitted order -> d_llr [batch][N], element pos[t] = element t, 0 at the
+ * punctured positions; the same element type (llr_fmt) in and out, nothing is requantised. */
+int ldpc_interleave_bits_dev(const ldpc_interleaver *il, int batch, const void *d_codewords, int cw_fmt, void *d_tx_bits, int tx_fmt, void *stream);
+int ldpc_deinterleave_llr_dev(const ldpc_interleaver *il, int batch, const void *d_llr_tx, void *d_llr, int llr_fmt, void *stream);
 /* the receive side: message bit i of a frame = decoded bit msg_pos[i] of d_bits [batch][N] bytes (bit 0 of each), written in
  * msg_fmt.  With the systematic form message and parity bits interleave; any source qualifies, LDPC_ENCODER_NONE included. */
 int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream);

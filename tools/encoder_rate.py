@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only | --messages caller | --modulation qpsk|8psk|table32|64qam|256qam|1024qam|4096qam|grid64] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
+"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only | --messages caller | --modulation qpsk|8psk|table32|64qam|256qam|1024qam|4096qam|grid64 [--interleaver none|block|random]] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
 sim.hip sim_parity_qc_kernel) against the dense packed GF(2) mat-vec of the expanded generator (Orig.hs:25-26), on the shipped AR4JA
 codes: the encoder alone (ldpc_sim_encode_batch: messages + parity -> codeword bytes) and the whole frame source
 (ldpc_sim_generate: + BPSK, AWGN, LLRs).  HIP events on the launch stream, median of 7.
@@ -22,7 +22,13 @@ Where a lane's m LLRs fit no vector store (8psk, table32) the demapper stores th
 recorded in profiles/r14_modulation.txt and is not in the library.
 --modulation 64qam|256qam|1024qam|4096qam: the same lines for the product built-ins (csrc/demap_product.hip, csrc/sim_mod_product.hip; no bar).
 grid64: the 8 x 8 grid as a 64-point table object.  64qam also runs that table in the same process, the two alternating, and prints the one
-bar of product constellations: ldpc_demap_dev -> f32 and ldpc_sim_generate_mod -> f32 on the product object no slower than on the table."""
+bar of product constellations: ldpc_demap_dev -> f32 and ldpc_sim_generate_mod -> f32 on the product object no slower than on the table.
+--interleaver none|block|random (with --modulation): the bit interleaver (csrc/demap_il.hip, csrc/sim_mod_il.hip) on the same source, after the
+lines above.  none: the identity table; block: the block table of floor(n_tx / m) rows and m columns over the first rows * m bits, the last
+n_tx mod m bits in place; random: a seeded random permutation of the transmitted prefix.  Into float32 and into int8, two rounds of the legs
+alternating in this process, each leg one warm-up and the median of 5: ldpc_demap_dev | ldpc_demap_dev_il | ldpc_demap_dev into a
+[batch][n_tx] buffer + ldpc_deinterleave_llr_dev (the two-pass baseline; its LLRs are compared with the fused ones bit for bit), and
+ldpc_sim_generate_mod | ldpc_sim_generate_mod_il | ldpc_sim_transmit_il + ldpc_demap_dev_il (the only unfused way to the same LLRs).  No bar."""
 import os
 import sys
 
@@ -231,7 +237,7 @@ def caller_leg(B, dev, st):
 PRODUCT_BUILTINS = ("64qam", "256qam", "1024qam", "4096qam")
 
 
-def modulation_leg(which, B, dev, st):
+def modulation_leg(which, B, dev, st, interleaver=None):
     import numpy as np
     from tests import modulation_spec as ms
     if which in PRODUCT_BUILTINS:
@@ -292,13 +298,81 @@ def modulation_leg(which, B, dev, st):
             print(f"  {call:30s} product object {p[0]:8.3f} {p[1]:8.3f} ms | 64-point table (grid64) {t[0]:8.3f} {t[1]:8.3f} ms | product / table = {min(p) / min(t):.3f}"
                   f" ({'within' if max(p) <= min(t) else 'MISSES'} the bar: no slower)", flush=True)
         tab.close()
+    if interleaver:
+        sim.transmit(mod, 1, 0, B, 2.0, sym.data_ptr(), None, "bytes", None, s_)
+        torch.cuda.synchronize()
+        del llr, q, two
+        interleaver_leg(interleaver, mod, sim, B, n_tx, N, sym, nv, dev, st)
     mod.close(); ecc.close()
+
+
+def interleaver_leg(kind, mod, sim, B, n_tx, N, sym, nv, dev, st):
+    import numpy as np
+    m, s_ = mod.bits, st.cuda_stream
+    if kind == "none":
+        pos = np.arange(n_tx)
+    elif kind == "block":
+        rows = n_tx // m
+        pos = np.concatenate([E.Interleaver.block_positions(rows, m), np.arange(rows * m, n_tx)])
+    else:
+        pos = np.random.default_rng(1).permutation(n_tx)
+    il = E.Interleaver(pos, N)
+    ns = mod.symbols(n_tx)
+    print(f"  interleaver {kind}: n_tx = {n_tx}, N = {N}, {N - n_tx} punctured; two rounds, legs alternating, each one warm-up + median of 5 (ms):", flush=True)
+    for fmt, dt, size in (("f32", torch.float32, 4), ("i8", torch.int8, 1)):
+        out = torch.empty((B, N), dtype=dt, device=dev)
+        two = torch.empty((B, N), dtype=dt, device=dev)
+        mid = torch.empty((B, n_tx), dtype=dt, device=dev)
+
+        def two_pass():
+            E.demap(mod, B, n_tx, n_tx, sym.data_ptr(), nv, mid.data_ptr(), fmt, 4.0, s_)
+            E.deinterleave_llr(il, B, mid.data_ptr(), two.data_ptr(), fmt, s_)
+
+        def unfused():
+            sim.transmit_il(mod, il, 1, 0, B, 2.0, sym.data_ptr(), None, "bytes", None, s_)
+            E.demap_il(mod, il, B, sym.data_ptr(), nv, two.data_ptr(), fmt, 4.0, s_)
+
+        demap_legs = (("ldpc_demap_dev", lambda: E.demap(mod, B, n_tx, N, sym.data_ptr(), nv, out.data_ptr(), fmt, 4.0, s_)),
+                      ("ldpc_demap_dev_il", lambda: E.demap_il(mod, il, B, sym.data_ptr(), nv, out.data_ptr(), fmt, 4.0, s_)),
+                      ("demap + deinterleave_llr", two_pass))
+        gen_legs = (("ldpc_sim_generate_mod", lambda: sim.generate_mod(mod, 1, 0, B, 2.0, out.data_ptr(), fmt, 4.0, None, "bytes", None, s_)),
+                    ("ldpc_sim_generate_mod_il", lambda: sim.generate_mod_il(mod, il, 1, 0, B, 2.0, out.data_ptr(), fmt, 4.0, None, "bytes", None, s_)),
+                    ("transmit_il + demap_il", unfused))
+        for legs, what in ((demap_legs, "demap"), (gen_legs, "generate_mod")):
+            res = {name: [] for name, _ in legs}
+            for _ in range(2):
+                for name, fn in legs:
+                    res[name].append(timed(fn, st, 5))
+            base, fused, other = (res[name] for name, _ in legs)
+            nbytes = B * (ns * 8 + N * size)
+            extra = f" | {nbytes / 1e6:.1f} MB moved: {nbytes / min(base) / 1e9:.2f} and {nbytes / min(fused) / 1e9:.2f} TB/s" if what == "demap" else ""
+            print(f"  -> {fmt:3s} " + " | ".join(f"{name} {t[0]:8.3f} {t[1]:8.3f}" for name, t in res.items())
+                  + f" | fused / plain = {min(fused) / min(base):.3f}, fused / two-pass = {min(fused) / min(other):.3f}{extra}", flush=True)
+            if what == "demap":
+                E.demap_il(mod, il, B, sym.data_ptr(), nv, out.data_ptr(), fmt, 4.0, s_)
+                two_pass()
+            else:
+                unfused()
+                sim.generate_mod_il(mod, il, 1, 0, B, 2.0, out.data_ptr(), fmt, 4.0, None, "bytes", None, s_)
+            torch.cuda.synchronize()
+            iv = torch.int32 if fmt == "f32" else torch.int8
+            assert torch.equal(out.view(iv), two.view(iv)), f"{what}: the fused LLRs differ from the two-pass ones ({fmt})"
+        del out, two, mid
+    print(f"  fused = two-pass bit for bit (demap_il = demap + deinterleave_llr; generate_mod_il = transmit_il + demap_il)", flush=True)
+    il.close()
 
 
 def main():
     argv = sys.argv[1:]
     messages = None
     modulation = None
+    interleaver = None
+    if "--interleaver" in argv:
+        i = argv.index("--interleaver")
+        interleaver = argv[i + 1] if i + 1 < len(argv) else ""
+        del argv[i:i + 2]
+        if interleaver not in ("none", "block", "random") or "--modulation" not in argv:
+            sys.exit("--interleaver takes one value: none, block or random, and goes with --modulation")
     if "--modulation" in argv:
         i = argv.index("--modulation")
         modulation = argv[i + 1] if i + 1 < len(argv) else ""
@@ -318,7 +392,7 @@ def main():
     st = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(st)
     if modulation:
-        modulation_leg(modulation, B, dev, st)
+        modulation_leg(modulation, B, dev, st, interleaver)
         return
     if messages:
         caller_leg(B, dev, st)
