@@ -29,6 +29,10 @@ class CtxConfig(C.Structure):   # ldpc_ctx_config
     _fields_ = [("struct_size", C.c_size_t), ("device", C.c_int), ("variant", C.c_int), ("dtype", C.c_int), ("max_batch", C.c_int),
                 ("path", C.c_int), ("schedule", C.c_int), ("sum_order", C.c_int), ("llr_qscale", C.c_float), ("cn_scale", C.c_float), ("cn_offset", C.c_float)]
 
+class FadingStruct(C.Structure):   # ldpc_fading
+    _fields_ = [("struct_size", C.c_size_t), ("block", C.c_int), ("k_factor", C.c_float)]
+
+
 # every symbol include/ldpc_hip.h declares (tests/test_abi.py checks the library exports them all)
 ABI_SYMBOLS = [
     "ldpc_init", "ldpc_shutdown", "ldpc_current_device", "ldpc_ctx_create_on", "ldpc_sim_create_on", "ldpc_ctx_create_cfg", "ldpc_ctx_schedule", "ldpc_ctx_code", "ldpc_ctx_max_batch", "ldpc_ctx_device",
@@ -51,6 +55,7 @@ ABI_SYMBOLS = [
     "ldpc_modulation_symbols", "ldpc_modulation_create_product", "ldpc_modulation_axis_levels", "ldpc_demap_dev", "ldpc_sim_noise_var", "ldpc_sim_transmit", "ldpc_sim_generate_mod",
     "ldpc_interleaver_create_on", "ldpc_interleaver_destroy", "ldpc_interleaver_dims", "ldpc_interleaver_positions", "ldpc_interleaver_block_positions",
     "ldpc_demap_dev_il", "ldpc_sim_transmit_il", "ldpc_sim_generate_mod_il", "ldpc_interleave_bits_dev", "ldpc_deinterleave_llr_dev",
+    "ldpc_demap_dev_il_csi", "ldpc_sim_transmit_il_fading", "ldpc_sim_generate_mod_il_fading",
     "ldpc_matrix_load", "ldpc_matrix_load_mackay", "ldpc_matrix_destroy", "ldpc_matrix_info", "ldpc_matrix_dense",
     "ldpc_matrix_qc_offsets", "ldpc_code_from_matrix",
     "ldpc_ecc_create", "ldpc_ecc_destroy", "ldpc_ecc_name", "ldpc_ecc_message_length", "ldpc_ecc_codeword_length",
@@ -271,6 +276,9 @@ def lib():
     L.ldpc_sim_generate_mod_il.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, C.c_float, vp, vp]
     L.ldpc_interleave_bits_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]
     L.ldpc_deinterleave_llr_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
+    L.ldpc_demap_dev_il_csi.argtypes = [vp, vp, C.c_int, vp, vp, C.c_double, vp, C.c_int, C.c_float, vp]
+    L.ldpc_sim_transmit_il_fading.argtypes = [vp, vp, vp, C.POINTER(FadingStruct), C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp, vp]
+    L.ldpc_sim_generate_mod_il_fading.argtypes = [vp, vp, vp, C.POINTER(FadingStruct), C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, C.c_float, vp, vp, vp]
     L.ldpc_matrix_qc_words.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.ldpc_matrix_rank.argtypes = [vp]
     L.ldpc_matrix_load.restype = vp
@@ -947,6 +955,28 @@ def demap_il(mod: Modulation, il: Interleaver, batch, d_sym_ptr, noise_var, d_ll
     check(lib().ldpc_demap_dev_il(_h(mod), _h(il), int(batch), d_sym_ptr, float(noise_var), d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), stream))
 
 
+def demap_il_csi(mod: Modulation, il: Interleaver, batch, d_sym_ptr, d_gain_ptr, noise_var, d_llr_ptr, llr_fmt="f32", qscale=0.0, stream=None):
+    """ldpc_demap_dev_il_csi: demap_il() with the power gain of every symbol, d_gain [batch][n_sym] float32: the noise variance of symbol
+    s is noise_var / gain, its LLRs are scaled by float32(1 / (2 noise_var)) * gain"""
+    check(lib().ldpc_demap_dev_il_csi(_h(mod), _h(il), int(batch), d_sym_ptr, d_gain_ptr, float(noise_var), d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), stream))
+
+
+class Fading:
+    """ldpc_fading: block fading with `block` symbols per block and the Rician factor k_factor (linear; 0 = Rayleigh).  A plain value:
+    nothing is checked here, the entry points judge it.  struct_size: for the tests of that field"""
+
+    def __init__(self, block=1, k_factor=0.0, struct_size=None):
+        self.block, self.k_factor = int(block), float(k_factor)
+        self.struct = FadingStruct(C.sizeof(FadingStruct) if struct_size is None else int(struct_size), self.block, self.k_factor)
+
+    def _ref(self):
+        return C.byref(self.struct)
+
+
+def _fad(f):
+    return f._ref() if f is not None else None
+
+
 def interleave_bits(il: Interleaver, batch, d_cw_ptr, d_tx_ptr, cw_fmt="bytes", tx_fmt="bytes", stream=None):
     """ldpc_interleave_bits_dev: codewords [batch][N] ("bytes", or "packed" rows of ceil(N / 8) bytes) -> transmitted bits [batch][n_tx]"""
     check(lib().ldpc_interleave_bits_dev(_h(il), int(batch), d_cw_ptr, Sim._bits_fmt(cw_fmt), d_tx_ptr, Sim._bits_fmt(tx_fmt), stream))
@@ -1063,6 +1093,19 @@ class Sim:
         """transmit_il() and demap_il() in one kernel (ldpc_sim_generate_mod_il)"""
         check(lib().ldpc_sim_generate_mod_il(self._h, _h(mod), _h(il), int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_in_ptr, self._bits_fmt(msg_fmt),
                                              d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), d_msg_ptr, stream))
+
+    def transmit_il_fading(self, mod: "Modulation", il: "Interleaver", fad: "Fading", seed, first_frame, batch, ebn0_db, d_sym_ptr, d_gain_ptr=None, d_msg_in_ptr=None,
+                           msg_fmt="bytes", d_msg_ptr=None, stream=None):
+        """transmit_il() over a fading channel (ldpc_sim_transmit_il_fading): the equalised samples, and the power gains [batch][n_sym]
+        float32 at d_gain_ptr if given"""
+        check(lib().ldpc_sim_transmit_il_fading(self._h, _h(mod), _h(il), _fad(fad), int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_in_ptr,
+                                                self._bits_fmt(msg_fmt), d_sym_ptr, d_gain_ptr, d_msg_ptr, stream))
+
+    def generate_mod_il_fading(self, mod: "Modulation", il: "Interleaver", fad: "Fading", seed, first_frame, batch, ebn0_db, d_llr_ptr, llr_fmt="f32", qscale=0.0,
+                               d_gain_ptr=None, d_msg_in_ptr=None, msg_fmt="bytes", d_msg_ptr=None, stream=None):
+        """transmit_il_fading() and demap_il_csi() in one kernel (ldpc_sim_generate_mod_il_fading)"""
+        check(lib().ldpc_sim_generate_mod_il_fading(self._h, _h(mod), _h(il), _fad(fad), int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_in_ptr,
+                                                    self._bits_fmt(msg_fmt), d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), d_gain_ptr, d_msg_ptr, stream))
 
     def tally(self, batch, d_bits_ptr, d_iters_ptr, d_tally_ptr, stream=None):
         check(lib().ldpc_sim_tally(self._h, int(batch), d_bits_ptr, d_iters_ptr, d_tally_ptr, stream))

@@ -14,6 +14,7 @@
 #include "backend.h"
 #include "demap.h"
 #include "interleaver.h"
+#include "fading.h"
 #include "jit.h"
 #include "sim.h"
 #include "systematic.h"
@@ -1560,6 +1561,82 @@ int ldpc_sim_generate_mod_il(ldpc_sim *sim, const ldpc_modulation *mod, const ld
                                                 qscale == 0.f ? 4.0f : qscale);
     return ldpc::mod_generate_il_launch(st, mod->tab, mod->m, il->tab, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), inv, d_llr, llr_fmt,
                                         qscale == 0.f ? 4.0f : qscale);
+}
+
+// ---- the fading channel and the per-symbol channel state (csrc/fading.h): the demapper with a gain per symbol, the modulated path
+// with gains drawn per block, the two fused
+// the public descriptor checked and turned into the kernel argument
+static int fade_arg(const char *what, const ldpc_fading *fad, ldpc::FadeArg &out) {
+    if (!fad) return set_error(LDPC_EINVAL, "%s: null ldpc_fading", what);
+    if (fad->struct_size < offsetof(ldpc_fading, k_factor) + sizeof(fad->k_factor))
+        return set_error(LDPC_EINVAL, "%s: ldpc_fading.struct_size %zu does not cover block and k_factor", what, fad->struct_size);
+    if (fad->block < 1) return set_error(LDPC_EINVAL, "%s: %d symbols per fading block (must be >= 1)", what, fad->block);
+    if (!(fad->k_factor >= 0.f) || !std::isfinite(fad->k_factor)) return set_error(LDPC_EINVAL, "%s: the Rician K must be finite and >= 0", what);
+    const double K = (double)fad->k_factor;
+    out.block = fad->block;
+    out.mu = (float)sqrt(K / (K + 1.0));
+    out.sd = (float)sqrt(1.0 / (2.0 * (K + 1.0)));
+    return LDPC_OK;
+}
+
+int ldpc_demap_dev_il_csi(const ldpc_modulation *mod, const ldpc_interleaver *il, int batch, const float *d_sym, const float *d_gain, double noise_var, void *d_llr,
+                          int llr_fmt, float qscale, void *stream) {
+    if (!mod || !il || !d_sym || !d_gain || !d_llr) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: null argument");
+    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: bad dimensions (batch=%d)", batch);
+    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: noise_var must be finite and > 0");
+    int rc = check_llr_out("ldpc_demap_dev_il_csi", llr_fmt, qscale);
+    if (rc != LDPC_OK) return rc;
+    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0)
+        return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: samples must be 8-byte aligned, gains 4-byte aligned and LLRs aligned to their element");
+    const float inv = (float)(1.0 / (2.0 * noise_var));
+    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
+    if ((rc = il_device("ldpc_demap_dev_il_csi", il)) != LDPC_OK) return rc;
+    if (mod->b) return ldpc::demap_csi_product_launch((hipStream_t)stream, mod->ax, mod->b, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    return ldpc::demap_csi_launch((hipStream_t)stream, mod->tab, mod->m, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+}
+
+int ldpc_sim_transmit_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, const ldpc_fading *fad, uint64_t seed, uint64_t first_frame, int batch,
+                                double ebn0_db, const void *d_msg_in, int msg_fmt, float *d_sym, float *d_gain, uint8_t *d_msg, void *stream) {
+    int rc = sim_mod_check("ldpc_sim_transmit_il_fading", sim, mod, batch, d_msg_in, msg_fmt, d_sym);
+    if (rc != LDPC_OK) return rc;
+    if ((rc = sim_il_check("ldpc_sim_transmit_il_fading", sim, il)) != LDPC_OK) return rc;
+    ldpc::FadeArg fa;
+    if ((rc = fade_arg("ldpc_sim_transmit_il_fading", fad, fa)) != LDPC_OK) return rc;
+    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il_fading: samples must be 8-byte aligned, gains 4-byte aligned");
+    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
+    if (!(nv >= 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il_fading: Eb/N0 gives no finite noise variance");
+    HIPCHK(hipSetDevice(sim->device));
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = sim_mod_codewords("ldpc_sim_transmit_il_fading", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
+    const int PB = (sim->dev.n_tx + 7) / 8;
+    if (mod->b) return ldpc::fading_product_transmit_launch(st, mod->ax, mod->b, il->tab, fa, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), d_sym, d_gain);
+    return ldpc::fading_transmit_launch(st, mod->tab, mod->m, il->tab, fa, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), d_sym, d_gain);
+}
+
+int ldpc_sim_generate_mod_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, const ldpc_fading *fad, uint64_t seed, uint64_t first_frame,
+                                    int batch, double ebn0_db, const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt, float qscale, float *d_gain, uint8_t *d_msg,
+                                    void *stream) {
+    int rc = sim_mod_check("ldpc_sim_generate_mod_il_fading", sim, mod, batch, d_msg_in, msg_fmt, d_llr);
+    if (rc != LDPC_OK) return rc;
+    if ((rc = sim_il_check("ldpc_sim_generate_mod_il_fading", sim, il)) != LDPC_OK) return rc;
+    ldpc::FadeArg fa;
+    if ((rc = fade_arg("ldpc_sim_generate_mod_il_fading", fad, fa)) != LDPC_OK) return rc;
+    if ((rc = check_llr_out("ldpc_sim_generate_mod_il_fading", llr_fmt, qscale)) != LDPC_OK) return rc;
+    if ((uintptr_t)d_llr % llr_elem(llr_fmt) != 0 || (uintptr_t)d_gain % 4 != 0)
+        return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il_fading: LLRs must be aligned to their element, gains 4-byte aligned");
+    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
+    if (!(nv > 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il_fading: Eb/N0 gives no finite noise variance > 0");
+    const float inv = (float)(1.0 / (2.0 * nv));
+    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il_fading: 1 / (2 sigma^2) does not fit a float32 at %g dB", ebn0_db);
+    HIPCHK(hipSetDevice(sim->device));
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = sim_mod_codewords("ldpc_sim_generate_mod_il_fading", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
+    const int PB = (sim->dev.n_tx + 7) / 8;
+    if (mod->b)
+        return ldpc::fading_product_generate_launch(st, mod->ax, mod->b, il->tab, fa, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), inv, d_llr, llr_fmt,
+                                                    qscale == 0.f ? 4.0f : qscale, d_gain);
+    return ldpc::fading_generate_launch(st, mod->tab, mod->m, il->tab, fa, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), inv, d_llr, llr_fmt,
+                                        qscale == 0.f ? 4.0f : qscale, d_gain);
 }
 
 int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream) {

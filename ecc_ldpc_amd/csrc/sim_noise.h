@@ -27,7 +27,7 @@ struct Philox {
 };
 
 // counter streams: 0 = message words, 1 = the BPSK source's noise (one call per four positions), 2 = the modulated path's noise (one
-// call per symbol pair)
+// call per symbol pair), 3 = fading gains (one call per pair of fading blocks: fading.h)
 // Box-Muller on two pairs of 32-bit uniforms (u1 in (0,1]); both branches of each pair are used: z[0], z[1] = cos and sin branch
 // of (r0, r1), z[2], z[3] of (r2, r3)
 static __device__ __forceinline__ void box_muller4(const uint32_t (&r)[4], float (&z)[4]) {

@@ -599,6 +599,48 @@ int ldpc_sim_generate_mod_il(ldpc_sim *sim, const ldpc_modulation *mod, const ld
  * punctured positions; the same element type (llr_fmt) in and out, nothing is requantised. */
 int ldpc_interleave_bits_dev(const ldpc_interleaver *il, int batch, const void *d_codewords, int cw_fmt, void *d_tx_bits, int tx_fmt, void *stream);
 int ldpc_deinterleave_llr_dev(const ldpc_interleaver *il, int batch, const void *d_llr_tx, void *d_llr, int llr_fmt, void *stream);
+/* ---- fading channels and per-symbol channel state, in the interleaved family (the identity table is "no interleaver").  A coherent
+ * receiver with perfect channel knowledge is modelled: the phase is taken out and the samples are delivered EQUALISED, so of the channel
+ * only the POWER gain a of a symbol appears: the noise variance per real dimension of its sample is noise_var / a.  The rules are
+ * restated in float32, one operation at a time, in tests/fading_spec.py; the kernels reproduce them bit for bit.
+ *
+ * ldpc_demap_dev_il_csi: ldpc_demap_dev_il with d_gain [batch][n_sym] float32 (4-byte aligned), the power gain of every symbol.
+ * inv = float32(1 / (2 noise_var)) as there, inv_s = fl(inv a), and the LLRs of symbol s are exactly ldpc_demap_dev_il's rule with
+ * inv_s in place of inv: a table object fl(fl(m0_j - m1_j) inv_s), a product object the per-axis form.  Everything else -- positions
+ * through the table, zeros at the punctured positions, pad bits, the formats, every element written once, no memset -- is
+ * ldpc_demap_dev_il's, and a = 1 everywhere gives its output bit for bit.  With a finite sample a = 0 gives zero LLRs (an erasure) and
+ * a NaN gain NaN LLRs (int8: 0).  A negative gain is the caller's error and is not looked for: the gains are device data.
+ * LDPC_EINVAL as ldpc_demap_dev_il, and for a null or misaligned d_gain, all before the device is touched. */
+int ldpc_demap_dev_il_csi(const ldpc_modulation *mod, const ldpc_interleaver *il, int batch, const float *d_sym /* [batch][n_sym][2] */,
+                          const float *d_gain /* [batch][n_sym] */, double noise_var, void *d_llr, int llr_fmt, float qscale, void *stream);
+/* The channel.  Symbol s of a frame lies in block q = s / block, and all symbols of a block share one gain (block >= n_sym: one gain
+ * per frame; block = 1: independent per symbol).  DRAW: block pair Q = blocks 2Q and 2Q + 1 takes one Philox call with counter
+ * (frame lo, frame hi, Q, stream 3) and key = seed, and the Box-Muller of the noise: (z0, z1) -> block 2Q, (z2, z3) -> block 2Q + 1.
+ * Streams 0, 1 and 2 are untouched.  GAIN: with mu = float32(sqrt(K / (K + 1))) and sd = float32(sqrt(1 / (2 (K + 1)))), computed in
+ * double and rounded once (K = k_factor, the Rician factor, linear; 0 = Rayleigh),
+ *   hI = fl(mu + fl(sd z0)),  hQ = fl(sd z1),  a = max(fl(fl(hI hI) + fl(hQ hQ)), 2^-20).
+ * The floor keeps a sample finite when the Box-Muller radius is 0.  E[a] = 1, so ldpc_sim_noise_var and the meaning of Eb/N0 (the
+ * average) are unchanged.  SAMPLE: sg_s = fl(sg / fl(sqrt a)), y = fl(c + fl(sg_s z)) per coordinate with sg and the stream-2 normal z
+ * of ldpc_sim_transmit_il; a = 1 gives the AWGN rule.  Doppler-correlated gains, imperfect channel knowledge, fp16 samples and entry
+ * points without a table are not provided. */
+typedef struct {
+    size_t struct_size; /* sizeof(ldpc_fading) */
+    int block;          /* symbols per fading block, >= 1 */
+    float k_factor;     /* Rician K, linear, finite, >= 0; 0 = Rayleigh */
+} ldpc_fading;
+/* ldpc_sim_transmit_il over that channel: d_sym as there; d_gain [batch][n_sym] float32 (4-byte aligned) receives the gains and may be
+ * NULL.  Everything else -- the labels through the table, the packed codeword buffer, the caller's messages, the words kept for
+ * ldpc_sim_tally, the refusals -- is ldpc_sim_transmit_il's.  LDPC_EINVAL also for a null `fad`, a struct_size that does not cover the
+ * three fields, block < 1, a negative or non-finite k_factor, a misaligned d_gain. */
+int ldpc_sim_transmit_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, const ldpc_fading *fad, uint64_t seed,
+                                uint64_t first_frame, int batch, double ebn0_db, const void *d_msg_in, int msg_fmt, float *d_sym,
+                                float *d_gain /* [batch][n_sym], may be NULL */, uint8_t *d_msg, void *stream);
+/* ldpc_sim_transmit_il_fading and ldpc_demap_dev_il_csi(.., ldpc_sim_noise_var(..), ..) in ONE kernel, bit for bit: neither samples
+ * nor gains need reach memory; a non-null d_gain receives the gains ldpc_sim_transmit_il_fading would have written, bit for bit.
+ * Otherwise as ldpc_sim_generate_mod_il. */
+int ldpc_sim_generate_mod_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, const ldpc_fading *fad, uint64_t seed,
+                                    uint64_t first_frame, int batch, double ebn0_db, const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt,
+                                    float qscale, float *d_gain /* [batch][n_sym], may be NULL */, uint8_t *d_msg, void *stream);
 /* the receive side: message bit i of a frame = decoded bit msg_pos[i] of d_bits [batch][N] bytes (bit 0 of each), written in
  * msg_fmt.  With the systematic form message and parity bits interleave; any source qualifies, LDPC_ENCODER_NONE included. */
 int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream);

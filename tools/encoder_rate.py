@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only | --messages caller | --modulation qpsk|8psk|table32|64qam|256qam|1024qam|4096qam|grid64 [--interleaver none|block|random]] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
+"""tools/encoder_rate.py [frames] [--sparse-only | --systematic-only | --messages caller | --modulation qpsk|8psk|table32|64qam|256qam|1024qam|4096qam|grid64 [--interleaver none|block|random [--fading BLOCK[,K]]]] -- device encoder throughput, quasi-cyclic rotate-and-xor (Fast/Encoder.hs:26-63,
 sim.hip sim_parity_qc_kernel) against the dense packed GF(2) mat-vec of the expanded generator (Orig.hs:25-26), on the shipped AR4JA
 codes: the encoder alone (ldpc_sim_encode_batch: messages + parity -> codeword bytes) and the whole frame source
 (ldpc_sim_generate: + BPSK, AWGN, LLRs).  HIP events on the launch stream, median of 7.
@@ -28,7 +28,12 @@ lines above.  none: the identity table; block: the block table of floor(n_tx / m
 n_tx mod m bits in place; random: a seeded random permutation of the transmitted prefix.  Into float32 and into int8, two rounds of the legs
 alternating in this process, each leg one warm-up and the median of 5: ldpc_demap_dev | ldpc_demap_dev_il | ldpc_demap_dev into a
 [batch][n_tx] buffer + ldpc_deinterleave_llr_dev (the two-pass baseline; its LLRs are compared with the fused ones bit for bit), and
-ldpc_sim_generate_mod | ldpc_sim_generate_mod_il | ldpc_sim_transmit_il + ldpc_demap_dev_il (the only unfused way to the same LLRs).  No bar."""
+ldpc_sim_generate_mod | ldpc_sim_generate_mod_il | ldpc_sim_transmit_il + ldpc_demap_dev_il (the only unfused way to the same LLRs).  No bar.
+--fading BLOCK[,K] (with --modulation and --interleaver): ONLY the fading channel and the per-symbol channel state (csrc/demap_csi.hip,
+csrc/sim_mod_fading.hip) on the same source and table, BLOCK symbols per fading block, Rician factor K (default 0): into float32 and into
+int8, two rounds of the legs alternating, each leg one warm-up and the median of 5: ldpc_demap_dev_il | ldpc_demap_dev_il_csi (with the
+bytes model (12 + m size) / (8 + m size) next to the measured ratio), and ldpc_sim_generate_mod_il | ldpc_sim_generate_mod_il_fading |
+ldpc_sim_transmit_il_fading + ldpc_demap_dev_il_csi (its LLRs are compared with the fused ones bit for bit).  No bar."""
 import os
 import sys
 
@@ -237,15 +242,30 @@ def caller_leg(B, dev, st):
 PRODUCT_BUILTINS = ("64qam", "256qam", "1024qam", "4096qam")
 
 
-def modulation_leg(which, B, dev, st, interleaver=None):
+def make_modulation(which):
     import numpy as np
     from tests import modulation_spec as ms
     if which in PRODUCT_BUILTINS:
-        mod = E.Modulation(which)
-    else:
-        pts = {"qpsk": lambda: ms.builtin(ms.QPSK), "8psk": lambda: ms.builtin(ms.PSK8), "grid64": ms.grid64,
-               "table32": lambda: ms.rings((1.0, 2.84, 5.27), (4, 12, 16), (np.pi / 4, np.pi / 12, 0.0))}[which]()
-        mod = E.Modulation(pts)
+        return E.Modulation(which)
+    pts = {"qpsk": lambda: ms.builtin(ms.QPSK), "8psk": lambda: ms.builtin(ms.PSK8), "grid64": ms.grid64,
+           "table32": lambda: ms.rings((1.0, 2.84, 5.27), (4, 12, 16), (np.pi / 4, np.pi / 12, 0.0))}[which]()
+    return E.Modulation(pts)
+
+
+def table_positions(kind, n_tx, m):
+    """none: the identity; block: floor(n_tx / m) rows and m columns over the first rows * m bits, the rest in place; random: seeded"""
+    import numpy as np
+    if kind == "none":
+        return np.arange(n_tx)
+    if kind == "block":
+        rows = n_tx // m
+        return np.concatenate([E.Interleaver.block_positions(rows, m), np.arange(rows * m, n_tx)])
+    return np.random.default_rng(1).permutation(n_tx)
+
+
+def modulation_leg(which, B, dev, st, interleaver=None):
+    from tests import modulation_spec as ms
+    mod = make_modulation(which)
     m = mod.bits
     ecc = E.ECC(os.path.join(ROOT, "codes"), "ldpc/hip-minsum/jpl.4096.4.5/50/4/5", max_batch=B)
     sim, k, n_tx, N = ecc.sim, ecc.message_length, ecc.codeword_length, ecc.unpunctured_length
@@ -307,16 +327,8 @@ def modulation_leg(which, B, dev, st, interleaver=None):
 
 
 def interleaver_leg(kind, mod, sim, B, n_tx, N, sym, nv, dev, st):
-    import numpy as np
     m, s_ = mod.bits, st.cuda_stream
-    if kind == "none":
-        pos = np.arange(n_tx)
-    elif kind == "block":
-        rows = n_tx // m
-        pos = np.concatenate([E.Interleaver.block_positions(rows, m), np.arange(rows * m, n_tx)])
-    else:
-        pos = np.random.default_rng(1).permutation(n_tx)
-    il = E.Interleaver(pos, N)
+    il = E.Interleaver(table_positions(kind, n_tx, m), N)
     ns = mod.symbols(n_tx)
     print(f"  interleaver {kind}: n_tx = {n_tx}, N = {N}, {N - n_tx} punctured; two rounds, legs alternating, each one warm-up + median of 5 (ms):", flush=True)
     for fmt, dt, size in (("f32", torch.float32, 4), ("i8", torch.int8, 1)):
@@ -362,8 +374,73 @@ def interleaver_leg(kind, mod, sim, B, n_tx, N, sym, nv, dev, st):
     il.close()
 
 
+def fading_leg(which, kind, block, K, B, dev, st):
+    mod = make_modulation(which)
+    m, s_ = mod.bits, st.cuda_stream
+    ecc = E.ECC(os.path.join(ROOT, "codes"), "ldpc/hip-minsum/jpl.4096.4.5/50/4/5", max_batch=B)
+    sim, n_tx, N = ecc.sim, ecc.codeword_length, ecc.unpunctured_length
+    ns = mod.symbols(n_tx)
+    il = E.Interleaver(table_positions(kind, n_tx, m), N)
+    fad = E.Fading(block, K)
+    db = 2.0
+    nv = sim.noise_var(mod, db)
+    sym = torch.empty((B, ns, 2), dtype=torch.float32, device=dev)
+    gain = torch.empty((B, ns), dtype=torch.float32, device=dev)
+    sim.transmit_il_fading(mod, il, fad, 1, 0, B, db, sym.data_ptr(), gain.data_ptr(), None, "bytes", None, s_)
+    torch.cuda.synchronize()
+    print(f"jpl.4096.4.5 qc source, {which} (m = {m}, {ns} symbols a frame), interleaver {kind}, fading block = {block}, K = {K:g}, {B} frames, {db} dB; mean gain "
+          f"{float(gain.mean()):.4f}; two rounds, legs alternating, each one warm-up + median of 5 (ms):", flush=True)
+    for fmt, dt, size in (("f32", torch.float32, 4), ("i8", torch.int8, 1)):
+        out = torch.empty((B, N), dtype=dt, device=dev)
+        two = torch.empty((B, N), dtype=dt, device=dev)
+
+        def unfused():
+            sim.transmit_il_fading(mod, il, fad, 1, 0, B, db, sym.data_ptr(), gain.data_ptr(), None, "bytes", None, s_)
+            E.demap_il_csi(mod, il, B, sym.data_ptr(), gain.data_ptr(), nv, two.data_ptr(), fmt, 4.0, s_)
+
+        demap_legs = (("ldpc_demap_dev_il", lambda: E.demap_il(mod, il, B, sym.data_ptr(), nv, out.data_ptr(), fmt, 4.0, s_)),
+                      ("ldpc_demap_dev_il_csi", lambda: E.demap_il_csi(mod, il, B, sym.data_ptr(), gain.data_ptr(), nv, out.data_ptr(), fmt, 4.0, s_)))
+        gen_legs = (("ldpc_sim_generate_mod_il", lambda: sim.generate_mod_il(mod, il, 1, 0, B, db, out.data_ptr(), fmt, 4.0, None, "bytes", None, s_)),
+                    ("ldpc_sim_generate_mod_il_fading", lambda: sim.generate_mod_il_fading(mod, il, fad, 1, 0, B, db, out.data_ptr(), fmt, 4.0, None, None, "bytes", None, s_)),
+                    ("transmit_il_fading + demap_il_csi", unfused))
+        for legs, what in ((demap_legs, "demap"), (gen_legs, "generate_mod")):
+            res = {name: [] for name, _ in legs}
+            for _ in range(2):
+                for name, fn in legs:
+                    res[name].append(timed(fn, st, 5))
+            ts = [res[name] for name, _ in legs]
+            line = f"  -> {fmt:3s} " + " | ".join(f"{name} {t[0]:8.3f} {t[1]:8.3f}" for name, t in res.items())
+            if what == "demap":
+                model = (12.0 + m * size) / (8.0 + m * size)
+                nbytes = B * (ns * 12 + N * size)
+                line += f" | csi / plain = {min(ts[1]) / min(ts[0]):.3f} (bytes model {model:.3f}) | {nbytes / 1e6:.1f} MB moved = {nbytes / min(ts[1]) / 1e9:.2f} TB/s"
+            else:
+                line += f" | fading / awgn = {min(ts[1]) / min(ts[0]):.3f} (one more Philox call a lane), fused / two-step = {min(ts[1]) / min(ts[2]):.3f}"
+            print(line, flush=True)
+        unfused()
+        sim.generate_mod_il_fading(mod, il, fad, 1, 0, B, db, out.data_ptr(), fmt, 4.0, None, None, "bytes", None, s_)
+        torch.cuda.synchronize()
+        iv = torch.int32 if fmt == "f32" else torch.int8
+        assert torch.equal(out.view(iv), two.view(iv)), f"generate_mod_il_fading differs from transmit_il_fading + demap_il_csi ({fmt})"
+        del out, two
+    print("  generate_mod_il_fading = transmit_il_fading + demap_il_csi bit for bit", flush=True)
+    il.close(); mod.close(); ecc.close()
+
+
 def main():
     argv = sys.argv[1:]
+    fading = None
+    if "--fading" in argv:
+        i = argv.index("--fading")
+        try:
+            parts = argv[i + 1].split(",")
+            fading = (int(parts[0]), float(parts[1]) if len(parts) > 1 else 0.0)
+            assert len(parts) <= 2
+        except (IndexError, ValueError, AssertionError):
+            sys.exit("--fading takes BLOCK[,K]: symbols per fading block and the Rician factor")
+        del argv[i:i + 2]
+        if "--modulation" not in argv or "--interleaver" not in argv:
+            sys.exit("--fading goes with --modulation and --interleaver")
     messages = None
     modulation = None
     interleaver = None
@@ -391,6 +468,9 @@ def main():
     dev = torch.device("cuda", 0)
     st = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(st)
+    if fading:
+        fading_leg(modulation, interleaver, fading[0], fading[1], B, dev, st)
+        return
     if modulation:
         modulation_leg(modulation, B, dev, st, interleaver)
         return
