@@ -229,6 +229,11 @@ __global__ __launch_bounds__(256) void sim_tally_kernel(SimDev s, const uint32_t
     }
 }
 
+// frames per launch of the kernels whose frame is blockIdx.y (sim_frame_kernel, pack_bits_kernel): the 65 536 the device reports as its
+// largest gridDim.y (hipDeviceAttributeMaxGridDimY; the runtime has been seen to run more, which nothing promises), so that a batch
+// up to there is one launch as before; even, so that a slice starts on the alignment the first one has
+constexpr int kFrameSlice = 65536;
+
 // ---- caller-supplied messages (ldpc_sim_encode_messages, ldpc_sim_generate_from, ldpc_sim_extract_messages).  The three kernels
 // index (frame, word) through one flat grid-stride loop over blockIdx.x: no batch limit of their own.
 static unsigned sim_grid(size_t total) { return (unsigned)std::min<size_t>((total + 255) / 256, (size_t)1 << 20); }
@@ -386,18 +391,30 @@ int sim_generate(const SimDev &s0, const SimSparse *sp, const SimSys *sy, uint32
         return LDPC_OK;
     }
     const int groups = ((out_fmt == 2 ? s.n_tx : s.N) + 3) / 4;
-    const dim3 grid((groups + 255) / 256, batch);
     const float sg = (float)sqrt(sigma2), sc = (float)(2.0 / sigma2);
-    // 16-byte (f32) / 8-byte (fp16) vector stores when every row starts aligned
+    // 16-byte (f32) / 8-byte (fp16) vector stores when every row starts aligned: decided once, from the caller's pointer (an even
+    // slice keeps every slice start aligned whenever the first one is)
     const bool vec = (s.N % 4 == 0) && ((uintptr_t)d_out % 16 == 0);
-    if (out_fmt == 2) {
-        hipLaunchKernelGGL((sim_frame_kernel<uint8_t, false>), grid, dim3(256), 0, st, s, msgw, parw, (uint8_t *)d_out, d_msg, seed, first_frame, batch, 0.f, 1.f);
-    } else if (out_fmt == 1) {
-        if (vec) hipLaunchKernelGGL((sim_frame_kernel<__half, true>), grid, dim3(256), 0, st, s, msgw, parw, (__half *)d_out, d_msg, seed, first_frame, batch, sg, sc);
-        else hipLaunchKernelGGL((sim_frame_kernel<__half, false>), grid, dim3(256), 0, st, s, msgw, parw, (__half *)d_out, d_msg, seed, first_frame, batch, sg, sc);
-    } else {
-        if (vec) hipLaunchKernelGGL((sim_frame_kernel<float, true>), grid, dim3(256), 0, st, s, msgw, parw, (float *)d_out, d_msg, seed, first_frame, batch, sg, sc);
-        else hipLaunchKernelGGL((sim_frame_kernel<float, false>), grid, dim3(256), 0, st, s, msgw, parw, (float *)d_out, d_msg, seed, first_frame, batch, sg, sc);
+    // the frame is blockIdx.y (kFrameSlice): a larger batch goes in slices, all on the caller's stream.  The Philox counters are
+    // functions of (frame id, group), so the slices write what one launch would
+    const size_t row = out_fmt == 2 ? (size_t)s.n_tx : (size_t)s.N * (out_fmt == 1 ? 2 : 4);   // bytes of an output row
+    for (int f0 = 0; f0 < batch; f0 += kFrameSlice) {
+        const int b = std::min(kFrameSlice, batch - f0);
+        const dim3 grid((groups + 255) / 256, b);
+        const uint32_t *mw = msgw + (size_t)f0 * s.kwords;
+        const uint32_t *pw = parw ? parw + (size_t)f0 * s.pwords : nullptr;
+        uint8_t *dm = d_msg ? d_msg + (size_t)f0 * s.k : nullptr;
+        void *out = (uint8_t *)d_out + (size_t)f0 * row;
+        const uint64_t first = first_frame + (uint64_t)f0;
+        if (out_fmt == 2) {
+            hipLaunchKernelGGL((sim_frame_kernel<uint8_t, false>), grid, dim3(256), 0, st, s, mw, pw, (uint8_t *)out, dm, seed, first, b, 0.f, 1.f);
+        } else if (out_fmt == 1) {
+            if (vec) hipLaunchKernelGGL((sim_frame_kernel<__half, true>), grid, dim3(256), 0, st, s, mw, pw, (__half *)out, dm, seed, first, b, sg, sc);
+            else hipLaunchKernelGGL((sim_frame_kernel<__half, false>), grid, dim3(256), 0, st, s, mw, pw, (__half *)out, dm, seed, first, b, sg, sc);
+        } else {
+            if (vec) hipLaunchKernelGGL((sim_frame_kernel<float, true>), grid, dim3(256), 0, st, s, mw, pw, (float *)out, dm, seed, first, b, sg, sc);
+            else hipLaunchKernelGGL((sim_frame_kernel<float, false>), grid, dim3(256), 0, st, s, mw, pw, (float *)out, dm, seed, first, b, sg, sc);
+        }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(LDPC_EHIP, "sim_generate: %s", hipGetErrorString(e));
@@ -433,7 +450,10 @@ __global__ __launch_bounds__(256) void pack_bits_kernel(const uint8_t *__restric
 
 int pack_bits(hipStream_t st, const uint8_t *d_bits, uint8_t *d_packed, int batch, int N) {
     const int PB = (N + 7) / 8;
-    hipLaunchKernelGGL(pack_bits_kernel, dim3((PB + 255) / 256, batch), dim3(256), 0, st, d_bits, d_packed, batch, N, PB);
+    for (int f0 = 0; f0 < batch; f0 += kFrameSlice) {   // the frame is blockIdx.y: slices, as in sim_generate
+        const int b = std::min(kFrameSlice, batch - f0);
+        hipLaunchKernelGGL(pack_bits_kernel, dim3((PB + 255) / 256, b), dim3(256), 0, st, d_bits + (size_t)f0 * N, d_packed + (size_t)f0 * PB, b, N, PB);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(LDPC_EHIP, "pack_bits: %s", hipGetErrorString(e));
     return LDPC_OK;

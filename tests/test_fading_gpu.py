@@ -102,19 +102,24 @@ def test_demapper_csi_against_the_spec(hip, kind, n):
 
 
 # ---- the frame source
-def _source203(hip):
-    """a dense source of N = 203, n_tx = 187, k = 100: a random generator (the source does not look at H; 29 checks of 7 positions)"""
+def _source203(hip, max_batch=B, n_tx=187, generator=True):
+    """a dense source of N = 203, n_tx = 187, k = 100: a random generator (the source does not look at H; 29 checks of 7 positions).
+    The generator is kept as .G; generator=False: the source without one (all-zero codewords), .G = None"""
     code = hip.Code.from_csr(np.arange(0, 204, 7, dtype=np.int32), np.arange(203, dtype=np.int32), 203)
-    G = np.random.default_rng(11).integers(0, 2, (100, 103)).astype(np.uint8)
-    sim = hip.Sim(code, 100, 187, G=G, max_batch=B)
-    return Source(sim, code, 203, 187, (sim, code))
+    G = np.random.default_rng(11).integers(0, 2, (100, 103)).astype(np.uint8) if generator else None
+    sim = hip.Sim(code, 100, n_tx, G=G, max_batch=max_batch)
+    src = Source(sim, code, 203, n_tx, (sim, code))
+    src.G = G
+    return src
 
 
-def _source120(hip):
+def _source120(hip, max_batch=B):
     code = hip.Code.from_csr(np.arange(0, 121, 6, dtype=np.int32), np.arange(120, dtype=np.int32), 120)
     G = np.random.default_rng(12).integers(0, 2, (50, 70)).astype(np.uint8)
-    sim = hip.Sim(code, 50, 120, G=G, max_batch=B)
-    return Source(sim, code, 120, 120, (sim, code))
+    sim = hip.Sim(code, 50, 120, G=G, max_batch=max_batch)
+    src = Source(sim, code, 120, 120, (sim, code))
+    src.G = G
+    return src
 
 
 def _source_table(src, m):
