@@ -407,6 +407,28 @@ __global__ void flood_finalize_kernel(FloodDev d, int max_iters) {
     d.conv[b] = (d.unsat[b] != max_iters + 1) ? 1 : 0;
 }
 
+// min-sum f32 (ldpc_math.h kVetoesNonFinite): once per decode, after the last turn and before the results are read.  A frame that
+// came back "converged" with an LLR that is not finite is failed: flag clear, the iteration limit as its count (store_bits_kernel
+// then hands out the channel's decisions).  A non-finite CHANNEL LLR stays non-finite in its column's lam whatever is added to it
+// or however often the frame is rescaled, so this also fails every frame that was given one -- the flooding turns never look, and
+// layered_kernel does not for a frame whose channel decisions are a codeword before the first sweep.  One block per slab of 64
+// frames, lane = frame, the waves share the columns; a slab without a converged frame costs one load per lane.
+__global__ __launch_bounds__(1024) void flood_veto_kernel(FloodDev d, const float *__restrict__ lam, int max_iters) {
+    __shared__ int bad[kWave];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const size_t b = (size_t)blockIdx.x * kWave + lane;
+    const bool conv = d.conv[b] != 0;
+    if (!__builtin_amdgcn_ballot_w64(conv)) return;      // (the same answer in every wave of the block)
+    if (wave == 0) bad[lane] = 0;
+    __syncthreads();                                     // every wave has read the flags
+    bool nf = false;
+    if (conv)
+        for (int c = wave; c < d.N; c += nw) nf |= not_finite(lam[(size_t)c * d.Bp + b]);
+    if (nf) bad[lane] = 1;                               // (benign race: every writer stores 1)
+    __syncthreads();
+    if (wave == 0 && bad[lane]) { d.conv[b] = 0; d.iters[b] = max_iters; }
+}
+
 __global__ void flood_reset_kernel(FloodDev d, int batch) {
     size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= (size_t)d.Bp) return;
@@ -439,6 +461,7 @@ __global__ __launch_bounds__(256) void load_llr_kernel(const IT *__restrict__ in
         if (n < N && b < Bp) {
             typename Store<ST>::CT v;
             if constexpr (sizeof(IT) == 8) v = (typename Store<ST>::CT)tiled[tx][r]; else v = (typename Store<ST>::CT)tile[tx][r];
+            if constexpr (sizeof(ST) == 2) v = nan_as_zero(v);   // fp16 storage: a NaN is an erasure (ldpc_math.h)
             Store<ST>::st(orig + (size_t)n * Bp + b, v);
             Store<ST>::st(lam + (size_t)n * Bp + b, v);
         }
@@ -894,6 +917,8 @@ static int decode_impl(FloodState &s, hipStream_t st, int max_iters, int batch, 
         hipLaunchKernelGGL((load_llr_kernel<float, ST>), tgrid, dim3(256), 0, st, (const float *)d_llr, (ST *)s.orig, (ST *)s.lam, batch, d.N, d.Bp);
     int rc = run_turns<ST, VARIANT>(s, st, max_iters, batch, d_trace);
     if (rc != LDPC_OK) return rc;
+    if constexpr (kVetoesNonFinite<typename Store<ST>::CT, VARIANT> && sizeof(ST) == 4)
+        hipLaunchKernelGGL(flood_veto_kernel, dim3(d.Bp / kWave), dim3(1024), 0, st, d, (const float *)s.lam, max_iters);
     hipLaunchKernelGGL((store_bits_kernel<ST>), tgrid, dim3(256), 0, st, d, (const ST *)s.orig, (const ST *)s.lam, d_bits, d_final, batch);
     HIPCHK(hipGetLastError());
     return LDPC_OK;
@@ -961,6 +986,8 @@ static int layered_decode_impl(FloodState &s, hipStream_t st, int max_iters, int
     LayerArgs a{max_iters, 0, d_trace, batch};
     int rc = layered_launch<ST, VARIANT>(s, st, a);
     if (rc != LDPC_OK) return rc;
+    if constexpr (kVetoesNonFinite<typename Store<ST>::CT, VARIANT> && sizeof(ST) == 4)   // (a frame that stopped before the first sweep)
+        hipLaunchKernelGGL(flood_veto_kernel, dim3(d.Bp / kWave), dim3(1024), 0, st, d, (const float *)s.lam, max_iters);
     hipLaunchKernelGGL((store_bits_kernel<ST>), tgrid, dim3(256), 0, st, d, (const ST *)s.orig, (const ST *)s.lam, d_bits, d_final, batch);
     HIPCHK(hipGetLastError());
     return LDPC_OK;

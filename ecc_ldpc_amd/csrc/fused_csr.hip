@@ -84,8 +84,14 @@ __global__ __launch_bounds__(THREADS) void fused_csr_kernel(CsrArgs A) {
     const int M = A.M, N = A.N;
     const size_t fN = (size_t)frame * N, fE = (size_t)frame * A.E;
 
+    // min-sum f32 (ldpc_math.h kVetoesNonFinite): the frame is rescaled before an LLR can leave the float range, so only a CHANNEL LLR
+    // can be non-finite -- and then its column's lam is for good.  Looked for here, once per frame, combined at the barrier that ends
+    // the prologue; a frame with one is failed after the turn loop, whatever its syndrome said.  Nothing of it is in the turn loop.
+    constexpr bool kVeto = kVetoesNonFinite<CT, VARIANT>;
+    bool chan_nf = false;
     for (int n = tid; n < N; n += THREADS) {
         CT v = maybe_round_f16<CT>(load_llr<CT>(A.llr, fN + n, A.llr_fmt), A.llr_round16);
+        if constexpr (kVeto) chan_nf |= not_finite(v);
         orig[n] = v;
         lam[n] = A.step_mode ? (CT)A.st_lam[fN + n] : v;
     }
@@ -94,7 +100,9 @@ __global__ __launch_bounds__(THREADS) void fused_csr_kernel(CsrArgs A) {
 #pragma unroll
         for (int k = 0; k < DMAX; k++) msg[k * M + m] = (A.step_mode && k < deg) ? (CT)A.st_ne_in[fE + e0 + k] : CT(0);  // Orig.hs:64-65
     }
-    __syncthreads();
+    int chan_bad = 0;
+    if constexpr (kVeto) chan_bad = __syncthreads_or(chan_nf ? 1 : 0);
+    else __syncthreads();
 
     constexpr bool kCached = RPT > 0;
     int rcol[kCached ? RPT : 1][DMAX];
@@ -236,6 +244,7 @@ __global__ __launch_bounds__(THREADS) void fused_csr_kernel(CsrArgs A) {
         } else __syncthreads();
         if (A.step_mode) break;
     }
+    if (kVeto && chan_bad && converged) { converged = false; n_done = turns; }   // (a non-finite channel LLR: failed, not "converged")
 
     if (A.step_mode) {
         for (int c = tid; c < N; c += THREADS) A.final_lam[fN + c] = ldexp((double)lam[c], kexp);
@@ -397,6 +406,11 @@ __global__ __launch_bounds__(THREADS, (DMAX <= 8 ? (THREADS > 512 ? 4 : THREADS 
     while (frame < A.batch) {
     const size_t fN = (size_t)frame * N, fE = (size_t)frame * A.E;
     CT mreg[RPT][DMAX], oreg[CPT];
+    // (min-sum f32: a non-finite CHANNEL LLR is looked for while the frame comes in and combined at the prologue's barrier, as in
+    // fused_csr_kernel above; the frame is failed after its turn loop)
+    constexpr bool kVeto = kVetoesNonFinite<CT, VARIANT>;
+    bool chan_nf = false;
+    int chan_bad = 0;
     int colreg[CPT];   // (re-read per frame, one coalesced load: kept across frames it costs the turn loop four registers)
     if constexpr (!STAGED) {
 #pragma unroll
@@ -418,10 +432,13 @@ __global__ __launch_bounds__(THREADS, (DMAX <= 8 ? (THREADS > 512 ? 4 : THREADS 
             oreg[i] = CT(0);
             if (c < N) {
                 oreg[i] = maybe_round_f16<CT>((CT)stage[cpos[c]], A.llr_round16);
+                if constexpr (kVeto) chan_nf |= not_finite(oreg[i]);
                 lam[c] = oreg[i];
             }
         }
-        __syncthreads();   // the staging area has been read: it is the next frame's now
+        // the staging area has been read: it is the next frame's now
+        if constexpr (kVeto) chan_bad = __syncthreads_or(chan_nf ? 1 : 0);
+        else __syncthreads();
         if (frame_next >= 0 && frame_next < A.batch) stage_frame(frame_next, tf);
         if (tid == THREADS - 64) claim(frame_next, true);   // the frame after the one held next
     } else {
@@ -442,10 +459,12 @@ __global__ __launch_bounds__(THREADS, (DMAX <= 8 ? (THREADS > 512 ? 4 : THREADS 
         oreg[i] = CT(0);
         if (c < N) {
             oreg[i] = maybe_round_f16<CT>(load_llr<CT>(A.llr, fN + colreg[i], A.llr_fmt), A.llr_round16);
+            if constexpr (kVeto) chan_nf |= not_finite(oreg[i]);
             lam[c] = A.step_mode ? (CT)A.st_lam[fN + colreg[i]] : oreg[i];
         }
     }
-    __syncthreads();
+    if constexpr (kVeto) chan_bad = __syncthreads_or(chan_nf ? 1 : 0);
+    else __syncthreads();
     }
     CSR_STAMP(0);
 
@@ -574,6 +593,7 @@ __global__ __launch_bounds__(THREADS, (DMAX <= 8 ? (THREADS > 512 ? 4 : THREADS 
         } else __syncthreads();
         if (step_mode) break;
     }
+    if (kVeto && chan_bad && converged) { converged = false; n_done = turns; }   // (a non-finite channel LLR: failed, not "converged")
     CSR_STAMP(1);
 
     if (step_mode) {

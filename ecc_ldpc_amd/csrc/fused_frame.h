@@ -97,13 +97,27 @@ template <typename CT, bool NEG> struct LamCell {      // lam itself, or 0 - lam
         return (double)maybe_round_f16<CT>(load_llr_as<CT, FMT>(A.llr, gi), A.llr_round16);
     }
 };
-struct LamCellPk16 {   // two frames: L = -lam as fp16 in the low / high half (fused_pk16_body.h)
+// the f32 cell of the on-chip layered kernel (fused_layered_body.h lay::body): its LDPC_F16 rounding is still the plain saturation
+// (ldpc_math.h round_f16_sat: a NaN comes out as -65504) -- that kernel is not under rule 1 and rule 3 of include/ldpc_hip.h yet
+struct LamCellLay : LamCell<float, false> {
+    template <int FMT> static __device__ __forceinline__ double channel(const FusedArgs &A, size_t gi) {
+        const float v = load_llr_as<float, FMT>(A.llr, gi);
+        return (double)(A.llr_round16 ? round_f16_sat(v) : v);
+    }
+};
+// NANZ: a NaN channel LLR is taken in as +0, an erasure (include/ldpc_hip.h, non-finite channel LLRs, rule 1): the layered kernel.  The
+// flooding kernel (fused_pk16_body.h) still has the plain saturation, under which fmaxf(NaN, -M) = -M makes a NaN the LLR -16384: with
+// the erasure form in its prologue that kernel lost 3 % although its turn loop, registers and spills were unchanged (DESIGN.md sections 4, 7).
+template <bool NANZ> struct LamCellPk16T {   // two frames: L = -lam as fp16 in the low / high half (fused_pk16_body.h)
     using word = uint32_t;
     static constexpr int FPL = 2;
     static constexpr float LLR16_MAX = 16384.0f;
-    // -(x) of a channel LLR as fp16 bits, saturated at +-LLR16_MAX, a zero as +0
+    // -(x) of a channel LLR as fp16 bits, saturated at +-LLR16_MAX, a zero as +0.  NANZ, without a compare: fmaxf(NaN, -M) = -M and
+    // fminf(NaN, M) = M, so the median of {max(x, -M), min(x, M), 0} is 0 for a NaN, x itself inside +-M and +-M outside
     static __device__ __forceinline__ uint32_t neg_llr16(float x) {
-        const float v = fminf(fmaxf(x, -LLR16_MAX), LLR16_MAX);
+        float v;
+        if constexpr (NANZ) v = __builtin_amdgcn_fmed3f(fmaxf(x, -LLR16_MAX), fminf(x, LLR16_MAX), 0.0f);
+        else v = fminf(fmaxf(x, -LLR16_MAX), LLR16_MAX);
         const _Float16 h = (_Float16)(0.0f - v);          // 0 - (+-0) = +0; the f32 negation is exact, the conversion rounds to nearest even
         uint16_t b;
         __builtin_memcpy(&b, &h, 2);
@@ -120,6 +134,8 @@ struct LamCellPk16 {   // two frames: L = -lam as fp16 in the low / high half (f
         return value(neg_llr16(load_llr_as<float, FMT>(A.llr, gi)), 0);
     }
 };
+using LamCellPk16 = LamCellPk16T<true>;
+using LamCellPk16Sat = LamCellPk16T<false>;
 
 // The plumbing of wave group P of a workgroup whose lam cells are Cell's.  lds: the workgroup's LDS; p4: the lane's byte offset
 // inside a block column; w: where the lane is; h: which of the lane's FPL frames.  FULL: the `done` mask with every frame finished
@@ -177,9 +193,9 @@ template <class Plan, int SZ, int P, class Cell> struct Frame : SplitGeom<Plan, 
 
 // ---- packed fp16: L <- -(channel LLRs) of the lane's two frames.  Every LLR is read from memory once; the hard decisions of the
 // lane's own columns stay in obits[h] (the answer of a frame that runs out of turns).
-template <class Plan, int SZ, int P, class Bits>
+template <class Plan, int SZ, int P, class Cell = LamCellPk16, class Bits>
 __device__ __forceinline__ void load_llrs_pk16(const FusedArgs &A, char *lds, uint32_t p4, Bits (&obits)[2]) {
-    using F = Frame<Plan, SZ, P, LamCellPk16>;
+    using F = Frame<Plan, SZ, P, Cell>;
     const typename F::W w(p4, A.batch);   // (a frame past the batch shadows frame 0: every load below is unconditional and in range)
     with_llr_format(A.llr_fmt, [&](auto fc) {
         constexpr int FMT = decltype(fc)::value;
@@ -194,7 +210,7 @@ __device__ __forceinline__ void load_llrs_pk16(const FusedArgs &A, char *lds, ui
             uint32_t packed = 0;
 #pragma unroll
             for (int h = 0; h < 2; h++) {
-                const uint32_t b = LamCellPk16::neg_llr16(x[bc / Plan::NP][h]);
+                const uint32_t b = Cell::neg_llr16(x[bc / Plan::NP][h]);
                 obits[h].set(bc / Plan::NP, (b >> 15) & 1u);      // hard(llr) = llr > 0 = sign of -llr
                 packed |= b << (16 * h);
             }

@@ -99,7 +99,7 @@ template <class Plan, int SZ, class T, int P, bool RS>
 __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32_t tid) {
     using S = Split<Plan, T>;
     using H = Halves<Plan>;
-    using F = Frame<Plan, SZ, P, LamCell<float, false>>;
+    using F = Frame<Plan, SZ, P, LamCellLay>;   // (LDPC_F16: the plain saturating rounding -- fused_frame.h LamCellLay)
     using Where = typename F::W;
     constexpr int CPW = F::CPW, V = F::V, VT = F::VT, NW = F::NW;
     constexpr uint32_t ES = 4, vmask = F::vmask, FULL = F::FULL;
@@ -118,7 +118,8 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
             constexpr int FMT = decltype(fc)::value;
             own_columns<Plan, P>([&](auto bcc) {
                 constexpr int bc = decltype(bcc)::value;
-                const float v = maybe_round_f16<float>(load_llr_as<float, FMT>(A.llr, w.fN[0] + bc * SZ + w.r0), A.llr_round16);
+                const float x = load_llr_as<float, FMT>(A.llr, w.fN[0] + bc * SZ + w.r0);
+                const float v = A.llr_round16 ? round_f16_sat(x) : x;
                 obits.set(bc / Plan::NP, v > 0.0f);
                 lds_st<float>(lds, p4 + (bc * V * ES), v);
             });

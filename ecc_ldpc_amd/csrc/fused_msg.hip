@@ -155,8 +155,32 @@ __global__ __launch_bounds__((MsgCfg<CT, VARIANT, Plan, SZ>::THREADS), (MsgCfg<C
         }
         if (A.step_mode) {
             if (valid && r0 == 0) A.st_syn[frame] = frame_unsat ? 0 : 1;
-        } else if (active && !frame_unsat) {
-            converged = true; active = false; n_done = n;
+        } else {
+            bool stop = active && !frame_unsat;   // Orig.hs:69
+            if constexpr (kVetoesNonFinite<CT, VARIANT>) {
+                // (once per frame) an LLR that is not finite: failed, not "converged" (ldpc_math.h) -- the channel's decisions, the turn
+                // limit as its count.  Two waves per frame means one frame per workgroup: `stop` is then the same in both waves
+                // (it derives from the shared flags), so both reach the barrier; the words 2 and 3 of the flag area are written here only
+                if (__any(stop)) {
+                    LDPC_COLD_PATH();
+                    bool nf = false;
+                    if (stop)
+                        static_for<0, Plan::NBC>([&](auto bcc) {
+                            constexpr int bc = decltype(bcc)::value;
+#pragma unroll
+                            for (int h = 0; h < RPL; h++) nf |= not_finite(lds_ld<CT>(lds, (p4 + HSTEP * h) | (bc * V * ES)));
+                        });
+                    bool bad = (__ballot(nf) & fmask) != 0ull;
+                    if constexpr (WPF > 1) {
+                        volatile uint32_t *vflags = reinterpret_cast<volatile uint32_t *>(lds + Cfg::LAM_BYTES) + 2;
+                        if ((lane & 63) == 0) vflags[lane >> 6] = bad ? 1u : 0u;
+                        __syncthreads();
+                        bad = (vflags[0] | vflags[1]) != 0u;
+                    }
+                    if (stop && bad) { stop = false; active = false; n_done = turns; }
+                }
+            }
+            if (stop) { converged = true; active = false; n_done = n; }
         }
         if (last) {
             if (active) { active = false; n_done = n; }

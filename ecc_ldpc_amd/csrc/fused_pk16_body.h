@@ -191,7 +191,7 @@ __device__ __forceinline__ void round(char *lds, uint32_t p4, uint32_t vmask, co
 template <class Plan, int SZ, class T, int P>
 __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32_t tid) {
     using S = Split<Plan, T>;
-    using F = Frame<Plan, SZ, P, LamCellPk16>;
+    using F = Frame<Plan, SZ, P, LamCellPk16Sat>;   // (not under rule 1 yet: fused_frame.h LamCellPk16T)
     constexpr int CPW = F::CPW, V = F::V, VT = F::VT, NW = F::NW;
     constexpr uint32_t ES = 4, vmask = F::vmask, FULL = F::FULL;
     static_assert(CPW <= 8, "the done mask holds 2 * CPW frames");
@@ -205,7 +205,7 @@ __device__ __forceinline__ void body(const FusedArgs &A, char *lds, const uint32
     for (int i = 0; i < S::NORIG; i++) orig[i] = 0u;
     // ---- L <- -(channel LLRs) of both frames: group P fills the block columns bc with bc % NP == P
     typename SplitResult<F::NBCP>::Bits obits[2];
-    load_llrs_pk16<Plan, SZ, P>(A, lds, p4, obits);
+    load_llrs_pk16<Plan, SZ, P, LamCellPk16Sat>(A, lds, p4, obits);
     __syncthreads();
     static_for<0, Plan::NBC>([&](auto bcc) {   // L == -(channel LLRs) right now: the round-0 (rotated) copies are an LDS gather away
         constexpr int bc = decltype(bcc)::value;

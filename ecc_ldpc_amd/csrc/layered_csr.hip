@@ -102,6 +102,7 @@ template <> struct Cell<_Float16> {
     typedef half8 vec8;
     typedef CsrRec Rec;
     static __device__ __forceinline__ _Float16 of(float v) { return sat16(v); }
+    static __device__ __forceinline__ _Float16 llr(float v) { return sat16(nan_as_zero(v)); }   // a channel LLR: a NaN is an erasure (ldpc_math.h)
     static __device__ __forceinline__ void st8(_Float16 *p, const half8 &h) { *reinterpret_cast<half8 *>(p) = h; }
     static __device__ __forceinline__ half8 ld8(const _Float16 *p) { return *reinterpret_cast<const half8 *>(p); }
 };
@@ -109,6 +110,7 @@ template <> struct Cell<float> {
     typedef float8 vec8;
     typedef CsrRec Rec;
     static __device__ __forceinline__ float of(float v) { return v; }
+    static __device__ __forceinline__ float llr(float v) { return v; }                          // (f32 state takes the values as they are)
     static __device__ __forceinline__ void st8(float *p, const float8 &h) {      // two 16-byte LDS stores
         *reinterpret_cast<float4 *>(p) = make_float4(h[0], h[1], h[2], h[3]);
         *reinterpret_cast<float4 *>(p + 4) = make_float4(h[4], h[5], h[6], h[7]);
@@ -125,16 +127,16 @@ template <> struct Cell<float> {
 template <typename LT, int FMT> __device__ __forceinline__ void load_llr8(const void *base, size_t i, typename Cell<LT>::vec8 &h) {
     if constexpr (FMT == LLR_F64) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) h[k] = Cell<LT>::of((float)reinterpret_cast<const double *>(base)[i + k]);
+        for (int k = 0; k < 8; k++) h[k] = Cell<LT>::llr((float)reinterpret_cast<const double *>(base)[i + k]);
     } else if constexpr (FMT == LLR_F16) {
         const half8 v = *reinterpret_cast<const half8 *>(reinterpret_cast<const _Float16 *>(base) + i);
 #pragma unroll
-        for (int k = 0; k < 8; k++) h[k] = Cell<LT>::of((float)v[k]);
+        for (int k = 0; k < 8; k++) h[k] = Cell<LT>::llr((float)v[k]);
     } else {
         const float4 a = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + i);
         const float4 b = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + i + 4);
-        h[0] = Cell<LT>::of(a.x); h[1] = Cell<LT>::of(a.y); h[2] = Cell<LT>::of(a.z); h[3] = Cell<LT>::of(a.w);
-        h[4] = Cell<LT>::of(b.x); h[5] = Cell<LT>::of(b.y); h[6] = Cell<LT>::of(b.z); h[7] = Cell<LT>::of(b.w);
+        h[0] = Cell<LT>::llr(a.x); h[1] = Cell<LT>::llr(a.y); h[2] = Cell<LT>::llr(a.z); h[3] = Cell<LT>::llr(a.w);
+        h[4] = Cell<LT>::llr(b.x); h[5] = Cell<LT>::llr(b.y); h[6] = Cell<LT>::llr(b.z); h[7] = Cell<LT>::llr(b.w);
     }
 }
 
@@ -413,7 +415,7 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
         } else {
             with_llr_format(A.llr_fmt, [&](auto fmt) {
 #pragma unroll 8
-                for (int i = tid; i < g.N; i += T) lam[i] = Cell<LT>::of(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
+                for (int i = tid; i < g.N; i += T) lam[i] = Cell<LT>::llr(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
             });
         }
         if (tid == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; ctl[4] = 0; if constexpr (kVeto) ctl[5] = 0; }
@@ -461,16 +463,17 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
                 if (ctl[1 + n % 3] == 0) { conv = true; break; }
             }
             if (n > A.max_iters) n = A.max_iters;
-            if constexpr (kVeto) {
-                // LLRs that left the float range: failed, not "converged" (ldpc_math.h).  Once per frame; `conv` comes from a control
-                // word every thread read after a barrier, so it is workgroup-uniform and every wave reaches the barrier below
-                if (conv) {
-                    bool bad = false;
-                    for (int i = tid; i < g.N; i += T) bad |= not_finite(lam[i]);
-                    if (__builtin_amdgcn_ballot_w64(bad) != 0 && (tid & 63) == 0) ctl[5] = 1;
-                    lds_barrier();
-                    conv = ctl[5] == 0;
-                }
+        }
+        if constexpr (kVeto) {
+            // LLRs that are not finite -- they left the float range, or the channel gave them: failed, not "converged" (ldpc_math.h),
+            // also for a frame whose channel decisions are a codeword before the first sweep.  Once per frame; `conv` comes from a
+            // control word every thread read after a barrier, so it is workgroup-uniform and every wave reaches the barrier below
+            if (conv) {
+                bool bad = false;
+                for (int i = tid; i < g.N; i += T) bad |= not_finite(lam[i]);
+                if (__builtin_amdgcn_ballot_w64(bad) != 0 && (tid & 63) == 0) ctl[5] = 1;
+                lds_barrier();
+                conv = ctl[5] == 0;
             }
         }
         // ---- result: hard(lam) of a frame that stopped by the rule, the channel's decisions (as stored) otherwise (Orig.hs:69-70)
@@ -518,7 +521,7 @@ __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(Cs
             with_llr_format(A.llr_fmt, [&](auto fmt) {
 #pragma unroll 4
                 for (int i = tid; i < g.N; i += T) {
-                    const float v = conv ? (float)lam[i] : (float)Cell<LT>::of(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
+                    const float v = conv ? (float)lam[i] : (float)Cell<LT>::llr(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
                     A.bits[fN + i] = v > 0.f ? 1 : 0;
                     if (A.final_lam) A.final_lam[fN + i] = (double)v;
                 }

@@ -66,22 +66,23 @@ __device__ __forceinline__ void lds_barrier() {     // LDS traffic only: global 
 }
 
 __device__ __forceinline__ _Float16 sat16(float v) { return (_Float16)__builtin_amdgcn_fmed3f(v, -65504.f, 65504.f); }   // Store<__half>::st
+__device__ __forceinline__ _Float16 llr16(float v) { return sat16(nan_as_zero(v)); }   // a channel LLR as stored: a NaN is an erasure (ldpc_math.h)
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-// eight channel LLRs starting at element i (16-byte aligned), as a decoder with fp16 storage holds them: saturated, rounded to nearest even
+// eight channel LLRs starting at element i (16-byte aligned), as a decoder with fp16 storage holds them: a NaN as +0, saturated, rounded to nearest even
 template <int FMT> __device__ __forceinline__ void load_llr8(const void *base, size_t i, half8 &h) {
     if constexpr (FMT == LLR_F64) {                                      // (never taken: the wide path is for fp16 and f32 input)
 #pragma unroll
-        for (int k = 0; k < 8; k++) h[k] = sat16((float)reinterpret_cast<const double *>(base)[i + k]);
+        for (int k = 0; k < 8; k++) h[k] = llr16((float)reinterpret_cast<const double *>(base)[i + k]);
     } else if constexpr (FMT == LLR_F16) {
         const half8 v = *reinterpret_cast<const half8 *>(reinterpret_cast<const _Float16 *>(base) + i);
 #pragma unroll
-        for (int k = 0; k < 8; k++) h[k] = sat16((float)v[k]);          // (an infinity saturates like any other value)
+        for (int k = 0; k < 8; k++) h[k] = llr16((float)v[k]);          // (an infinity saturates like any other value)
     } else {
         const float4 a = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + i);
         const float4 b = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + i + 4);
-        h[0] = sat16(a.x); h[1] = sat16(a.y); h[2] = sat16(a.z); h[3] = sat16(a.w);
-        h[4] = sat16(b.x); h[5] = sat16(b.y); h[6] = sat16(b.z); h[7] = sat16(b.w);
+        h[0] = llr16(a.x); h[1] = llr16(a.y); h[2] = llr16(a.z); h[3] = llr16(a.w);
+        h[4] = llr16(b.x); h[5] = llr16(b.y); h[6] = llr16(b.z); h[7] = llr16(b.w);
     }
 }
 
@@ -273,7 +274,7 @@ __global__ __launch_bounds__(lds_max_threads(DCLASS, P)) void layered_lds_kernel
         } else {
             with_llr_format(A.llr_fmt, [&](auto fmt) {
 #pragma unroll 8
-                for (int i = tid; i < g.N; i += T) lam[i] = sat16(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
+                for (int i = tid; i < g.N; i += T) lam[i] = llr16(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
             });
         }
         if (tid == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; ctl[4] = 0; }
@@ -430,7 +431,7 @@ __global__ __launch_bounds__(lds_max_threads(DCLASS, P)) void layered_lds_kernel
             with_llr_format(A.llr_fmt, [&](auto fmt) {
 #pragma unroll 4
                 for (int i = tid; i < g.N; i += T) {
-                    const float v = conv ? (float)lam[i] : (float)sat16(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
+                    const float v = conv ? (float)lam[i] : (float)llr16(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
                     A.bits[fN + i] = v > 0.f ? 1 : 0;
                     if (A.final_lam) A.final_lam[fN + i] = (double)v;
                 }

@@ -53,6 +53,10 @@ struct QcLayerArgs {
 // half the bytes of the dominant stream of the record kernel); Store<> converts, saturating on the way to fp16
 template <typename CT, typename LT> __device__ __forceinline__ CT ldlam(const LT *lam, int i) { return (CT)Store<LT>::ld(lam + i); }
 template <typename CT, typename LT> __device__ __forceinline__ void stlam(LT *lam, int i, CT v) { Store<LT>::st(lam + i, v); }
+// a channel LLR on its way into a lam cell: fp16 storage takes a NaN as +0, an erasure (ldpc_math.h nan_as_zero); f32 and f64 as it is
+template <typename LT, typename CT> __device__ __forceinline__ CT llr_in(CT v) {
+    if constexpr (sizeof(LT) == 2) return nan_as_zero(v); else return v;
+}
 // the value a lam cell holds after v was stored into it
 template <typename LT, typename CT> __device__ __forceinline__ CT lam_round(CT v) {
     if constexpr (std::is_same<LT, CT>::value) return v;
@@ -278,7 +282,7 @@ __global__ __launch_bounds__(1024, (DCLASS <= 8 && sizeof(CT) == 4 ? LQC_WAVES_L
                 for (int k = 0; k < deg; k++) msg[(size_t)(e0 + k) * g.sz + r] = (CT)A.st_ne_in[frame * (size_t)g.E + (size_t)e0 * g.sz + (size_t)r * deg + k];
         }
     } else {
-        for (int i = r; i < g.N; i += blockDim.x) stlam(lam, i, load_llr<CT>(A.llr, fN + i, A.llr_fmt));
+        for (int i = r; i < g.N; i += blockDim.x) stlam(lam, i, llr_in<LT>(load_llr<CT>(A.llr, fN + i, A.llr_fmt)));
     }
     __syncthreads();
     bool conv = false;
@@ -333,7 +337,7 @@ __global__ __launch_bounds__(1024, (DCLASS <= 8 && sizeof(CT) == 4 ? LQC_WAVES_L
     }
     // ---- result: hard(lam) of a frame that stopped by the rule, the channel's decisions otherwise (as Orig.hs:69-70)
     for (int i = r; i < g.N; i += blockDim.x) {
-        const CT v = conv ? ldlam<CT>(lam, i) : lam_round<LT>(load_llr<CT>(A.llr, fN + i, A.llr_fmt));   // (an LLR counts as stored in LT)
+        const CT v = conv ? ldlam<CT>(lam, i) : lam_round<LT>(llr_in<LT>(load_llr<CT>(A.llr, fN + i, A.llr_fmt)));   // (an LLR counts as stored in LT)
         A.bits[fN + i] = v > CT(0) ? 1 : 0;
         if (A.final_lam) A.final_lam[fN + i] = (double)v;
     }

@@ -99,10 +99,20 @@ template <class F> __device__ __forceinline__ void with_llr_format(int fmt, F &&
     else if (fmt == LLR_F16) f(std::integral_constant<int, LLR_F16>{});
     else f(std::integral_constant<int, LLR_F32>{});
 }
-// value a float LLR has after being stored as fp16 (LDPC_F16 contexts): saturating round-to-nearest-even
+// A NaN channel LLR says nothing about its bit: every conversion of a channel LLR into a narrower format (fp16 storage, LDPC_F16
+// rounding, packed fp16; the int8 quantiser has its own) takes it in as +0, an erasure (include/ldpc_hip.h, non-finite channel
+// LLRs, rule 1).  fmaxf(NaN, x) = x and v_med3_f32 would make it the most confident "bit 0" the format holds.  One ordered compare
+// and a select per element, in frame prologues only: the state of such a decoder is finite from there on.
+__device__ __forceinline__ float nan_as_zero(float v) { return v == v ? v : 0.0f; }
+// value a float LLR has after being stored as fp16 (LDPC_F16 contexts): a NaN as +0, saturating round-to-nearest-even
 __device__ __forceinline__ float round_f16(float v) {
-    v = fminf(fmaxf(v, -65504.f), 65504.f);
+    v = fminf(fmaxf(nan_as_zero(v), -65504.f), 65504.f);
     return (float)(_Float16)v;   // IEEE binary16, round to nearest even (== __float2half_rn)
+}
+// the saturating rounding alone, as every kernel had it: fmaxf(NaN, x) = x makes a NaN -65504 (fused_layered_body.h, see fused_frame.h LamCellLay)
+__device__ __forceinline__ float round_f16_sat(float v) {
+    v = fminf(fmaxf(v, -65504.f), 65504.f);
+    return (float)(_Float16)v;
 }
 template <typename CT> __device__ __forceinline__ CT maybe_round_f16(CT v, int on) {
     if constexpr (sizeof(CT) == 4) return on ? round_f16(v) : v;

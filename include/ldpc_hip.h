@@ -257,6 +257,31 @@ void ldpc_ctx_destroy(ldpc_ctx *ctx);
 /* LDPC_PATH_FLOOD or LDPC_PATH_FUSED: what the context resolved to */
 int ldpc_ctx_path(const ldpc_ctx *ctx);
 
+/* Non-finite channel LLRs.  A NaN or an infinity reaches every decode entry point in ordinary use: the demappers and the fused
+ * ldpc_sim_generate_mod* calls write a NaN LLR for a NaN sample or gain (f32 and fp16), and ldpc_decode_batch_f64 on an LDPC_F32
+ * context turns a double above FLT_MAX into an infinity.  What a decoder does with such a value (tests/test_nonfinite_llr_gpu.py, one
+ * context per kernel family).  THREE KERNELS ARE NOT UNDER THESE RULES YET:
+ *   - flood_qc_kernel (a quasi-cyclic code with LDPC_PATH_FLOOD, flooding schedule): a decode of frames with NaN / infinite LLRs has
+ *     aborted with a GPU memory fault whose cause is not known; only its +-inf case is tested (tests/test_split_wave_gpu.py);
+ *   - the flooding LDPC_F16PK kernel (built-in and run-time specialised): a NaN is taken in as the LLR -16384, not as +0;
+ *   - the on-chip layered LDPC_F32 / LDPC_F16 kernel of quasi-cyclic codes (fused_layered_kernel, ldpc_jit_layered_*): LDPC_F16 rounding
+ *     takes a NaN as -65504, and a frame whose channel decisions already are a codeword stops before the first sweep, converged, with
+ *     the non-finite LLR it was given (after a sweep the check of rule 3 applies).
+ * Everywhere else:
+ *   1. Converting conversions turn +inf into +max, -inf into -max and a NaN of either sign into +0, an erasure: fp16 storage and
+ *      LDPC_F16 rounding (max 65504), LDPC_F16PK (16384; the layered kernel), LDPC_I8 (127: the quantiser's "NaN -> 0" above).  This holds for f32, f64
+ *      and fp16 input buffers alike, on the 16-byte loads and on the element-wise ones.  After the conversion the frame is an
+ *      ordinary finite frame (oracle/emulate_f16.py r16 / neg_llr16, tests/layered_i8_spec.py quantize).
+ *   2. LDPC_F32 and LDPC_F64 state takes the values as they are.
+ *   3. LDPC_F32 min-sum -- every kernel family, both schedules, the 3/4 or a per-context rule: whatever comes back converged has
+ *      finite final LLRs.  A frame with any non-finite channel LLR therefore FAILS: converged = 0, iters = max_iters, bits = llr > 0
+ *      (a NaN of either sign and -inf give 0, +inf gives 1), final_lam = the channel LLRs as given -- also when the channel's hard
+ *      decisions already are a codeword.
+ *   4. The tanh rule and LDPC_F64 (the parity modes): no parity with the oracle is claimed on non-finite input; 5 and 6 hold.
+ *   5. Self-consistency, every context: a converged frame has H bits = 0 and bits = hard(final_lam); a frame that is not converged
+ *      has iters = max_iters and bits = hard(channel LLR as taken in).
+ *   6. Isolation, every context: the finite frames of a batch come back bit for bit the same -- bits, iters, flags, final_lam --
+ *      whatever non-finite frames share their lane, wave, workgroup or slab of 64, or were decoded by the same workgroup before them. */
 /* ---- decode ------------------------------------------------------------------------------------
  * ldpc_decode_one replaces the per-frame closure
  *   Rate -> Int -> U.Vector Double -> IO (Maybe (U.Vector Bool))     (Arraylet2.hs:151-273)

@@ -23,10 +23,15 @@ import numpy as np
 F16_MAX = np.float32(65504.0)
 
 
-def r16(x):
-    """value of float32 x after being stored as fp16: saturate, round to nearest even, read back"""
+def finite_llr(x):
+    """a NaN carries no information: it is taken in as +0, an erasure (include/ldpc_hip.h, non-finite channel LLRs, rule 1)"""
     x = np.asarray(x, np.float32)
-    return np.clip(x, -F16_MAX, F16_MAX).astype(np.float16).astype(np.float32)
+    return np.where(np.isnan(x), np.float32(0), x)
+
+
+def r16(x):
+    """value of float32 x after being stored as fp16: a NaN as +0, saturate (+-inf too), round to nearest even, read back"""
+    return np.clip(finite_llr(x), -F16_MAX, F16_MAX).astype(np.float16).astype(np.float32)
 
 
 def _rows(g):
@@ -103,9 +108,13 @@ LLR16_MAX = np.float32(16384.0)    # channel LLRs saturate here ...
 U16_MAX = np.float16(2048.0)       # ... and message magnitudes (before their 3/4) here: with column degree <= 30 nothing overflows
 
 
-def neg_llr16(llr):
-    """channel LLRs (float32) -> L0 = -(LLR saturated at +-16384 and rounded to fp16), a zero as +0"""
-    v = np.clip(np.asarray(llr, np.float32), -LLR16_MAX, LLR16_MAX)
+def neg_llr16(llr, nan_is_erasure=True):
+    """channel LLRs (float32) -> L0 = -(LLR saturated at +-16384 and rounded to fp16), a zero and a NaN as +0.
+    nan_is_erasure=False: the flooding kernel's load (csrc/fused_frame.h LamCellPk16Sat), which is not under rule 1 yet: its
+    fmaxf(NaN, -16384) = -16384 makes a NaN the LLR -16384"""
+    x = np.asarray(llr, np.float32)
+    x = finite_llr(x) if nan_is_erasure else np.where(np.isnan(x), -LLR16_MAX, x)
+    v = np.clip(x, -LLR16_MAX, LLR16_MAX)
     h = (np.float32(0) - v).astype(np.float16)
     h[h == 0] = np.float16(0)
     return h
@@ -150,7 +159,7 @@ def decode_minsum_pk16(g, llr, max_iters):
     zero for a frame that has finished -- ldpc_decode_trace leaves those rows untouched)"""
     llr = np.asarray(llr, np.float32)
     F = llr.shape[0]
-    L0 = neg_llr16(llr)
+    L0 = neg_llr16(llr, nan_is_erasure=False)     # (the flooding kernel: see neg_llr16)
     L = L0.copy()
     u = np.zeros((F, g.E), np.float16)
     iters = np.zeros(F, np.int32)

@@ -81,6 +81,28 @@ def test_quantiser():
     assert q(np.array([1.0], np.float16), 3.3).tolist() == [3] and q(np.array([1.0], np.float16), 3.3).dtype == np.int32
 
 
+def test_quantiser_on_non_finite_input_of_every_element_type():
+    """include/ldpc_hip.h, non-finite channel LLRs, rule 1: +inf -> 127, -inf -> -127, NaN of either sign -> 0, whatever the buffer's type"""
+    q = spec.quantize
+    h = np.array([0x7C00, 0xFC00, 0x7E00, 0xFE00, 0x7C01], np.uint16).view(np.float16)       # +inf, -inf, NaN, -NaN, a signalling NaN
+    assert np.isinf(h[:2]).all() and np.isnan(h[2:]).all() and np.signbit(h).tolist() == [False, True, False, True, False]
+    for qs in (4.0, 3.3, 0.01):
+        assert q(h, qs).tolist() == [127, -127, 0, 0, 0]
+    f = np.array([0x7FC00000, 0xFFC00000, 0x7F800000, 0xFF800000], np.uint32).view(np.float32)
+    assert q(f, 4.0).tolist() == [0, 0, 127, -127]
+    d = np.array([1e300, -1e300, np.nan, -np.nan, np.inf, 3e38], np.float64)                 # 1e300 is an infinity once it is a float
+    assert q(d, 4.0).tolist() == [127, -127, 0, 0, 127, 127] and q(d, 1e-38).tolist() == [127, -127, 0, 0, 127, 3]
+    # after the quantiser the frame is an ordinary frame: a decode with NaNs equals the decode with zeros in their place
+    c = load("moon.7.13")
+    _, llr = c.frames(4, 3.0, seed=9)
+    p, z = llr.astype(np.float16), llr.astype(np.float16)
+    p[0, 2], p[1, 4], p[2, :] = h[2], h[3], h[4]
+    z[0, 2], z[1, 4], z[2, :] = 0, 0, 0
+    a = spec.decode_minsum_i8_layered(c.graph, q(p, 4.0), 10)
+    b = spec.decode_minsum_i8_layered(c.graph, q(z, 4.0), 10)
+    assert all(np.array_equal(x, y) for x, y in zip(a, b)) and np.isfinite(a[3]).all()
+
+
 def test_decoder_stopping_rule_and_final_lam():
     c = load("moon.7.13")
     g = c.graph
