@@ -56,6 +56,8 @@ ABI_SYMBOLS = [
     "ldpc_interleaver_create_on", "ldpc_interleaver_destroy", "ldpc_interleaver_dims", "ldpc_interleaver_positions", "ldpc_interleaver_block_positions",
     "ldpc_demap_dev_il", "ldpc_sim_transmit_il", "ldpc_sim_generate_mod_il", "ldpc_interleave_bits_dev", "ldpc_deinterleave_llr_dev",
     "ldpc_demap_dev_il_csi", "ldpc_sim_transmit_il_fading", "ldpc_sim_generate_mod_il_fading",
+    "ldpc_ratematch_create_on", "ldpc_ratematch_destroy", "ldpc_ratematch_dims", "ldpc_ratematch_positions", "ldpc_ratematch_fanin", "ldpc_ratematch_circular_positions",
+    "ldpc_demap_dev_rm", "ldpc_ratematch_llr_dev", "ldpc_ratematch_bits_dev", "ldpc_sim_noise_var_rm", "ldpc_sim_transmit_rm",
     "ldpc_matrix_load", "ldpc_matrix_load_mackay", "ldpc_matrix_destroy", "ldpc_matrix_info", "ldpc_matrix_dense",
     "ldpc_matrix_qc_offsets", "ldpc_code_from_matrix",
     "ldpc_ecc_create", "ldpc_ecc_destroy", "ldpc_ecc_name", "ldpc_ecc_message_length", "ldpc_ecc_codeword_length",
@@ -279,6 +281,20 @@ def lib():
     L.ldpc_demap_dev_il_csi.argtypes = [vp, vp, C.c_int, vp, vp, C.c_double, vp, C.c_int, C.c_float, vp]
     L.ldpc_sim_transmit_il_fading.argtypes = [vp, vp, vp, C.POINTER(FadingStruct), C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp, vp]
     L.ldpc_sim_generate_mod_il_fading.argtypes = [vp, vp, vp, C.POINTER(FadingStruct), C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, C.c_float, vp, vp, vp]
+    L.ldpc_ratematch_create_on.restype = vp
+    L.ldpc_ratematch_create_on.argtypes = [C.c_int, C.c_int, C.c_int, i32p]
+    L.ldpc_ratematch_destroy.restype = None
+    L.ldpc_ratematch_destroy.argtypes = [vp]
+    L.ldpc_ratematch_dims.argtypes = [vp, ip, ip]
+    L.ldpc_ratematch_positions.argtypes = [vp, i32p]
+    L.ldpc_ratematch_fanin.argtypes = [vp, i32p]
+    L.ldpc_ratematch_circular_positions.argtypes = [C.c_int, i32p, C.c_int, C.c_int, i32p]
+    L.ldpc_demap_dev_rm.argtypes = [vp, vp, C.c_int, vp, vp, C.c_double, vp, C.c_int, C.c_float, C.c_int, vp]
+    L.ldpc_ratematch_llr_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_float, C.c_int, vp]
+    L.ldpc_ratematch_bits_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]
+    L.ldpc_sim_noise_var_rm.restype = C.c_double
+    L.ldpc_sim_noise_var_rm.argtypes = [vp, vp, vp, C.c_double]
+    L.ldpc_sim_transmit_rm.argtypes = [vp, vp, vp, C.POINTER(FadingStruct), C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp, vp]
     L.ldpc_matrix_qc_words.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.ldpc_matrix_rank.argtypes = [vp]
     L.ldpc_matrix_load.restype = vp
@@ -987,6 +1003,91 @@ def deinterleave_llr(il: Interleaver, batch, d_llr_tx_ptr, d_llr_ptr, llr_fmt="f
     check(lib().ldpc_deinterleave_llr_dev(_h(il), int(batch), d_llr_tx_ptr, d_llr_ptr, _llr_fmt(llr_fmt), stream))
 
 
+class Ratematch:
+    """A rate-matching table (ldpc_ratematch): transmitted bit t is codeword bit pos[t], pos [E] ANY map into 0..N-1 -- entries may
+    repeat, E may exceed N; the positions no entry names are not sent in this round.  Ratematch.circular(...) is the circular-buffer
+    rule.  The table is checked before the device is touched; it then lives on `device` (None: the calling thread's) with its inverse."""
+
+    def __init__(self, pos, N, device=None):
+        a = np.asarray(pos)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31)):
+            raise LdpcError(EINVAL, "Ratematch: pos must be a one-dimensional array of 32-bit integers")
+        p = np.ascontiguousarray(a, np.int32)
+        dev = int(device) if device is not None else lib().ldpc_current_device()
+        h = lib().ldpc_ratematch_create_on(dev, p.shape[0], int(N), ptr(p, C.c_int32) if p.size else None)
+        if not h:
+            raise LdpcError(lib().ldpc_last_error_code(), last_error())
+        self._h = h
+        self.E, self.N = int(p.shape[0]), int(N)
+        _register(self)
+
+    @staticmethod
+    def circular_positions(n_buf, start, E, buf=None):
+        """ldpc_ratematch_circular_positions (host only): pos[t] = buf[(start + t) mod n_buf], buf None = the identity -> [E] int32"""
+        n_buf, start, E = int(n_buf), int(start), int(E)
+        b = None if buf is None else np.ascontiguousarray(buf, np.int32)
+        if b is not None and b.shape != (n_buf,):
+            raise LdpcError(EINVAL, "Ratematch.circular_positions: buf must be [n_buf]")
+        out = np.zeros(max(E, 1), np.int32)
+        check(lib().ldpc_ratematch_circular_positions(n_buf, None if b is None else ptr(b, C.c_int32), start, E, ptr(out, C.c_int32)))
+        return out
+
+    @classmethod
+    def circular(cls, N, start, E, buf=None, n_buf=None, device=None):
+        """the table of a circular buffer of n_buf (default: len(buf), or N) positions read for E bits from `start`"""
+        n_buf = (N if buf is None else len(buf)) if n_buf is None else n_buf
+        return cls(cls.circular_positions(n_buf, start, E, buf), N, device=device)
+
+    @property
+    def positions(self):
+        out = np.zeros(self.E, np.int32)
+        assert lib().ldpc_ratematch_positions(self._h, ptr(out, C.c_int32)) == self.E
+        return out
+
+    @property
+    def fanin(self):
+        """[N] int32: how many transmitted bits name each codeword position"""
+        out = np.zeros(self.N, np.int32)
+        check(lib().ldpc_ratematch_fanin(self._h, ptr(out, C.c_int32)))
+        return out
+
+    @property
+    def dims(self):
+        a, b = C.c_int(), C.c_int()
+        check(lib().ldpc_ratematch_dims(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if self._h:
+            lib().ldpc_ratematch_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        if _finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def demap_rm(mod: Modulation, rm: Ratematch, batch, d_sym_ptr, d_gain_ptr, noise_var, d_llr_ptr, llr_fmt="f32", qscale=0.0, accumulate=False, stream=None):
+    """ldpc_demap_dev_rm: per codeword position the left-to-right float32 sum of the LLRs of the transmitted bits that name it (d_gain_ptr
+    None: no channel state), written to [batch][rm.N] (accumulate False; 0 where nothing was sent) or added to the soft buffer there"""
+    check(lib().ldpc_demap_dev_rm(_h(mod), _h(rm), int(batch), d_sym_ptr, d_gain_ptr, float(noise_var), d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), int(accumulate),
+                                  stream))
+
+
+def ratematch_llr(rm: Ratematch, batch, d_llr_tx_ptr, d_llr_ptr, llr_fmt="f32", qscale=0.0, accumulate=False, stream=None):
+    """ldpc_ratematch_llr_dev: demap_rm() with the LLRs of the transmitted bits given, [batch][rm.E] float32"""
+    check(lib().ldpc_ratematch_llr_dev(_h(rm), int(batch), d_llr_tx_ptr, d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), int(accumulate), stream))
+
+
+def ratematch_bits(rm: Ratematch, batch, d_cw_ptr, d_tx_ptr, cw_fmt="bytes", tx_fmt="bytes", stream=None):
+    """ldpc_ratematch_bits_dev: codewords [batch][N] ("bytes", or "packed" rows of ceil(N / 8) bytes) -> transmitted bits [batch][E]"""
+    check(lib().ldpc_ratematch_bits_dev(_h(rm), int(batch), d_cw_ptr, Sim._bits_fmt(cw_fmt), d_tx_ptr, Sim._bits_fmt(tx_fmt), stream))
+
+
 class Sim:
     """Device-side frame source + error tally (ldpc_sim)."""
 
@@ -1106,6 +1207,17 @@ class Sim:
         """transmit_il_fading() and demap_il_csi() in one kernel (ldpc_sim_generate_mod_il_fading)"""
         check(lib().ldpc_sim_generate_mod_il_fading(self._h, _h(mod), _h(il), _fad(fad), int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_in_ptr,
                                                     self._bits_fmt(msg_fmt), d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), d_gain_ptr, d_msg_ptr, stream))
+
+    def noise_var_rm(self, mod: "Modulation", rm: "Ratematch", ebn0_db):
+        """noise_var() at the rate of one transmission through the table, R = k / E (ldpc_sim_noise_var_rm)"""
+        return float(lib().ldpc_sim_noise_var_rm(self._h, _h(mod), _h(rm), float(ebn0_db)))
+
+    def transmit_rm(self, mod: "Modulation", rm: "Ratematch", fad: "Fading", seed, first_frame, batch, ebn0_db, d_sym_ptr, d_gain_ptr=None, d_msg_in_ptr=None,
+                    msg_fmt="bytes", d_msg_ptr=None, stream=None):
+        """one transmission through a rate-matching table (ldpc_sim_transmit_rm): samples [batch][mod.symbols(rm.E)][2]; fad None: AWGN.
+        A retransmission: the first round's messages as d_msg_in_ptr and another seed"""
+        check(lib().ldpc_sim_transmit_rm(self._h, _h(mod), _h(rm), _fad(fad), int(seed), int(first_frame), int(batch), float(ebn0_db), d_msg_in_ptr,
+                                         self._bits_fmt(msg_fmt), d_sym_ptr, d_gain_ptr, d_msg_ptr, stream))
 
     def tally(self, batch, d_bits_ptr, d_iters_ptr, d_tally_ptr, stream=None):
         check(lib().ldpc_sim_tally(self._h, int(batch), d_bits_ptr, d_iters_ptr, d_tally_ptr, stream))

@@ -15,6 +15,7 @@
 #include "demap.h"
 #include "interleaver.h"
 #include "fading.h"
+#include "ratematch.h"
 #include "jit.h"
 #include "sim.h"
 #include "systematic.h"
@@ -1637,6 +1638,128 @@ int ldpc_sim_generate_mod_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, c
                                                     qscale == 0.f ? 4.0f : qscale, d_gain);
     return ldpc::fading_generate_launch(st, mod->tab, mod->m, il->tab, fa, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), inv, d_llr, llr_fmt,
                                         qscale == 0.f ? 4.0f : qscale, d_gain);
+}
+
+// ---- rate matching and HARQ (csrc/ratematch.h): the table whose entries may repeat, the demapper summing through it, the table alone,
+// the modulated path reading it
+ldpc_ratematch *ldpc_ratematch_create_on(int device, int E, int N, const int32_t *pos) {
+    if (ldpc::ratematch_check("ldpc_ratematch_create_on", E, N, pos) != LDPC_OK) return nullptr;   // before the device is touched
+    ldpc_ratematch *rm = new (std::nothrow) ldpc_ratematch();
+    if (!rm) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    std::vector<int32_t> tab;
+    // one allocation: pos | pad (0) | inv_ptr | inv_t, each part starting on 16 bytes
+    const size_t ptr_at = ((size_t)E + ldpc::kIlPad + 3) / 4 * 4, t_at = ptr_at + ((size_t)N + 1 + 3) / 4 * 4;
+    try {
+        rm->pos.assign(pos, pos + E);
+        if (ldpc::ratematch_invert(E, N, pos, rm->inv_ptr, rm->inv_t) != LDPC_OK) { delete rm; return nullptr; }
+        tab.assign(t_at + (size_t)E, 0);
+    } catch (const std::bad_alloc &) { delete rm; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    if (device < 0) { delete rm; set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded"); return nullptr; }
+    if (check_device(device) != LDPC_OK) { delete rm; return nullptr; }
+    rm->E = E; rm->N = N; rm->device = device;
+    rm->max_pos = *std::max_element(rm->pos.begin(), rm->pos.end());
+    std::copy(rm->pos.begin(), rm->pos.end(), tab.begin());
+    std::copy(rm->inv_ptr.begin(), rm->inv_ptr.end(), tab.begin() + ptr_at);
+    std::copy(rm->inv_t.begin(), rm->inv_t.end(), tab.begin() + t_at);
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void **)&rm->d_tab, tab.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(rm->d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_error(LDPC_EHIP, "ldpc_ratematch_create_on: %s", hipGetErrorString(e)); ldpc_ratematch_destroy(rm); return nullptr; }
+    rm->tab.pos = rm->d_tab; rm->tab.inv_ptr = rm->d_tab + ptr_at; rm->tab.inv_t = rm->d_tab + t_at; rm->tab.E = E; rm->tab.N = N;
+    return rm;
+}
+
+void ldpc_ratematch_destroy(ldpc_ratematch *rm) {
+    if (!rm) return;
+    if (rm->d_tab) { (void)hipSetDevice(rm->device); hipFree(rm->d_tab); }
+    delete rm;
+}
+
+// the calling thread's device, which must be the table's
+static int rm_device(const char *what, const ldpc_ratematch *rm) {
+    const int device = current_device();
+    if (device < 0) return set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded");
+    if (rm->device != device) return set_error(LDPC_EINVAL, "%s: the table lives on device %d, the calling thread's device is %d", what, rm->device, device);
+    HIPCHK(hipSetDevice(device));
+    return LDPC_OK;
+}
+
+int ldpc_demap_dev_rm(const ldpc_modulation *mod, const ldpc_ratematch *rm, int batch, const float *d_sym, const float *d_gain, double noise_var, void *d_llr, int llr_fmt,
+                      float qscale, int accumulate, void *stream) {
+    if (!mod || !rm || !d_sym || !d_llr) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: null argument");
+    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: bad dimensions (batch=%d)", batch);
+    if (accumulate != 0 && accumulate != 1) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: accumulate must be 0 or 1");
+    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: noise_var must be finite and > 0");
+    int rc = check_llr_out("ldpc_demap_dev_rm", llr_fmt, qscale);
+    if (rc != LDPC_OK) return rc;
+    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0)
+        return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: samples must be 8-byte aligned, gains 4-byte aligned and LLRs aligned to their element");
+    const float inv = (float)(1.0 / (2.0 * noise_var));
+    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
+    if ((rc = rm_device("ldpc_demap_dev_rm", rm)) != LDPC_OK) return rc;
+    const float qs = qscale == 0.f ? 4.0f : qscale;
+    if (mod->b) return ldpc::demap_rm_product_launch((hipStream_t)stream, mod->ax, mod->b, rm->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qs, accumulate != 0);
+    return ldpc::demap_rm_launch((hipStream_t)stream, mod->tab, mod->m, rm->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qs, accumulate != 0);
+}
+
+int ldpc_ratematch_llr_dev(const ldpc_ratematch *rm, int batch, const float *d_llr_tx, void *d_llr, int llr_fmt, float qscale, int accumulate, void *stream) {
+    if (!rm || !d_llr_tx || !d_llr) return set_error(LDPC_EINVAL, "ldpc_ratematch_llr_dev: null argument");
+    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_ratematch_llr_dev: bad dimensions (batch=%d)", batch);
+    if (accumulate != 0 && accumulate != 1) return set_error(LDPC_EINVAL, "ldpc_ratematch_llr_dev: accumulate must be 0 or 1");
+    int rc = check_llr_out("ldpc_ratematch_llr_dev", llr_fmt, qscale);
+    if (rc != LDPC_OK) return rc;
+    if ((uintptr_t)d_llr_tx % 4 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0)
+        return set_error(LDPC_EINVAL, "ldpc_ratematch_llr_dev: the transmitted LLRs must be 4-byte aligned and the output aligned to its element");
+    if ((rc = rm_device("ldpc_ratematch_llr_dev", rm)) != LDPC_OK) return rc;
+    return ldpc::ratematch_llr_launch((hipStream_t)stream, rm->tab, batch, d_llr_tx, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale, accumulate != 0);
+}
+
+int ldpc_ratematch_bits_dev(const ldpc_ratematch *rm, int batch, const void *d_codewords, int cw_fmt, void *d_tx_bits, int tx_fmt, void *stream) {
+    if (!rm || !d_codewords || !d_tx_bits) return set_error(LDPC_EINVAL, "ldpc_ratematch_bits_dev: null argument");
+    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_ratematch_bits_dev: bad dimensions (batch=%d)", batch);
+    if ((cw_fmt != LDPC_BITS_BYTES && cw_fmt != LDPC_BITS_PACKED) || (tx_fmt != LDPC_BITS_BYTES && tx_fmt != LDPC_BITS_PACKED))
+        return set_error(LDPC_EINVAL, "ldpc_ratematch_bits_dev: unknown bit format (LDPC_BITS_BYTES = 0, LDPC_BITS_PACKED = 1)");
+    const int rc = rm_device("ldpc_ratematch_bits_dev", rm);
+    if (rc != LDPC_OK) return rc;
+    // the interleaver's kernel: it reads pos [E] and gathers, and never assumed an injection
+    return ldpc::interleave_bits_launch((hipStream_t)stream, ldpc::rm_as_il(rm->tab), batch, (const uint8_t *)d_codewords, cw_fmt == LDPC_BITS_PACKED, (uint8_t *)d_tx_bits,
+                                        tx_fmt == LDPC_BITS_PACKED);
+}
+
+double ldpc_sim_noise_var_rm(const ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_ratematch *rm, double ebn0_db) {
+    if (!sim || !mod || !rm) { set_error(LDPC_EINVAL, "ldpc_sim_noise_var_rm: null argument"); return 0.0; }
+    const double R = (double)sim->dev.k / (double)rm->E;
+    return mod->es / (2.0 * R * (double)mod->m * pow(10.0, ebn0_db / 10.0));
+}
+
+int ldpc_sim_transmit_rm(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_ratematch *rm, const ldpc_fading *fad, uint64_t seed, uint64_t first_frame, int batch,
+                         double ebn0_db, const void *d_msg_in, int msg_fmt, float *d_sym, float *d_gain, uint8_t *d_msg, void *stream) {
+    int rc = sim_mod_check("ldpc_sim_transmit_rm", sim, mod, batch, d_msg_in, msg_fmt, d_sym);
+    if (rc != LDPC_OK) return rc;
+    if (!rm) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: null table");
+    if (rm->N != sim->dev.N) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: the table is for N = %d, the frame source for N = %d", rm->N, sim->dev.N);
+    if (rm->max_pos >= sim->dev.n_tx)
+        return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: the table reaches position %d, the frame source's codewords are cut at n_tx = %d", rm->max_pos, sim->dev.n_tx);
+    if (rm->device != sim->device) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: the table lives on device %d, the frame source on device %d", rm->device, sim->device);
+    ldpc::FadeArg fa{};
+    if (fad && (rc = fade_arg("ldpc_sim_transmit_rm", fad, fa)) != LDPC_OK) return rc;
+    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: samples must be 8-byte aligned, gains 4-byte aligned");
+    if ((size_t)batch * (size_t)rm->E > ldpc::kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: batch * E is more than one launch holds");
+    const double nv = ldpc_sim_noise_var_rm(sim, mod, rm, ebn0_db);
+    if (!(nv >= 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: Eb/N0 gives no finite noise variance");
+    HIPCHK(hipSetDevice(sim->device));
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = sim_mod_codewords("ldpc_sim_transmit_rm", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
+    // the interleaved path's kernels with n_tx = E: they read pos alone, through il_positions / il_label, which gather
+    const int PB = (sim->dev.n_tx + 7) / 8;
+    const ldpc::IlTab il = ldpc::rm_as_il(rm->tab);
+    const float sg = (float)sqrt(nv);
+    if (fad) {
+        if (mod->b) return ldpc::fading_product_transmit_launch(st, mod->ax, mod->b, il, fa, batch, sim->d_cw, PB, seed, first_frame, sg, d_sym, d_gain);
+        return ldpc::fading_transmit_launch(st, mod->tab, mod->m, il, fa, batch, sim->d_cw, PB, seed, first_frame, sg, d_sym, d_gain);
+    }
+    if (mod->b) return ldpc::product_transmit_il_launch(st, mod->ax, mod->b, il, batch, sim->d_cw, PB, seed, first_frame, sg, d_sym);
+    return ldpc::mod_transmit_il_launch(st, mod->tab, mod->m, il, batch, sim->d_cw, PB, seed, first_frame, sg, d_sym);
 }
 
 int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream) {

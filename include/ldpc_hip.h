@@ -666,6 +666,72 @@ int ldpc_sim_transmit_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const
 int ldpc_sim_generate_mod_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, const ldpc_fading *fad, uint64_t seed,
                                     uint64_t first_frame, int batch, double ebn0_db, const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt,
                                     float qscale, float *d_gain /* [batch][n_sym], may be NULL */, uint8_t *d_msg, void *stream);
+/* ---- rate matching and HARQ soft combining: a position table whose entries MAY REPEAT, and a demapper that SUMS through it, optionally
+ * onto the soft buffer of earlier transmissions.  The injective table stays the interleaver above, and every entry point above keeps its
+ * rule and its bits.  The rule is restated in float32, one operation at a time, in tests/ratematch_spec.py; the kernels reproduce it bit
+ * for bit.
+ * TABLE: transmitted bit t is codeword bit pos[t], t = 0 .. E - 1; symbol s carries transmitted bits m s .. m s + m - 1 by the labelling
+ * rule above (bits t >= E of the last symbol pad as 0).  pos is ANY map into 0 .. N - 1: entries may repeat, and E may be below, at or
+ * above N (a circular buffer read for E > N bits repeats bits).  1 <= E <= 2^31 - 1 - 32, and batch * max(E, N) of a call may be at most
+ * 2^32 - 256, what one launch holds (LDPC_EINVAL otherwise).  Positions that no entry names are NOT SENT in this round.
+ * The object holds, in device memory on `device`, pos and its INVERSE in CSR form: for every position c the transmitted indices t with
+ * pos[t] = c, in ASCENDING order -- the order of the float additions below.  The arguments are checked before the device is touched:
+ * LDPC_EINVAL and NULL for a null table, E < 1, N < 1 or an entry outside 0 .. N - 1; only then LDPC_ENODEVICE (device < 0, no such
+ * device) or LDPC_EHIP.  ldpc_ratematch_fanin: count[c] = how many t name position c (they sum to E). */
+typedef struct ldpc_ratematch ldpc_ratematch;
+ldpc_ratematch *ldpc_ratematch_create_on(int device, int E, int N, const int32_t *pos /* [E] */);
+void ldpc_ratematch_destroy(ldpc_ratematch *rm);
+int ldpc_ratematch_dims(const ldpc_ratematch *rm, int *E, int *N);                    /* either pointer may be NULL */
+int ldpc_ratematch_positions(const ldpc_ratematch *rm, int32_t *pos /* [E], may be NULL */);   /* returns E */
+int ldpc_ratematch_fanin(const ldpc_ratematch *rm, int32_t *count /* [N] */);
+/* The circular-buffer table, by formula, on the host (no device; NO claim is made that it is any standard's table):
+ *   pos[t] = buf[(start + t) mod n_buf],  t = 0 .. E - 1,
+ * buf [n_buf] the buffer's codeword positions in its order (a caller leaves out punctured or filler positions and reorders here), NULL =
+ * the identity 0 .. n_buf - 1; start = the offset of the redundancy version.  LDPC_EINVAL for n_buf < 1, E < 1, start outside
+ * 0 .. n_buf - 1, a null pos.  The entries of buf are judged by ldpc_ratematch_create_on. */
+int ldpc_ratematch_circular_positions(int n_buf, const int32_t *buf /* [n_buf] or NULL */, int start, int E, int32_t *pos /* [E] */);
+/* The receive side, one kernel, no memset before it and no atomic in it.  d_sym [batch][ceil(E / m)][2] as ldpc_demap_dev_il; d_gain
+ * [batch][n_sym] float32 or NULL = no channel state.  The LLR l_t of transmitted bit t is, bit for bit, ldpc_demap_dev_il's (d_gain
+ * NULL) or ldpc_demap_dev_il_csi's (inv_s = fl(inv a)) for that bit, for table objects and product objects; pad bits have none.  For
+ * position c with the transmitted indices t_1 < t_2 < .. < t_r,
+ *   v = fl(fl(fl(l_t1 + l_t2) + l_t3) + ..)  in float32, left to right;  r = 1: v = l_t1.
+ * accumulate = 0: element c = the output conversion of ldpc_demap_dev applied to v; 0 where r = 0.  EVERY element of d_llr [batch][N]
+ *   is written exactly once, none is read.  With an injective table this is ldpc_demap_dev_il (or _csi), bit for bit.
+ * accumulate = 1 (HARQ): d_llr holds the soft buffer of the earlier rounds in the same format, `old`:
+ *   LDPC_LLR_F32  fl(old + v);
+ *   LDPC_LLR_F16  fl(f32(old) + v), clamped to +-65504 and rounded as the fp16 store of ldpc_demap_dev; a NaN sum stays NaN;
+ *   LDPC_LLR_I8   clip(rint(fl(f32(old) + fl(v qscale))), -127, 127); with a NaN v (a NaN sample or gain) the element keeps `old`: an
+ *                 erasure, consistent with the quantiser's NaN -> 0.
+ *   An element with r > 0 is read once and then written once (int8 with a NaN v: read, not written); an element with r = 0 is neither
+ *   read nor written and keeps `old`.  No element is written twice.  The first round of a HARQ process is accumulate = 0, which also
+ *   clears the positions it does not send.
+ * The kernel is a GATHER, one lane per element of d_llr: the distances of a symbol are computed again by the lane of each of its bits.
+ * LDPC_EINVAL as ldpc_demap_dev_il_csi (a null d_gain excepted), for accumulate outside {0, 1}, and for a table on another device than
+ * the calling thread's; all but the last before the device is touched.
+ * NOT PROVIDED: a kernel that generates and demaps in one (the gather reads samples that several lanes share, so they must be in
+ * memory); combining buffers of different formats; a scale on `old`; punctured-position bookkeeping across rounds beyond "keeps old". */
+int ldpc_demap_dev_rm(const ldpc_modulation *mod, const ldpc_ratematch *rm, int batch, const float *d_sym /* [batch][ceil(E/m)][2] */,
+                      const float *d_gain /* [batch][n_sym] or NULL */, double noise_var, void *d_llr /* [batch][N] */, int llr_fmt,
+                      float qscale, int accumulate, void *stream);
+/* The table alone, for a caller's own demapper: the same kernel with l_t = d_llr_tx[f][t] (float32, 4-byte aligned, [batch][E]) in
+ * place of the demapper's rule; the sum, the formats, accumulate and what is read and written are ldpc_demap_dev_rm's.  ldpc_demap_dev on
+ * n_tx = N = E into float32, followed by this call, equals ldpc_demap_dev_rm bit for bit. */
+int ldpc_ratematch_llr_dev(const ldpc_ratematch *rm, int batch, const float *d_llr_tx /* [batch][E] */, void *d_llr /* [batch][N] */,
+                           int llr_fmt, float qscale, int accumulate, void *stream);
+/* The transmit side.  ldpc_ratematch_bits_dev: codewords [batch][N] as LDPC_BITS_BYTES or LDPC_BITS_PACKED -> transmitted bits
+ * [batch][E] in either format (rows of ceil(E / 8) bytes, pad bits 0), bit t = codeword bit pos[t]; as ldpc_interleave_bits_dev.
+ * ldpc_sim_noise_var_rm: ldpc_sim_noise_var with the rate of THIS transmission, R = k / E.
+ * ldpc_sim_transmit_rm: ldpc_sim_transmit_il (fad NULL: AWGN; d_gain is then not written) or ldpc_sim_transmit_il_fading with the
+ * labels gathered through pos [E] and sigma from ldpc_sim_noise_var_rm; d_sym [batch][ceil(E / m)][2].  The noise (Philox counters,
+ * stream 2, Box-Muller), the gains (stream 3) and the symbol rule are untouched.  The table's N must be the code's N, every pos[t] must
+ * be below the source's n_tx (its codewords are cut there) and the table must live on the source's device: LDPC_EINVAL otherwise.
+ * A RETRANSMISSION of the same messages with fresh noise and fresh gains: pass the first round's d_msg as d_msg_in (LDPC_BITS_BYTES)
+ * and another seed; Chase combining uses the same table, incremental redundancy another window of the buffer. */
+int ldpc_ratematch_bits_dev(const ldpc_ratematch *rm, int batch, const void *d_codewords, int cw_fmt, void *d_tx_bits, int tx_fmt, void *stream);
+double ldpc_sim_noise_var_rm(const ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_ratematch *rm, double ebn0_db);
+int ldpc_sim_transmit_rm(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_ratematch *rm, const ldpc_fading *fad /* NULL = AWGN */,
+                         uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg_in, int msg_fmt, float *d_sym,
+                         float *d_gain /* [batch][n_sym], may be NULL */, uint8_t *d_msg, void *stream);
 /* the receive side: message bit i of a frame = decoded bit msg_pos[i] of d_bits [batch][N] bytes (bit 0 of each), written in
  * msg_fmt.  With the systematic form message and parity bits interleave; any source qualifies, LDPC_ENCODER_NONE included. */
 int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream);
