@@ -146,8 +146,11 @@ __device__ __forceinline__ uint32_t row_addr(uint32_t a0, uint32_t p4, uint32_t 
 // phase A for the RPL rows a lane owns in one block row of degree D.  msg: [RPL][D] registers.
 // NEG: LDS holds L = 0 - lam (an exact zero therefore always as +0), so that "lam > 0" is L's sign bit: a row's parity
 // is then the sign of the XOR of its gathered words (one v_xor per edge instead of a v_cmp), and t = lam - m = (-L) - m.
-template <typename CT, int VARIANT, int D, int RPL, int HSTEP, bool SYNDROME_ONLY, bool NEG = false, class Row>
-__device__ __forceinline__ bool rows_a(const char *lds, Row tabrow, uint32_t p4, uint32_t vmask, CT *msg) {
+// MAY_SKIP (NEG form) with `settled` set (wave-uniform): the caller already knows the answer to "some row is unsatisfied"
+// (fused_split_body.h SPLIT_SYN_SKIP), so the wave branches around the row's parity chain and the row reports false; gathers
+// and update are the same.  Without MAY_SKIP there is no such branch and `settled` is not looked at.
+template <typename CT, int VARIANT, int D, int RPL, int HSTEP, bool SYNDROME_ONLY, bool NEG = false, bool MAY_SKIP = false, class Row>
+__device__ __forceinline__ bool rows_a(const char *lds, Row tabrow, uint32_t p4, uint32_t vmask, CT *msg, bool settled = false) {
     const uint32_t b4 = p4;   // edges that cannot wrap (Row::nowrap) address base + immediate: nothing to hoist, no fence
     if constexpr (Row::any_wrap(D)) asm volatile("" : "+v"(p4));  // keeps the loop-invariant address arithmetic inside the turn loop, row by row
     if constexpr (SYNDROME_ONLY) LDPC_COLD_PATH();   // the one extra pass after the last update (Orig.hs:69-70)
@@ -160,16 +163,22 @@ __device__ __forceinline__ bool rows_a(const char *lds, Row tabrow, uint32_t p4,
 #pragma unroll
         for (int h = 0; h < RPL; h++) l[h][k] = lds_ld<CT>(lds + hi, row_addr<RPL, HSTEP>(a0, p4, lo, vmask, h));
     });
+    static_assert(NEG || !MAY_SKIP, "skipping a row's parity: the negated-lam form only");
     bool any = false;
     if constexpr (NEG) {
         static_assert(VARIANT == LDPC_V_MINSUM && sizeof(CT) == 4, "negated lam: the f32 min-sum form only");
         uint32_t odd = 0;
+        bool parity = true;
+        if constexpr (MAY_SKIP) parity = !settled;
+        if (MAY_SKIP ? __builtin_expect(parity, false) : true) {   // (laid out so that the skipping wave falls through)
+            if constexpr (MAY_SKIP) LDPC_SKIP_PATH();
 #pragma unroll
-        for (int h = 0; h < RPL; h++) {
-            uint32_t px = 0;
+            for (int h = 0; h < RPL; h++) {
+                uint32_t px = 0;
 #pragma unroll
-            for (int k = 0; k < D; k++) px ^= __float_as_uint(l[h][k]);
-            odd |= px;
+                for (int k = 0; k < D; k++) px ^= __float_as_uint(l[h][k]);
+                odd |= px;
+            }
         }
         any = (odd >> 31) != 0u;
     } else {

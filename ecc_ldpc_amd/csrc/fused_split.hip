@@ -16,6 +16,10 @@
 // their circulant -- for every rotation one of a pair's two waves cannot, and addresses that edge as lane base +
 // immediate with no arithmetic (as shipped: in phase A, see SPLIT_WAVE_PHASES below).  Four turn loops of ~1 920 instructions
 // instead of two of ~2 280; the kernel's code about doubles (measured harmless: profiles/r06_split_wave_ab.txt).
+// The same instance skips syndrome work whose answer it has (SPLIT_SYN_SKIP): a wave is one frame's rows, and all the frame takes
+// from its rows' parities is the OR "some row is unsatisfied" -- so a wave that has seen an unsatisfied row in its group's first three
+// block rows branches around the XOR chains of the other three (one if-then per row; the turn with every chain stays an ordinary,
+// priced path: tools/isa_histogram.py hot_turn 901-913 VALU, light_turn 847-859).  Exact; profiles/r07_split_syn_skip.txt.
 //
 // Phase B keeps the column "rounds" of fused_msg.hip (round q = q-th contribution of every block column
 // in descending row order = Orig.hs:96 per column): in a round each pair adds the edges it owns; all
@@ -50,6 +54,12 @@
 #endif
 #ifndef SPLIT_NEG_LAM
 #define SPLIT_NEG_LAM 1
+#endif
+// Syndrome skip: a wave that has seen an unsatisfied row among its group's first SPLIT_SYN_SKIP block rows (the two of degree 3 and
+// the first of degree 18) branches around the parity chains of the group's other rows of that turn (three rows of degree 18: 54 of
+// the 78 v_xor).  Measured in profiles/r07_split_syn_skip.txt.
+#ifndef SPLIT_SYN_SKIP
+#define SPLIT_SYN_SKIP 3
 #endif
 #include "fused_split_body.h"
 

@@ -3,7 +3,7 @@
 // generated_tables.h) and at run time by hiprtc for any other single-circulant quasi-cyclic H (jit.cc: plan and
 // rotation table generated as constexpr structs from the code's description) -- so it includes nothing host-side.
 // The ahead-of-time f32 min-sum instances with whole waves of one frame (sz = 128) are built in a tighter form behind
-// SPLIT_WAVE_SPEC, SPLIT_FLAGS_LDS and SPLIT_NEG_LAM below; all three default to off here, so a run-time compiled instance
+// SPLIT_WAVE_SPEC, SPLIT_FLAGS_LDS, SPLIT_NEG_LAM and SPLIT_SYN_SKIP below; all default to off here, so a run-time compiled instance
 // and the sz = 32 instances compile to what they were.
 // What is not about check rows or column rounds -- LDS layout, lane locator, per-frame workgroup OR, the stores of trace rows,
 // snapshots and results -- is shared with the packed-fp16 and the layered bodies: fused_frame.h.
@@ -42,6 +42,13 @@
 // (final_lam, trace) or enters it (channel LLRs, a given lam) is negated on the way.
 #ifndef SPLIT_NEG_LAM
 #define SPLIT_NEG_LAM 0
+#endif
+// Syndrome skip (same instances; one wave = one frame): K > 0 = after the first K of its group's block rows a wave asks, with one
+// ballot, whether any of its lanes has seen an unsatisfied row.  If so its share of the frame's OR "some row is unsatisfied" is
+// settled, and the group's other rows of this turn branch around their parity chains (fused_rows.h rows_a MAY_SKIP): exact,
+// because that OR is the parities' only use.  If not, the other rows run as before.  0 = off.
+#ifndef SPLIT_SYN_SKIP
+#define SPLIT_SYN_SKIP 0
 #endif
 // wave priority while in phase A (check rows: long stretches of independent VALU work) and in phase B (column
 // rounds: short, LDS-bound, barrier-separated).  Measured on jpl.4096, 65 536 frames: A=0/B=0 20.72 ms,
@@ -119,6 +126,11 @@ struct Split {
     }
     static constexpr int owner_br(int br) { return Plan::owner_br(br); }
     static constexpr int owner(int e) { return owner_br(br_of(e)); }
+    static constexpr int own_index(int br) {  // index of block row br among its owner's block rows, plan order
+        int c = 0;
+        for (int b = 0; b < br; b++) c += owner_br(b) == owner_br(br) ? 1 : 0;
+        return c;
+    }
     static constexpr int slot(int e) {  // index of e among its owner's edges, plan order
         int c = 0;
         for (int j = 0; j < e; j++) c += owner(j) == owner(e) ? 1 : 0;
@@ -347,13 +359,21 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
         const bool last = (n >= turns);
         // ---- phase A over the pair's block rows
         bool unsat = false;
+        // Syndrome skip: one wave is one frame here, and all a frame takes from its rows' parities is the OR over its waves' lanes.  A
+        // wave in which some lane has seen an unsatisfied row among the group's first SKIP rows has settled its share of that OR:
+        // its other rows of this turn branch around their XOR chains (rows_a `settled`; one scalar branch per row, if-then only --
+        // an if-else over the rows is linearised by the structurizer into "if (c) A; if (!c) B", with both arms' messages live at once).
+        // The parity blocks are an ordinary turn's work too, not a cold path: a wave runs them whenever its first rows hold.
+        constexpr int SKIP = (NEG && CPW == 1) ? SPLIT_SYN_SKIP : 0;
+        bool settled = false;   // wave-uniform
         static_for<0, Plan::NBR>([&](auto brc) {
             constexpr int br = decltype(brc)::value;
             if constexpr (S::owner_br(br) == P) {
                 constexpr int D = Plan::deg(br), ms0 = S::slot(Plan::ebeg(br));
                 StatRowW<CT, SZ, T, Plan::ebeg(br), WVA> row;
+                if constexpr (SKIP > 0 && S::own_index(br) == SKIP) settled = !last && __ballot(unsat) != 0ull;
                 if (last) unsat |= rows_a<CT, VARIANT, D, 1, 0, true, NEG>(lds, row, WVA < 0 ? p4 : b4, vmask, (CT *)nullptr);
-                else unsat |= rows_a<CT, VARIANT, D, 1, 0, false, NEG>(lds, row, WVA < 0 ? p4 : b4, vmask, &msg[ms0]);
+                else unsat |= rows_a<CT, VARIANT, D, 1, 0, false, NEG, (SKIP > 0 && S::own_index(br) >= SKIP)>(lds, row, WVA < 0 ? p4 : b4, vmask, &msg[ms0], settled);
             }
         });
         // per wave: bit s = some lane of frame s saw an odd row parity (frames interleave lane by lane)

@@ -40,6 +40,9 @@ namespace ldpc { enum { LLR_F32 = 0, LLR_F64 = 1, LLR_F16 = 2 }; }
 // snapshot, ...).  Emits only an assembler comment; tools/isa_histogram.py reads it from the compiler's .s output to
 // tell the ordinary turn of the loop from the rare ones when it counts instructions.
 #define LDPC_COLD_PATH() asm volatile("; ldpc.cold")
+// Marks the enclosing basic block as part of an ORDINARY turn that a wave-uniform branch may leave out (the parity chains behind
+// the syndrome test of fused_split_body.h).  tools/isa_histogram.py counts such blocks in hot_turn and leaves them out of light_turn.
+#define LDPC_SKIP_PATH() asm volatile("; ldpc.skip")
 // first statement of the body of the BP iteration loop when that loop is nested in another (a persistent workgroup's loop over
 // frames): tools/isa_histogram.py then prices the innermost loop around this marker instead of the outermost loop
 #define LDPC_TURN_LOOP() asm volatile("; ldpc.turnloop")

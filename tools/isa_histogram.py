@@ -10,7 +10,9 @@ Method (static): the kernel's text is cut into basic blocks (labels, branch inst
 built from the branch targets, back edges give the natural loops, and the ITERATION loop is the outermost loop with
 the most instructions (a kernel with several such loops of similar size -- the split kernel runs one straight-line
 program per wave group behind a wave-uniform branch -- reports each of them; a wave executes exactly one).  Inside
-the loop two counts are given:
+the loop these counts are given:
+  hot_turn   : the heaviest path through one turn that avoids the blocks the source marks cold (LDPC_COLD_PATH())
+  light_turn : that path without the blocks the source marks as skippable by a wave-uniform branch (LDPC_SKIP_PATH())
   every_turn : blocks that dominate the loop's latch -- executed on every turn of the loop
   whole_loop : every block of the loop (adds conditional work: convergence snapshot, trace stores, the
                syndrome-only last turn); an upper bound
@@ -113,6 +115,8 @@ def blocks_of(lines):
             cur["cold"] = True            # LDPC_COLD_PATH() marker (ldpc_math.h)
         elif "ldpc.cold" in line:
             pending_cold = True
+        if "ldpc.skip" in line and cur is not None:
+            cur["skip"] = True            # LDPC_SKIP_PATH() marker (ldpc_math.h)
         line = line.split(";")[0].rstrip()
         lm = LABEL.match(line)
         if lm:
@@ -265,6 +269,18 @@ def hot_path(blocks, body, header, latch_list, must=frozenset()):
     return path
 
 
+def light_path(blocks, path):
+    """The lightest ORDINARY turn: the hot path without the blocks the source marks with LDPC_SKIP_PATH() as work a wave-uniform
+    branch may leave out (the parity chains behind the syndrome test of the split kernel).  A marked block is dropped only where the
+    block before it on the path does branch around it to the block after it, so what is counted is a path of the graph."""
+    out = []
+    for j, i in enumerate(path):
+        if blocks[i].get("skip") and out and j + 1 < len(path) and path[j + 1] in blocks[out[-1]]["succ"]:
+            continue
+        out.append(i)
+    return out
+
+
 def analyse(name, lines):
     blocks = blocks_of(lines)
     loops, latches, dom = natural_loops(blocks)
@@ -293,8 +309,10 @@ def analyse(name, lines):
         for l in latches[h]:
             every &= dom[l]
         every &= body
+        hot = hot_path(blocks, body, h, latches[h], every)
         res.append({"header": blocks[h]["label"], "blocks": len(body), "instructions": size(body),
-                    "hot_turn": histogram(blocks, hot_path(blocks, body, h, latches[h], every)),
+                    "hot_turn": histogram(blocks, hot),
+                    "light_turn": histogram(blocks, light_path(blocks, hot)),   # == hot_turn for a kernel without LDPC_SKIP_PATH()
                     # (loops that hang off a side path the source marks cold -- trace stores -- do not make a turn data-dependent)
                     "inner_loops": any(h2 != h and h2 in body and loops[h2] < body and not any(blocks[d].get("cold") for d in dom[h2] if d in body)
                                        for h2 in loops),
@@ -363,7 +381,7 @@ def main():
         for lp in a["loops"]:
             e, w = lp["every_turn"], lp["whole_loop"]
             print(f"  loop at {lp['header']}: {lp['instructions']} instructions in {lp['blocks']} blocks")
-            for tag, h in (("hot turn", lp["hot_turn"]), ("every turn", e), ("whole loop", w)):
+            for tag, h in (("hot turn", lp["hot_turn"]), ("light turn", lp["light_turn"]), ("every turn", e), ("whole loop", w)):
                 v = h["units"].get("valu", 0)
                 print(f"    {tag:10s}: VALU {v} (by class {h['valu_by_class']}; cost-weighted {h['valu_cost_weighted_clk']} clk = "
                       f"{h['valu_cost_weighted_clk'] / max(v, 1):.2f} clk/instr)  LDS {h['units'].get('lds', 0)}  spill {h['units'].get('spill', 0)}  SALU {h['units'].get('salu', 0)}  "
