@@ -58,6 +58,8 @@ ABI_SYMBOLS = [
     "ldpc_demap_dev_il_csi", "ldpc_sim_transmit_il_fading", "ldpc_sim_generate_mod_il_fading",
     "ldpc_ratematch_create_on", "ldpc_ratematch_destroy", "ldpc_ratematch_dims", "ldpc_ratematch_positions", "ldpc_ratematch_fanin", "ldpc_ratematch_circular_positions",
     "ldpc_demap_dev_rm", "ldpc_ratematch_llr_dev", "ldpc_ratematch_bits_dev", "ldpc_sim_noise_var_rm", "ldpc_sim_transmit_rm",
+    "ldpc_crc_builtin", "ldpc_crc_bits_host", "ldpc_crc_table", "ldpc_crc_create_on", "ldpc_crc_destroy", "ldpc_crc_params",
+    "ldpc_crc_attach_dev", "ldpc_crc_check_dev", "ldpc_sim_crc_check", "ldpc_sim_tally_crc",
     "ldpc_matrix_load", "ldpc_matrix_load_mackay", "ldpc_matrix_destroy", "ldpc_matrix_info", "ldpc_matrix_dense",
     "ldpc_matrix_qc_offsets", "ldpc_code_from_matrix",
     "ldpc_ecc_create", "ldpc_ecc_destroy", "ldpc_ecc_name", "ldpc_ecc_message_length", "ldpc_ecc_codeword_length",
@@ -295,6 +297,19 @@ def lib():
     L.ldpc_sim_noise_var_rm.restype = C.c_double
     L.ldpc_sim_noise_var_rm.argtypes = [vp, vp, vp, C.c_double]
     L.ldpc_sim_transmit_rm.argtypes = [vp, vp, vp, C.POINTER(FadingStruct), C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp, vp]
+    u32p = C.POINTER(C.c_uint32)
+    L.ldpc_crc_builtin.argtypes = [C.c_int, ip, u32p, u32p, u32p]
+    L.ldpc_crc_bits_host.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u8p, u32p]
+    L.ldpc_crc_table.argtypes = [C.c_int, C.c_uint32, C.c_int, u32p]
+    L.ldpc_crc_create_on.restype = vp
+    L.ldpc_crc_create_on.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
+    L.ldpc_crc_destroy.restype = None
+    L.ldpc_crc_destroy.argtypes = [vp]
+    L.ldpc_crc_params.argtypes = [vp, ip, u32p, u32p, u32p, ip]
+    L.ldpc_crc_attach_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    L.ldpc_crc_check_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
+    L.ldpc_sim_crc_check.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp]
+    L.ldpc_sim_tally_crc.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.ldpc_matrix_qc_words.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.ldpc_matrix_rank.argtypes = [vp]
     L.ldpc_matrix_load.restype = vp
@@ -1088,6 +1103,90 @@ def ratematch_bits(rm: Ratematch, batch, d_cw_ptr, d_tx_ptr, cw_fmt="bytes", tx_
     check(lib().ldpc_ratematch_bits_dev(_h(rm), int(batch), d_cw_ptr, Sim._bits_fmt(cw_fmt), d_tx_ptr, Sim._bits_fmt(tx_fmt), stream))
 
 
+CRC_KINDS = {"crc6": 0, "crc11": 1, "crc16": 2, "crc24a": 3, "crc24b": 4, "crc24c": 5, "crc32": 6}   # LDPC_CRC_*
+
+
+class Crc:
+    """A CRC (ldpc_crc): width w, poly (the generator without x^w), init, xorout, over the first n_bits bits of a message of
+    k = n_bits + w bits; unreflected, the CRC appended MSB first.  The parameters are checked before the device is touched; the table
+    then lives on `device` (None: the calling thread's).  Crc.builtin("crc24a", n_bits) takes a built-in parameter set."""
+
+    def __init__(self, width, poly, init=0, xorout=0, n_bits=None, device=None):
+        if n_bits is None:
+            raise LdpcError(EINVAL, "Crc: n_bits (the payload length) is required")
+        for name, v in (("width", width), ("n_bits", n_bits)):
+            if not -2 ** 31 <= int(v) < 2 ** 31:
+                raise LdpcError(EINVAL, f"Crc: {name} does not fit an int")
+        for name, v in (("poly", poly), ("init", init), ("xorout", xorout)):
+            if not 0 <= int(v) < 2 ** 32:
+                raise LdpcError(EINVAL, f"Crc: {name} must be in 0 .. 2^32 - 1")
+        dev = int(device) if device is not None else lib().ldpc_current_device()
+        h = lib().ldpc_crc_create_on(dev, int(width), int(poly), int(init), int(xorout), int(n_bits))
+        if not h:
+            raise LdpcError(lib().ldpc_last_error_code(), last_error())
+        self._h = h
+        self.width, self.n_bits, self.k = int(width), int(n_bits), int(n_bits) + int(width)
+        _register(self)
+
+    @staticmethod
+    def _kind(kind):
+        return CRC_KINDS[kind] if isinstance(kind, str) else int(kind)
+
+    @staticmethod
+    def builtin_params(kind):
+        """ldpc_crc_builtin (host only) -> (width, poly, init, xorout); kind: a name of CRC_KINDS or the integer of LDPC_CRC_*"""
+        w, p, i, x = C.c_int(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(lib().ldpc_crc_builtin(Crc._kind(kind), C.byref(w), C.byref(p), C.byref(i), C.byref(x)))
+        return w.value, p.value, i.value, x.value
+
+    @classmethod
+    def builtin(cls, kind, n_bits, device=None):
+        w, p, i, x = cls.builtin_params(kind)
+        return cls(w, p, i, x, n_bits=n_bits, device=device)
+
+    @staticmethod
+    def bits_host(width, poly, init, xorout, bits):
+        """ldpc_crc_bits_host (host only): the bit-serial rule over `bits` (one byte each, bit 0 read) -> the CRC"""
+        b = np.ascontiguousarray(bits, np.uint8).reshape(-1)
+        out = C.c_uint32()
+        check(lib().ldpc_crc_bits_host(int(width), int(poly), int(init), int(xorout), b.shape[0], ptr(b, C.c_uint8) if b.size else None, C.byref(out)))
+        return out.value
+
+    @staticmethod
+    def table(width, poly, n_bits):
+        """ldpc_crc_table (host only): T [n_bits] uint32 of the linear form crc = C0 ^ XOR over the set bits i of T[i]"""
+        out = np.zeros(max(int(n_bits), 1), np.uint32)
+        check(lib().ldpc_crc_table(int(width), int(poly), int(n_bits), ptr(out, C.c_uint32)))
+        return out[:int(n_bits)]
+
+    def params(self):
+        """ldpc_crc_params -> (width, poly, init, xorout, n_bits)"""
+        w, p, i, x, n = C.c_int(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int()
+        check(lib().ldpc_crc_params(self._h, C.byref(w), C.byref(p), C.byref(i), C.byref(x), C.byref(n)))
+        return w.value, p.value, i.value, x.value, n.value
+
+    def attach(self, batch, d_msg_ptr, msg_fmt="bytes", stream=None):
+        """ldpc_crc_attach_dev, in place: messages [batch][k] bytes, or "packed" rows of 4 * ceil(k / 32) bytes; bits n_bits .. k - 1 are written"""
+        check(lib().ldpc_crc_attach_dev(self._h, int(batch), d_msg_ptr, Sim._bits_fmt(msg_fmt), stream))
+
+    def check(self, batch, d_msg_ptr, d_ok_ptr, msg_fmt="bytes", stream=None):
+        """ldpc_crc_check_dev: d_ok [batch] bytes <- 1 where the trailing w bits are the CRC of the first n_bits, else 0"""
+        check(lib().ldpc_crc_check_dev(self._h, int(batch), d_msg_ptr, Sim._bits_fmt(msg_fmt), d_ok_ptr, stream))
+
+    def close(self):
+        if self._h:
+            lib().ldpc_crc_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        if _finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Sim:
     """Device-side frame source + error tally (ldpc_sim)."""
 
@@ -1221,6 +1320,15 @@ class Sim:
 
     def tally(self, batch, d_bits_ptr, d_iters_ptr, d_tally_ptr, stream=None):
         check(lib().ldpc_sim_tally(self._h, int(batch), d_bits_ptr, d_iters_ptr, d_tally_ptr, stream))
+
+    def crc_check(self, crc: "Crc", batch, d_bits_ptr, d_ok_ptr, bits_fmt="bytes", stream=None):
+        """ldpc_sim_crc_check: Crc.check() straight on decoded codewords ([batch][N] bytes, or "packed" rows of ceil(N / 8) bytes): the flags
+        of extract_messages() followed by crc.check(), with no message buffer in between"""
+        check(lib().ldpc_sim_crc_check(self._h, _h(crc), int(batch), d_bits_ptr, self._bits_fmt(bits_fmt), d_ok_ptr, stream))
+
+    def tally_crc(self, batch, d_bits_ptr, d_ok_ptr, d_tally_ptr, stream=None):
+        """ldpc_sim_tally_crc: d_tally [4] uint64 += {frames, CRC passes, frames with a message-bit error, passes with an error (undetected)}"""
+        check(lib().ldpc_sim_tally_crc(self._h, int(batch), d_bits_ptr, d_ok_ptr, d_tally_ptr, stream))
 
     def encode_host(self, msg, p):
         msg = np.ascontiguousarray(msg, np.uint8)

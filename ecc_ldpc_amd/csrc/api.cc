@@ -16,6 +16,7 @@
 #include "interleaver.h"
 #include "fading.h"
 #include "ratematch.h"
+#include "crc.h"
 #include "jit.h"
 #include "sim.h"
 #include "systematic.h"
@@ -1760,6 +1761,86 @@ int ldpc_sim_transmit_rm(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_r
     }
     if (mod->b) return ldpc::product_transmit_il_launch(st, mod->ax, mod->b, il, batch, sim->d_cw, PB, seed, first_frame, sg, d_sym);
     return ldpc::mod_transmit_il_launch(st, mod->tab, mod->m, il, batch, sim->d_cw, PB, seed, first_frame, sg, d_sym);
+}
+
+// ---- CRC attach and check (csrc/crc.h): the object, the two kernels on messages, the check on decoded codewords, the tally
+ldpc_crc *ldpc_crc_create_on(int device, int width, uint32_t poly, uint32_t init, uint32_t xorout, int n_bits) {
+    if (ldpc::crc_check_params("ldpc_crc_create_on", width, poly, init, xorout, n_bits) != LDPC_OK) return nullptr;   // before the device is touched
+    ldpc_crc *crc = new (std::nothrow) ldpc_crc();
+    if (!crc) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    const int k = n_bits + width;
+    std::vector<uint32_t> ext;
+    try { ext.assign(((size_t)k + 3) / 4 * 4, 0u); } catch (const std::bad_alloc &) { delete crc; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    if (device < 0) { delete crc; set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded"); return nullptr; }
+    if (check_device(device) != LDPC_OK) { delete crc; return nullptr; }
+    crc->width = width; crc->poly = poly; crc->init = init; crc->xorout = xorout; crc->n_bits = n_bits; crc->device = device;
+    ldpc::crc_table(width, poly, n_bits, ext.data());
+    for (int j = 0; j < width; j++) ext[(size_t)n_bits + j] = 1u << (width - 1 - j);    // the received CRC bits, as the number they spell
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void **)&crc->d_ext, ext.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(crc->d_ext, ext.data(), ext.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_error(LDPC_EHIP, "ldpc_crc_create_on: %s", hipGetErrorString(e)); ldpc_crc_destroy(crc); return nullptr; }
+    crc->tab.ext = crc->d_ext; crc->tab.L = n_bits; crc->tab.w = width; crc->tab.k = k;
+    crc->tab.c0 = ldpc::crc_serial(width, poly, init, xorout, n_bits, nullptr);
+    return crc;
+}
+
+void ldpc_crc_destroy(ldpc_crc *crc) {
+    if (!crc) return;
+    if (crc->d_ext) { (void)hipSetDevice(crc->device); hipFree(crc->d_ext); }
+    delete crc;
+}
+
+// what the two entry points on messages share; on LDPC_OK the calling thread's device, which is the object's, is current
+static int crc_call_check(const char *what, const ldpc_crc *crc, int batch, const void *d_msg, int msg_fmt) {
+    if (!crc || !d_msg) return set_error(LDPC_EINVAL, "%s: null argument", what);
+    if (batch <= 0 || (size_t)batch * (size_t)crc->tab.k > ldpc::kCrcMaxItems)
+        return set_error(LDPC_EINVAL, "%s: batch = %d: must be >= 1 with batch * k at most 2^32 - 256 (k = %d)", what, batch, crc->tab.k);
+    if (msg_fmt != LDPC_BITS_BYTES && msg_fmt != LDPC_BITS_PACKED) return set_error(LDPC_EINVAL, "%s: unknown bit format (LDPC_BITS_BYTES = 0, LDPC_BITS_PACKED = 1)", what);
+    if (msg_fmt == LDPC_BITS_PACKED && (uintptr_t)d_msg % 4 != 0) return set_error(LDPC_EINVAL, "%s: packed message rows must be 4-byte aligned", what);
+    const int device = current_device();
+    if (device < 0) return set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded");
+    if (crc->device != device) return set_error(LDPC_EINVAL, "%s: the CRC lives on device %d, the calling thread's device is %d", what, crc->device, device);
+    HIPCHK(hipSetDevice(device));
+    return LDPC_OK;
+}
+
+int ldpc_crc_attach_dev(const ldpc_crc *crc, int batch, void *d_msg, int msg_fmt, void *stream) {
+    const int rc = crc_call_check("ldpc_crc_attach_dev", crc, batch, d_msg, msg_fmt);
+    if (rc != LDPC_OK) return rc;
+    return ldpc::crc_attach_launch((hipStream_t)stream, crc->tab, batch, d_msg, msg_fmt == LDPC_BITS_PACKED);
+}
+
+int ldpc_crc_check_dev(const ldpc_crc *crc, int batch, const void *d_msg, int msg_fmt, uint8_t *d_ok, void *stream) {
+    if (!d_ok) return set_error(LDPC_EINVAL, "ldpc_crc_check_dev: null argument");
+    const int rc = crc_call_check("ldpc_crc_check_dev", crc, batch, d_msg, msg_fmt);
+    if (rc != LDPC_OK) return rc;
+    const bool packed = msg_fmt == LDPC_BITS_PACKED;
+    return ldpc::crc_check_launch((hipStream_t)stream, crc->tab, batch, (const uint8_t *)d_msg, packed ? (size_t)4 * ((crc->tab.k + 31) / 32) : (size_t)crc->tab.k, packed,
+                                  nullptr, d_ok);
+}
+
+int ldpc_sim_crc_check(const ldpc_sim *sim, const ldpc_crc *crc, int batch, const void *d_bits, int bits_fmt, uint8_t *d_ok, void *stream) {
+    if (!sim || !crc || !d_bits || !d_ok) return set_error(LDPC_EINVAL, "ldpc_sim_crc_check: null argument");
+    if (bits_fmt != LDPC_BITS_BYTES && bits_fmt != LDPC_BITS_PACKED)
+        return set_error(LDPC_EINVAL, "ldpc_sim_crc_check: unknown bit format (LDPC_BITS_BYTES = 0, LDPC_BITS_PACKED = 1)");
+    if (crc->tab.k != sim->dev.k)
+        return set_error(LDPC_EINVAL, "ldpc_sim_crc_check: the CRC is for messages of %d + %d bits, the frame source's have %d", crc->n_bits, crc->width, sim->dev.k);
+    if (crc->device != sim->device) return set_error(LDPC_EINVAL, "ldpc_sim_crc_check: the CRC lives on device %d, the frame source on device %d", crc->device, sim->device);
+    if (batch <= 0 || (size_t)batch * (size_t)sim->dev.k > ldpc::kCrcMaxItems)
+        return set_error(LDPC_EINVAL, "ldpc_sim_crc_check: batch = %d: must be >= 1 with batch * k at most 2^32 - 256 (k = %d)", batch, sim->dev.k);
+    HIPCHK(hipSetDevice(sim->device));
+    const bool packed = bits_fmt == LDPC_BITS_PACKED;
+    return ldpc::crc_check_launch((hipStream_t)stream, crc->tab, batch, (const uint8_t *)d_bits, packed ? (size_t)(sim->dev.N + 7) / 8 : (size_t)sim->dev.N, packed,
+                                  sim->systematic ? sim->sy.msg_pos : nullptr, d_ok);
+}
+
+int ldpc_sim_tally_crc(ldpc_sim *sim, int batch, const uint8_t *d_bits, const uint8_t *d_ok, uint64_t *d_tally, void *stream) {
+    if (!sim || !d_bits || !d_ok || !d_tally) return set_error(LDPC_EINVAL, "ldpc_sim_tally_crc: null argument");
+    if (batch <= 0 || batch > sim->max_batch) return set_error(LDPC_EINVAL, "ldpc_sim_tally_crc: batch %d outside 1..%d", batch, sim->max_batch);
+    HIPCHK(hipSetDevice(sim->device));
+    return ldpc::crc_tally_launch((hipStream_t)stream, sim->systematic ? sim->sy.msg_pos : nullptr, sim->dev.N, sim->dev.k, sim->dev.kwords, sim->d_msgw, batch,
+                                  d_bits, d_ok, (unsigned long long *)d_tally);
 }
 
 int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream) {

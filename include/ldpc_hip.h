@@ -741,6 +741,53 @@ int ldpc_sim_tally(ldpc_sim *sim, int batch, const uint8_t *d_bits, const int32_
                    uint64_t *d_tally, void *stream);
 /* host-side encode of one message with the same rule (parity only, p bytes; M bytes for the encoder from H) -- used by tests */
 int ldpc_sim_encode_host(const ldpc_sim *sim, const uint8_t *msg, uint8_t *parity);
+/* ---- CRC attach and check: what a receiver has in place of the transmitted message.  A message of k bits is L payload bits followed
+ * by the w bits of their CRC.  The rule is integer arithmetic, restated in tests/crc_spec.py; the kernels reproduce it exactly.
+ * PARAMETERS: width w in 1 .. 32; poly = the generator without its x^w term, odd and below 2^w; init and xorout below 2^w; the payload
+ * length L = n_bits >= 1; k = L + w <= 2^24.
+ * REGISTER: r = init; for the payload bits b_i, i = 0 .. L - 1, in message order (msg_pos order, the order ldpc_sim_encode_messages takes):
+ *   top = (r >> (w - 1)) & 1;  r = (r << 1) & (2^w - 1);  if (top ^ b_i) r ^= poly;
+ * crc = r ^ xorout.  No reflection and no notion of a byte.  APPENDED: message bit L + j = (crc >> (w - 1 - j)) & 1, j = 0 .. w - 1, the
+ * MSB first.  LDPC_BITS_PACKED is the layout above (bit i in byte i / 8 at bit i % 8), so for whole bytes w = 32, poly 0x04C11DB7,
+ * init = xorout = 0xFFFFFFFF over a packed row is zlib's crc32 of those bytes with its 32 bits reversed.
+ * LINEAR FORM: crc = C0 ^ XOR over the set payload bits i of T[i], T[i] = the register after the unit vector e_i with init = xorout = 0,
+ * C0 = the CRC of L zero bits.
+ * The built-in parameter sets are defined by formula, with NO claim that they are any standard's (w, poly, init, xorout):
+ *   LDPC_CRC_6 (6, 0x21, 0, 0)  LDPC_CRC_11 (11, 0x621, 0, 0)  LDPC_CRC_16 (16, 0x1021, 0, 0)  LDPC_CRC_24A (24, 0x864CFB, 0, 0)
+ *   LDPC_CRC_24B (24, 0x800063, 0, 0)  LDPC_CRC_24C (24, 0xB2B117, 0, 0)  LDPC_CRC_32 (32, 0x04C11DB7, 0xFFFFFFFF, 0xFFFFFFFF). */
+enum { LDPC_CRC_6 = 0, LDPC_CRC_11 = 1, LDPC_CRC_16 = 2, LDPC_CRC_24A = 3, LDPC_CRC_24B = 4, LDPC_CRC_24C = 5, LDPC_CRC_32 = 6 };
+/* Host only, no device touched.  ldpc_crc_builtin: the parameters of a kind (any pointer may be NULL); LDPC_EINVAL for an unknown kind.
+ * ldpc_crc_bits_host: the bit-serial rule over n_bits bytes, bit 0 of each.  ldpc_crc_table: T [n_bits] of the linear form.  Both check
+ * their parameters as ldpc_crc_create_on does. */
+int ldpc_crc_builtin(int kind, int *width, uint32_t *poly, uint32_t *init, uint32_t *xorout);
+int ldpc_crc_bits_host(int width, uint32_t poly, uint32_t init, uint32_t xorout, int n_bits, const uint8_t *bits /* [n_bits] */, uint32_t *crc);
+int ldpc_crc_table(int width, uint32_t poly, int n_bits, uint32_t *table /* [n_bits] */);
+/* The object holds the table the kernels read (4 k bytes, rounded up to 16) in device memory on `device`.  The arguments are checked
+ * before the device is touched: LDPC_EINVAL and NULL for a width outside 1 .. 32, an even poly, poly, init or xorout at or above 2^w,
+ * n_bits < 1, n_bits + width > 2^24; only then LDPC_ENODEVICE (device < 0, no such device) or LDPC_EHIP. */
+typedef struct ldpc_crc ldpc_crc;
+ldpc_crc *ldpc_crc_create_on(int device, int width, uint32_t poly, uint32_t init, uint32_t xorout, int n_bits);
+void ldpc_crc_destroy(ldpc_crc *crc);
+int ldpc_crc_params(const ldpc_crc *crc, int *width, uint32_t *poly, uint32_t *init, uint32_t *xorout, int *n_bits);   /* any pointer may be NULL */
+/* Device pointers, the calling thread's device = the object's, enqueued on `stream`, not synchronised.  batch >= 1 and batch * k <=
+ * 2^32 - 256 (LDPC_EINVAL otherwise, and for a null pointer or an unknown format).  One wave per frame; no atomics.
+ * ldpc_crc_attach_dev, IN PLACE: reads message bits 0 .. L - 1 and writes bits L .. k - 1.
+ *   LDPC_BITS_BYTES   d_msg [batch][k]: only bit 0 of a payload byte is read and no payload byte is written; the CRC bytes are 0 or 1.
+ *   LDPC_BITS_PACKED  rows of 4 * ceil(k / 32) bytes, 4-byte aligned: payload bits are kept, bits >= k of the last word are written 0.
+ * ldpc_crc_check_dev: d_ok[f] = 1 if the trailing w bits of message f are the CRC of its first L, else 0; every element of d_ok
+ * [batch] is written exactly once, the messages are not written. */
+int ldpc_crc_attach_dev(const ldpc_crc *crc, int batch, void *d_msg, int msg_fmt, void *stream);
+int ldpc_crc_check_dev(const ldpc_crc *crc, int batch, const void *d_msg, int msg_fmt, uint8_t *d_ok /* [batch] */, void *stream);
+/* The same check straight on decoded codewords: message bit i = decoded bit msg_pos[i] of d_bits, [batch][N] bytes (LDPC_BITS_BYTES, bit
+ * 0 of each) or packed rows of ceil(N / 8) bytes as ldpc_decode_batch_dev_packed writes them (LDPC_BITS_PACKED).  No message buffer is
+ * written in between: the flags are those of ldpc_sim_extract_messages followed by ldpc_crc_check_dev, bit for bit.  LDPC_EINVAL also
+ * when L + w is not the source's k, or the object lives on another device than the source. */
+int ldpc_sim_crc_check(const ldpc_sim *sim, const ldpc_crc *crc, int batch, const void *d_bits, int bits_fmt, uint8_t *d_ok /* [batch] */, void *stream);
+/* d_tally[4] (device, uint64) += {frames, CRC passes (d_ok != 0), frames with a message-bit error, frames that pass AND have an error:
+ * the undetected errors}.  d_bits [batch][N] bytes; the messages compared against are those ldpc_sim_tally compares against: the ones
+ * the source last drew, or the caller's after ldpc_sim_generate_from, ldpc_sim_encode_messages or a transmit with d_msg_in.
+ * 1 <= batch <= max_batch. */
+int ldpc_sim_tally_crc(ldpc_sim *sim, int batch, const uint8_t *d_bits, const uint8_t *d_ok /* [batch] */, uint64_t *d_tally /* [4] */, void *stream);
 
 /* ---- matrix ingest --------------------------------------------------------------------------------
  * replaces loadMatrix (src/Data/BitMatrix/Loader.hs:58-81): `name` is "<matrix>/H" or "<matrix>/G";
