@@ -22,6 +22,7 @@ SUM_REFERENCE, SUM_ARRAYLET, SUM_SPARSE = 0, 1, 2
 BITS_BYTES, BITS_PACKED = 0, 1   # ldpc_bit_format
 MOD_BPSK, MOD_QPSK, MOD_8PSK, MOD_16QAM = 1, 2, 3, 4
 MOD_64QAM, MOD_256QAM, MOD_1024QAM, MOD_4096QAM = 6, 8, 10, 12   # product constellations: the kind number is m
+DEMAP_MAXLOG, DEMAP_LOGMAP = 0, 1   # ldpc_demap_rule
 LLR_F32, LLR_F16, LLR_I8 = 0, 1, 2   # LDPC_LLR_*: the output formats of the demapper
 
 
@@ -52,7 +53,7 @@ ABI_SYMBOLS = [
     "ldpc_csr_systematic_form", "ldpc_sim_create_systematic_on", "ldpc_sim_message_length", "ldpc_sim_positions",
     "ldpc_sim_encode_messages", "ldpc_sim_generate_from", "ldpc_sim_extract_messages",
     "ldpc_modulation_create", "ldpc_modulation_create_builtin", "ldpc_modulation_destroy", "ldpc_modulation_bits", "ldpc_modulation_points", "ldpc_modulation_energy",
-    "ldpc_modulation_symbols", "ldpc_modulation_create_product", "ldpc_modulation_axis_levels", "ldpc_demap_dev", "ldpc_sim_noise_var", "ldpc_sim_transmit", "ldpc_sim_generate_mod",
+    "ldpc_modulation_symbols", "ldpc_modulation_create_product", "ldpc_modulation_axis_levels", "ldpc_modulation_with_rule", "ldpc_modulation_rule", "ldpc_demap_dev", "ldpc_sim_noise_var", "ldpc_sim_transmit", "ldpc_sim_generate_mod",
     "ldpc_interleaver_create_on", "ldpc_interleaver_destroy", "ldpc_interleaver_dims", "ldpc_interleaver_positions", "ldpc_interleaver_block_positions",
     "ldpc_demap_dev_il", "ldpc_sim_transmit_il", "ldpc_sim_generate_mod_il", "ldpc_interleave_bits_dev", "ldpc_deinterleave_llr_dev",
     "ldpc_demap_dev_il_csi", "ldpc_sim_transmit_il_fading", "ldpc_sim_generate_mod_il_fading",
@@ -263,6 +264,9 @@ def lib():
     L.ldpc_modulation_create_product.restype = vp
     L.ldpc_modulation_create_product.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.ldpc_modulation_axis_levels.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.ldpc_modulation_with_rule.restype = vp
+    L.ldpc_modulation_with_rule.argtypes = [vp, C.c_int]
+    L.ldpc_modulation_rule.argtypes = [vp]
     L.ldpc_demap_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, C.c_int, C.c_float, vp]
     L.ldpc_sim_noise_var.restype = C.c_double
     L.ldpc_sim_noise_var.argtypes = [vp, vp, C.c_double]
@@ -827,7 +831,10 @@ class Modulation:
     """A labelled constellation (ldpc_modulation): points [2^m][2] float32 (I, Q), m = 1..6, or a built-in by name.  Symbol s of a
     frame carries codeword bits m s .. m s + m - 1, the first one the MSB of the label = the index into the table.
     Modulation.product(levels_i, levels_q) and the built-ins "64qam" .. "4096qam" are product constellations: 2^b levels an axis,
-    b = 1..6, m = 2 b, label = (index into levels_i) << b | (index into levels_q)."""
+    b = 1..6, m = 2 b, label = (index into levels_i) << b | (index into levels_q).
+    The demappers' LLR rule travels with the object: max-log unless with_rule("logmap") made it (include/ldpc_hip.h, THE LLR RULE)."""
+
+    RULES = {"maxlog": DEMAP_MAXLOG, "logmap": DEMAP_LOGMAP}
 
     BUILTIN = {"bpsk": MOD_BPSK, "qpsk": MOD_QPSK, "8psk": MOD_8PSK, "16qam": MOD_16QAM,
                "64qam": MOD_64QAM, "256qam": MOD_256QAM, "1024qam": MOD_1024QAM, "4096qam": MOD_4096QAM}
@@ -884,6 +891,20 @@ class Modulation:
     @property
     def energy(self):
         return float(lib().ldpc_modulation_energy(self._h))
+
+    def with_rule(self, rule):
+        """ldpc_modulation_with_rule: a new object with this constellation, demapped by "maxlog" or "logmap" (or the rule's number)"""
+        r = self.RULES.get(rule.lower(), -1) if isinstance(rule, str) else int(rule)
+        h = lib().ldpc_modulation_with_rule(self._h, r)
+        if not h:
+            raise LdpcError(lib().ldpc_last_error_code(), last_error())
+        return type(self)(None, _handle=h)
+
+    @property
+    def rule(self):
+        """the demappers' LLR rule, "maxlog" or "logmap" (ldpc_modulation_rule)"""
+        r = int(lib().ldpc_modulation_rule(self._h))
+        return {v: k for k, v in self.RULES.items()}[r]
 
     def symbols(self, n_tx):
         n = lib().ldpc_modulation_symbols(self._h, int(n_tx))

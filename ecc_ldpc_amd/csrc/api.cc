@@ -1355,8 +1355,8 @@ int ldpc_demap_dev(const ldpc_modulation *mod, int batch, int n_tx, int N, const
     const int device = current_device();
     if (device < 0) return set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded");
     HIPCHK(hipSetDevice(device));
-    if (mod->b) return ldpc::demap_product_launch((hipStream_t)stream, mod->ax, mod->b, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
-    return ldpc::demap_launch((hipStream_t)stream, mod->tab, mod->m, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    if (mod->b) return ldpc::demap_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    return ldpc::demap_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
 }
 
 double ldpc_sim_noise_var(const ldpc_sim *sim, const ldpc_modulation *mod, double ebn0_db) {
@@ -1402,6 +1402,13 @@ static int sim_mod_check(const char *what, const ldpc_sim *sim, const ldpc_modul
     return LDPC_OK;
 }
 
+// the fused map + noise + demap kernels hold the max-log rule only (include/ldpc_hip.h, THE LLR RULE)
+static int sim_mod_maxlog_only(const char *what, const ldpc_modulation *mod) {
+    if (mod->rule != LDPC_DEMAP_MAXLOG)
+        return set_error(LDPC_EUNSUPPORTED, "%s: no fused kernel for the log-MAP rule (LDPC_DEMAP_LOGMAP); use ldpc_sim_transmit* and a demapper", what);
+    return LDPC_OK;
+}
+
 int ldpc_sim_transmit(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg_in, int msg_fmt,
                       float *d_sym, uint8_t *d_msg, void *stream) {
     int rc = sim_mod_check("ldpc_sim_transmit", sim, mod, batch, d_msg_in, msg_fmt, d_sym);
@@ -1420,6 +1427,7 @@ int ldpc_sim_generate_mod(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t se
                           void *d_llr, int llr_fmt, float qscale, uint8_t *d_msg, void *stream) {
     int rc = sim_mod_check("ldpc_sim_generate_mod", sim, mod, batch, d_msg_in, msg_fmt, d_llr);
     if (rc != LDPC_OK) return rc;
+    if ((rc = sim_mod_maxlog_only("ldpc_sim_generate_mod", mod)) != LDPC_OK) return rc;
     if ((rc = check_llr_out("ldpc_sim_generate_mod", llr_fmt, qscale)) != LDPC_OK) return rc;
     if ((uintptr_t)d_llr % (llr_fmt == LDPC_LLR_F32 ? 4 : llr_fmt == LDPC_LLR_F16 ? 2 : 1) != 0) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod: LLRs must be aligned to their element");
     const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
@@ -1489,8 +1497,8 @@ int ldpc_demap_dev_il(const ldpc_modulation *mod, const ldpc_interleaver *il, in
     const float inv = (float)(1.0 / (2.0 * noise_var));
     if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
     if ((rc = il_device("ldpc_demap_dev_il", il)) != LDPC_OK) return rc;
-    if (mod->b) return ldpc::demap_il_product_launch((hipStream_t)stream, mod->ax, mod->b, il->tab, batch, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
-    return ldpc::demap_il_launch((hipStream_t)stream, mod->tab, mod->m, il->tab, batch, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    if (mod->b) return ldpc::demap_il_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, il->tab, batch, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    return ldpc::demap_il_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, il->tab, batch, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
 }
 
 int ldpc_interleave_bits_dev(const ldpc_interleaver *il, int batch, const void *d_codewords, int cw_fmt, void *d_tx_bits, int tx_fmt, void *stream) {
@@ -1547,6 +1555,7 @@ int ldpc_sim_generate_mod_il(ldpc_sim *sim, const ldpc_modulation *mod, const ld
                              const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt, float qscale, uint8_t *d_msg, void *stream) {
     int rc = sim_mod_check("ldpc_sim_generate_mod_il", sim, mod, batch, d_msg_in, msg_fmt, d_llr);
     if (rc != LDPC_OK) return rc;
+    if ((rc = sim_mod_maxlog_only("ldpc_sim_generate_mod_il", mod)) != LDPC_OK) return rc;
     if ((rc = sim_il_check("ldpc_sim_generate_mod_il", sim, il)) != LDPC_OK) return rc;
     if ((rc = check_llr_out("ldpc_sim_generate_mod_il", llr_fmt, qscale)) != LDPC_OK) return rc;
     if ((uintptr_t)d_llr % llr_elem(llr_fmt) != 0) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il: LLRs must be aligned to their element");
@@ -1593,8 +1602,8 @@ int ldpc_demap_dev_il_csi(const ldpc_modulation *mod, const ldpc_interleaver *il
     const float inv = (float)(1.0 / (2.0 * noise_var));
     if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
     if ((rc = il_device("ldpc_demap_dev_il_csi", il)) != LDPC_OK) return rc;
-    if (mod->b) return ldpc::demap_csi_product_launch((hipStream_t)stream, mod->ax, mod->b, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
-    return ldpc::demap_csi_launch((hipStream_t)stream, mod->tab, mod->m, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    if (mod->b) return ldpc::demap_csi_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    return ldpc::demap_csi_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
 }
 
 int ldpc_sim_transmit_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, const ldpc_fading *fad, uint64_t seed, uint64_t first_frame, int batch,
@@ -1620,6 +1629,7 @@ int ldpc_sim_generate_mod_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, c
                                     void *stream) {
     int rc = sim_mod_check("ldpc_sim_generate_mod_il_fading", sim, mod, batch, d_msg_in, msg_fmt, d_llr);
     if (rc != LDPC_OK) return rc;
+    if ((rc = sim_mod_maxlog_only("ldpc_sim_generate_mod_il_fading", mod)) != LDPC_OK) return rc;
     if ((rc = sim_il_check("ldpc_sim_generate_mod_il_fading", sim, il)) != LDPC_OK) return rc;
     ldpc::FadeArg fa;
     if ((rc = fade_arg("ldpc_sim_generate_mod_il_fading", fad, fa)) != LDPC_OK) return rc;
@@ -1699,8 +1709,8 @@ int ldpc_demap_dev_rm(const ldpc_modulation *mod, const ldpc_ratematch *rm, int 
     if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
     if ((rc = rm_device("ldpc_demap_dev_rm", rm)) != LDPC_OK) return rc;
     const float qs = qscale == 0.f ? 4.0f : qscale;
-    if (mod->b) return ldpc::demap_rm_product_launch((hipStream_t)stream, mod->ax, mod->b, rm->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qs, accumulate != 0);
-    return ldpc::demap_rm_launch((hipStream_t)stream, mod->tab, mod->m, rm->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qs, accumulate != 0);
+    if (mod->b) return ldpc::demap_rm_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, rm->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qs, accumulate != 0);
+    return ldpc::demap_rm_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, rm->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qs, accumulate != 0);
 }
 
 int ldpc_ratematch_llr_dev(const ldpc_ratematch *rm, int batch, const float *d_llr_tx, void *d_llr, int llr_fmt, float qscale, int accumulate, void *stream) {

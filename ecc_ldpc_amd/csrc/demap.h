@@ -1,6 +1,7 @@
 // demap.h -- the modulation object and the device functions of the mapper and the max-log soft demapper, shared by the stand-alone
 // demapper (demap.hip) and the frame source's modulated path (sim_mod.hip): one copy of the symbol rule and of the LLR rule, so the
-// fused kernel equals the two-step one bit for bit.  The rule is restated in tests/modulation_spec.py.
+// fused kernel equals the two-step one bit for bit.  The rule is restated in tests/modulation_spec.py.  The stand-alone demappers also
+// hold the exact (log-MAP) rule, chosen by the modulation object's `rule` (demap_llrs_logmap below; tests/demap_logmap_spec.py).
 #pragma once
 #include "internal.h"
 #ifdef __HIPCC__
@@ -24,7 +25,7 @@ struct AxisTab {
 };
 
 // d_llr [batch][N] <- the LLRs of d_sym [batch][n_sym][2]; inv = float32(1 / (2 sigma^2))
-int demap_launch(hipStream_t st, const ModTab &tab, int m, int batch, int n_tx, int N, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
+int demap_launch(hipStream_t st, const ModTab &tab, int m, int rule, int batch, int n_tx, int N, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
 // d_cw: packed codewords [batch][PB] (bit i in byte i / 8 at bit i % 8, pad bits 0).  d_sym [batch][n_sym][2] <- the noisy symbols
 int mod_transmit_launch(hipStream_t st, const ModTab &tab, int m, int batch, int n_tx, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
                         float *d_sym);
@@ -33,7 +34,7 @@ int mod_generate_launch(hipStream_t st, const ModTab &tab, int m, int batch, int
                         float inv, void *d_llr, int fmt, float qscale);
 
 // the same three for a product constellation of b bits an axis (m = 2 b)
-int demap_product_launch(hipStream_t st, const AxisTab &tab, int b, int batch, int n_tx, int N, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
+int demap_product_launch(hipStream_t st, const AxisTab &tab, int b, int rule, int batch, int n_tx, int N, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
 int product_transmit_launch(hipStream_t st, const AxisTab &tab, int b, int batch, int n_tx, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
                             float *d_sym);
 int product_generate_launch(hipStream_t st, const AxisTab &tab, int b, int batch, int n_tx, int N, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
@@ -102,6 +103,62 @@ __device__ __forceinline__ void demap_llrs(const ModTab &tab, float yI, float yQ
     for (int j = 0; j < M; j++) llr[j] = (m0[j] - m1[j]) * inv;
 }
 
+// the log-MAP correction of one bit from the two sums of its subsets: c1 - c0, c_v = log(sum_v).  Every sum holds an exp(0) = 1, so it
+// lies in [1, 2^(M-1)] and no log sees a 0.  Where the correction is zero (single-point subsets; high SNR, where every other term has
+// underflowed; a scale of 0, where both sums are the same integer) the max-log value stands as it is, the sign of a zero included:
+// -0 + 0 would be +0.  A NaN correction is not zero and makes the LLR NaN
+__device__ __forceinline__ float logmap_llr(float maxlog, float s0, float s1) {
+    const float corr = __logf(s1) - __logf(s0);
+    return corr != 0.f ? maxlog + corr : maxlog;
+}
+
+// log-MAP LLRs of one sample (include/ldpc_hip.h, "The LLR rule"): the max-log value of demap_llrs, bit for bit, plus c1 - c0,
+// c_v = log(sum over the points p whose bit j is v of exp(-(d_p - m_v) inv)).  Two passes: the minima, then the M 2^M exponentials;
+// the second pass computes the distances again from the uniform table (5 operations a point beside M exponentials) -- the same
+// float32 operations, hence the same values -- where keeping them would hold 2^M registers across it.  The sums run in label order
+template <int M>
+__device__ __forceinline__ void demap_llrs_logmap(const ModTab &tab, float yI, float yQ, float inv, float (&llr)[M]) {
+    float m0[M], m1[M], s0[M], s1[M];
+#pragma unroll
+    for (int p = 0; p < (1 << M); p++) {
+        const float dx = yI - tab.pt[p][0], dy = yQ - tab.pt[p][1];
+        const float d = dx * dx + dy * dy;
+#pragma unroll
+        for (int j = 0; j < M; j++) {
+            const int bit = (p >> (M - 1 - j)) & 1;
+            if (bit) m1[j] = (p == (1 << (M - 1 - j))) ? d : __builtin_fminf(m1[j], d);
+            else m0[j] = (p == 0) ? d : __builtin_fminf(m0[j], d);
+        }
+    }
+    if constexpr (M == 1) {                               // one point a subset: both sums are exp(0)
+        llr[0] = (m0[0] - m1[0]) * inv;
+        return;
+    }
+#pragma unroll
+    for (int p = 0; p < (1 << M); p++) {
+        const float dx = yI - tab.pt[p][0], dy = yQ - tab.pt[p][1];
+        const float d = dx * dx + dy * dy;
+#pragma unroll
+        for (int j = 0; j < M; j++) {
+            const int bit = (p >> (M - 1 - j)) & 1;
+            const float e = __expf((bit ? m1[j] - d : m0[j] - d) * inv);
+            if (bit) s1[j] = (p == (1 << (M - 1 - j))) ? e : s1[j] + e;
+            else s0[j] = (p == 0) ? e : s0[j] + e;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < M; j++) llr[j] = logmap_llr((m0[j] - m1[j]) * inv, s0[j], s1[j]);
+}
+
+// the LLRs of one sample by the rule of the modulation object (LDPC_DEMAP_MAXLOG = 0, LDPC_DEMAP_LOGMAP = 1): a template argument of
+// every demapper kernel, so a max-log instance holds demap_llrs alone, as before the rule existed
+enum { DEMAP_MAXLOG = 0, DEMAP_LOGMAP = 1 };
+template <int M, int RULE>
+__device__ __forceinline__ void demap_llrs_by(const ModTab &tab, float yI, float yQ, float inv, float (&llr)[M]) {
+    if constexpr (RULE == DEMAP_LOGMAP) demap_llrs_logmap<M>(tab, yI, yQ, inv, llr);
+    else demap_llrs<M>(tab, yI, yQ, inv, llr);
+}
+
 // one output element in the decoder's input formats
 template <typename OT> __device__ __forceinline__ OT llr_out(float v, float qs);
 template <> __device__ __forceinline__ float llr_out<float>(float v, float) { return v; }
@@ -150,4 +207,5 @@ struct ldpc_modulation {
     double es = 0.0;
     int b = 0;            // a product object: bits per axis, m = 2 b
     ldpc::AxisTab ax{};
+    int rule = 0;         // LDPC_DEMAP_MAXLOG, or LDPC_DEMAP_LOGMAP (ldpc_modulation_with_rule): the demappers' LLR rule
 };

@@ -8,6 +8,7 @@
 // elements for each bit index j, so the stores coalesce per j; a random table scatters them.  The lanes from n_sym on take the hole list
 // (the punctured positions, sorted), m holes a lane, and store zeros.
 // ONE ITEM A LANE, no grid-stride loop, for the reason demap_product.hip gives.
+// The LLR rule (demap.h DEMAP_MAXLOG / DEMAP_LOGMAP) is a template argument of the two demapper kernels.
 #include "demap_product.h"
 #include "interleaver.h"
 #include <algorithm>
@@ -17,7 +18,7 @@ namespace ldpc {
 // lanes per frame: the symbols, then ceil(n_holes / K) lanes of K holes each
 static int il_lanes(int items, int n_holes, int K) { return items + (n_holes + K - 1) / K; }
 
-template <int M, typename OT>
+template <int M, typename OT, int RULE>
 __global__ __launch_bounds__(256) void demap_il_kernel(ModTab tab, IlTab il, const float *__restrict__ sym, OT *__restrict__ llr, int n_sym, int lanes, size_t total,
                                                        float inv, float qs) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -29,7 +30,7 @@ __global__ __launch_bounds__(256) void demap_il_kernel(ModTab tab, IlTab il, con
             const float2 y = *reinterpret_cast<const float2 *>(sym + 2 * (f * (size_t)n_sym + s));
             float v[M];
             int32_t p[M];
-            demap_llrs<M>(tab, y.x, y.y, inv, v);
+            demap_llrs_by<M, RULE>(tab, y.x, y.y, inv, v);
             il_positions<M>(il.pos + (size_t)M * s, p);
             il_store<M, OT>(row, p, il.n_tx - M * s, v, qs);
         } else {
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(256) void demap_il_kernel(ModTab tab, IlTab il, con
     }
 }
 
-template <int B, typename OT>
+template <int B, typename OT, int RULE>
 __global__ __launch_bounds__(256) void demap_il_product_kernel(AxisTab tab, IlTab il, const float *__restrict__ sym, OT *__restrict__ llr, int n_sym, int lanes,
                                                                size_t total, float inv, float qs) {
     constexpr int M = 2 * B;
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void demap_il_product_kernel(AxisTab tab, IlTa
 #pragma unroll 1
             for (int a = 0; a < 2; a++) {
                 float r[B];
-                axis_llrs<B>(tab.lev[a], a ? y.y : y.x, inv, r);
+                axis_llrs_by<B, RULE>(tab.lev[a], a ? y.y : y.x, inv, r);
 #pragma unroll
                 for (int j = 0; j < B; j++) {
                     if (a) v[B + j] = r[j]; else v[j] = r[j];
@@ -70,38 +71,38 @@ __global__ __launch_bounds__(256) void demap_il_product_kernel(AxisTab tab, IlTa
     }
 }
 
-template <int M, typename OT>
+template <int M, typename OT, int RULE>
 static int demap_il_as(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, float qs) {
     const int n_sym = (il.n_tx + M - 1) / M, lanes = il_lanes(n_sym, il.n_holes, M);
     const size_t total = (size_t)batch * lanes;
     if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((demap_il_kernel<M, OT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tab, il, d_sym, (OT *)d_llr, n_sym, lanes, total, inv, qs);
+    hipLaunchKernelGGL((demap_il_kernel<M, OT, RULE>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tab, il, d_sym, (OT *)d_llr, n_sym, lanes, total, inv, qs);
     return LDPC_OK;
 }
 
-template <int B, typename OT>
+template <int B, typename OT, int RULE>
 static int demap_il_product_as(hipStream_t st, const AxisTab &tab, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, float qs) {
     constexpr int M = 2 * B;
     const int n_sym = (il.n_tx + M - 1) / M, lanes = il_lanes(n_sym, il.n_holes, M);
     const size_t total = (size_t)batch * lanes;
     if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((demap_il_product_kernel<B, OT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tab, il, d_sym, (OT *)d_llr, n_sym, lanes, total, inv,
+    hipLaunchKernelGGL((demap_il_product_kernel<B, OT, RULE>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tab, il, d_sym, (OT *)d_llr, n_sym, lanes, total, inv,
                        qs);
     return LDPC_OK;
 }
 
-template <int M>
+template <int M, int RULE>
 static int demap_il_m(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) return demap_il_as<M, int8_t>(st, tab, il, batch, d_sym, inv, d_llr, qs);
-    if (fmt == MOD_LLR_F16) return demap_il_as<M, __half>(st, tab, il, batch, d_sym, inv, d_llr, qs);
-    return demap_il_as<M, float>(st, tab, il, batch, d_sym, inv, d_llr, qs);
+    if (fmt == MOD_LLR_I8) return demap_il_as<M, int8_t, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
+    if (fmt == MOD_LLR_F16) return demap_il_as<M, __half, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
+    return demap_il_as<M, float, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
 }
 
-template <int B>
+template <int B, int RULE>
 static int demap_il_product_b(hipStream_t st, const AxisTab &tab, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) return demap_il_product_as<B, int8_t>(st, tab, il, batch, d_sym, inv, d_llr, qs);
-    if (fmt == MOD_LLR_F16) return demap_il_product_as<B, __half>(st, tab, il, batch, d_sym, inv, d_llr, qs);
-    return demap_il_product_as<B, float>(st, tab, il, batch, d_sym, inv, d_llr, qs);
+    if (fmt == MOD_LLR_I8) return demap_il_product_as<B, int8_t, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
+    if (fmt == MOD_LLR_F16) return demap_il_product_as<B, __half, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
+    return demap_il_product_as<B, float, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
 }
 
 static int il_launched(const char *what, int rc) {
@@ -111,32 +112,44 @@ static int il_launched(const char *what, int rc) {
     return LDPC_OK;
 }
 
-int demap_il_launch(hipStream_t st, const ModTab &tab, int m, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
+template <int RULE>
+static int demap_il_launch_r(hipStream_t st, const ModTab &tab, int m, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
     int rc;
     switch (m) {
-        case 1: rc = demap_il_m<1>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 2: rc = demap_il_m<2>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 3: rc = demap_il_m<3>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 4: rc = demap_il_m<4>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 5: rc = demap_il_m<5>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 6: rc = demap_il_m<6>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 1: rc = demap_il_m<1, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 2: rc = demap_il_m<2, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 3: rc = demap_il_m<3, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 4: rc = demap_il_m<4, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 5: rc = demap_il_m<5, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 6: rc = demap_il_m<6, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
         default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: %d bits per symbol", m);
     }
     return il_launched("ldpc_demap_dev_il", rc);
 }
 
-int demap_il_product_launch(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
+template <int RULE>
+static int demap_il_product_launch_r(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
     int rc;
     switch (b) {
-        case 1: rc = demap_il_product_b<1>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 2: rc = demap_il_product_b<2>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 3: rc = demap_il_product_b<3>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 4: rc = demap_il_product_b<4>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 5: rc = demap_il_product_b<5>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 6: rc = demap_il_product_b<6>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 1: rc = demap_il_product_b<1, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 2: rc = demap_il_product_b<2, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 3: rc = demap_il_product_b<3, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 4: rc = demap_il_product_b<4, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 5: rc = demap_il_product_b<5, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
+        case 6: rc = demap_il_product_b<6, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
         default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: %d bits per axis", b);
     }
     return il_launched("ldpc_demap_dev_il", rc);
+}
+
+int demap_il_launch(hipStream_t st, const ModTab &tab, int m, int rule, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
+    if (rule == DEMAP_LOGMAP) return demap_il_launch_r<DEMAP_LOGMAP>(st, tab, m, il, batch, d_sym, inv, d_llr, fmt, qscale);
+    return demap_il_launch_r<DEMAP_MAXLOG>(st, tab, m, il, batch, d_sym, inv, d_llr, fmt, qscale);
+}
+
+int demap_il_product_launch(hipStream_t st, const AxisTab &tab, int b, int rule, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
+    if (rule == DEMAP_LOGMAP) return demap_il_product_launch_r<DEMAP_LOGMAP>(st, tab, b, il, batch, d_sym, inv, d_llr, fmt, qscale);
+    return demap_il_product_launch_r<DEMAP_MAXLOG>(st, tab, b, il, batch, d_sym, inv, d_llr, fmt, qscale);
 }
 
 // ---- the table alone

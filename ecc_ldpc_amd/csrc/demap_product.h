@@ -80,6 +80,58 @@ __device__ __forceinline__ void axis_llrs(const float (&lev)[kAxisMaxLevels], fl
     }
 }
 
+// log-MAP LLRs of one coordinate (include/ldpc_hip.h, "The LLR rule"): the max-log value of axis_llrs, bit for bit, plus c1 - c0,
+// c_v = log(sum over the axis labels l whose bit j is v of exp(-(e_l - m_v) inv)).  Exact for the product constellation, not an
+// approximation: the other axis's factor is common to both subsets and cancels.  Two passes, as demap_llrs_logmap: axis_llrs's prefix
+// tree with the minima kept, then the B 2^B exponentials over distances computed again from the uniform levels (2 operations a level)
+// -- the tree has consumed the first ones.  The sums run in label order
+template <int B>
+__device__ __forceinline__ void axis_llrs_logmap(const float (&lev)[kAxisMaxLevels], float y, float inv, float (&llr)[B]) {
+    float t[1 << B], m0[B], m1[B], s0[B], s1[B];
+#pragma unroll
+    for (int l = 0; l < (1 << B); l++) {
+        const float dx = y - lev[l];
+        t[l] = dx * dx;
+    }
+#pragma unroll
+    for (int k = B; k >= 1; k--) {                        // t holds T_k: 2^k entries
+        float a0 = t[0], a1 = t[1];
+#pragma unroll
+        for (int p = 1; p < (1 << (k - 1)); p++) {
+            a0 = __builtin_fminf(a0, t[2 * p]);
+            a1 = __builtin_fminf(a1, t[2 * p + 1]);
+        }
+        m0[k - 1] = a0; m1[k - 1] = a1;
+#pragma unroll
+        for (int p = 0; p < (1 << (k - 1)); p++) t[p] = __builtin_fminf(t[2 * p], t[2 * p + 1]);
+    }
+    if constexpr (B == 1) {                               // one level a subset: both sums are exp(0)
+        llr[0] = (m0[0] - m1[0]) * inv;
+        return;
+    }
+#pragma unroll
+    for (int l = 0; l < (1 << B); l++) {
+        const float dx = y - lev[l];
+        const float d = dx * dx;
+#pragma unroll
+        for (int j = 0; j < B; j++) {
+            const int bit = (l >> (B - 1 - j)) & 1;
+            const float e = __expf((bit ? m1[j] - d : m0[j] - d) * inv);
+            if (bit) s1[j] = (l == (1 << (B - 1 - j))) ? e : s1[j] + e;
+            else s0[j] = (l == 0) ? e : s0[j] + e;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < B; j++) llr[j] = logmap_llr((m0[j] - m1[j]) * inv, s0[j], s1[j]);
+}
+
+// the LLRs of one coordinate by the rule of the modulation object, as demap_llrs_by
+template <int B, int RULE>
+__device__ __forceinline__ void axis_llrs_by(const float (&lev)[kAxisMaxLevels], float y, float inv, float (&llr)[B]) {
+    if constexpr (RULE == DEMAP_LOGMAP) axis_llrs_logmap<B>(lev, y, inv, llr);
+    else axis_llrs<B>(lev, y, inv, llr);
+}
+
 // store_slot's rule for any even M: a slot's M sizeof(OT) bytes go out in the largest 16 / 8 / 4-byte pieces that divide them
 // (0: no such piece -- int8 with M = 2, 6, 10)
 template <int M, typename OT>

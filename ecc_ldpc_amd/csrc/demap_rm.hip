@@ -20,6 +20,8 @@
 // Lanes of a wave may walk lists of different lengths; the wave runs the longest.  For a circular table consecutive c have consecutive
 // t, hence the same or neighbouring samples, and equal lengths up to one.
 // ONE ITEM A LANE, no grid-stride loop, as demap_il.hip.
+// THE LOG-MAP RULE (demap.h DEMAP_LOGMAP, a template argument of the two rules below): a second walk over the same distances adds the
+// exponentials of the bit's two subsets, 2^m (2^b) a bit; the value then enters the sum and the store exactly as a max-log one.
 #include "demap_product.h"
 #include "fading.h"
 #include "ratematch.h"
@@ -37,7 +39,7 @@ static __device__ __forceinline__ int rm_hidden_zero() {
 }
 
 // the LLR of transmitted bit t of frame f, a table object of M bits: bit j = t % M (the first one the MSB) of symbol s = t / M
-template <int M>
+template <int M, int RULE>
 struct RmTableRule {
     ModTab tab;
     const float *sym, *gain;   // gain may be null: inv_s = inv
@@ -59,12 +61,31 @@ struct RmTableRule {
             m0 = __builtin_fminf(m0, one ? kRmInf : d);
             m1 = __builtin_fminf(m1, one ? d : kRmInf);
         }
-        return (m0 - m1) * inv_s;
+        if constexpr (RULE == DEMAP_MAXLOG || M == 1) return (m0 - m1) * inv_s;
+        // log-MAP (demap.h demap_llrs_logmap, this bit alone): a second walk over the table, behind a hidden zero of its own, adds
+        // exp(-(d_p - m_v) inv_s) to the sum its label's bit selects; the other sum takes a +0, which changes no sum.  16 points at a
+        // time in a loop that is NOT unrolled, as RmProductRule: with the first walk's minima live, the 128 coordinates of m = 6 at
+        // once do not fit the scalar registers
+        constexpr int CH = (1 << M) < 16 ? (1 << M) : 16;
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll 1
+        for (int p0 = rm_hidden_zero(); p0 < (1 << M); p0 += CH) {
+#pragma unroll
+            for (int p = 0; p < CH; p++) {
+                const float dx = y.x - tab.pt[p0 + p][0], dy = y.y - tab.pt[p0 + p][1];
+                const float d = dx * dx + dy * dy;
+                const bool one = (mask & (uint32_t)(p0 + p)) != 0u;
+                const float e = __expf(((one ? m1 : m0) - d) * inv_s);
+                s0 += one ? 0.f : e;
+                s1 += one ? e : 0.f;
+            }
+        }
+        return logmap_llr((m0 - m1) * inv_s, s0, s1);
     }
 };
 
 // the same of a product object of B bits an axis: bits 0 .. B - 1 of a symbol are the I axis's, B .. 2 B - 1 the Q axis's
-template <int B>
+template <int B, int RULE>
 struct RmProductRule {
     AxisTab tab;
     const float *sym, *gain;
@@ -94,7 +115,22 @@ struct RmProductRule {
                 m1 = __builtin_fminf(m1, one ? d : kRmInf);
             }
         }
-        return (m0 - m1) * inv_s;
+        if constexpr (RULE == DEMAP_MAXLOG || B == 1) return (m0 - m1) * inv_s;
+        // log-MAP (demap_product.h axis_llrs_logmap, this bit alone): the same chunked walk again, as RmTableRule's second one
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll 1
+        for (int l0 = rm_hidden_zero(); l0 < (1 << B); l0 += CH) {
+#pragma unroll
+            for (int l = 0; l < CH; l++) {
+                const float dx = y - (q ? tab.lev[1][l0 + l] : tab.lev[0][l0 + l]);
+                const float d = dx * dx;
+                const bool one = (mask & (uint32_t)(l0 + l)) != 0u;
+                const float e = __expf(((one ? m1 : m0) - d) * inv_s);
+                s0 += one ? 0.f : e;
+                s1 += one ? e : 0.f;
+            }
+        }
+        return logmap_llr((m0 - m1) * inv_s, s0, s1);
     }
 };
 
@@ -160,44 +196,58 @@ static int rm_launch(const char *what, hipStream_t st, const RULE &rule, const R
     return LDPC_OK;
 }
 
-template <int M>
+template <int M, int RULE>
 static int demap_rm_m(hipStream_t st, const ModTab &tab, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt, float qs,
                       bool acc) {
-    const RmTableRule<M> rule{tab, d_sym, d_gain, (rm.E + M - 1) / M, inv};
+    const RmTableRule<M, RULE> rule{tab, d_sym, d_gain, (rm.E + M - 1) / M, inv};
     return rm_launch("ldpc_demap_dev_rm", st, rule, rm, batch, d_llr, fmt, qs, acc);
 }
 
-template <int B>
+template <int B, int RULE>
 static int demap_rm_b(hipStream_t st, const AxisTab &tab, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt, float qs,
                       bool acc) {
-    const RmProductRule<B> rule{tab, d_sym, d_gain, (rm.E + 2 * B - 1) / (2 * B), inv};
+    const RmProductRule<B, RULE> rule{tab, d_sym, d_gain, (rm.E + 2 * B - 1) / (2 * B), inv};
     return rm_launch("ldpc_demap_dev_rm", st, rule, rm, batch, d_llr, fmt, qs, acc);
 }
 
-int demap_rm_launch(hipStream_t st, const ModTab &tab, int m, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
-                    float qscale, bool accumulate) {
+template <int RULE>
+static int demap_rm_launch_r(hipStream_t st, const ModTab &tab, int m, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
+                             float qscale, bool accumulate) {
     switch (m) {
-        case 1: return demap_rm_m<1>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 2: return demap_rm_m<2>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 3: return demap_rm_m<3>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 4: return demap_rm_m<4>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 5: return demap_rm_m<5>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 6: return demap_rm_m<6>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 1: return demap_rm_m<1, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 2: return demap_rm_m<2, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 3: return demap_rm_m<3, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 4: return demap_rm_m<4, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 5: return demap_rm_m<5, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 6: return demap_rm_m<6, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
         default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: %d bits per symbol", m);
     }
 }
 
-int demap_rm_product_launch(hipStream_t st, const AxisTab &tab, int b, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr,
-                            int fmt, float qscale, bool accumulate) {
+template <int RULE>
+static int demap_rm_product_launch_r(hipStream_t st, const AxisTab &tab, int b, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr,
+                                     int fmt, float qscale, bool accumulate) {
     switch (b) {
-        case 1: return demap_rm_b<1>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 2: return demap_rm_b<2>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 3: return demap_rm_b<3>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 4: return demap_rm_b<4>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 5: return demap_rm_b<5>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 6: return demap_rm_b<6>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 1: return demap_rm_b<1, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 2: return demap_rm_b<2, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 3: return demap_rm_b<3, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 4: return demap_rm_b<4, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 5: return demap_rm_b<5, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+        case 6: return demap_rm_b<6, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
         default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: %d bits per axis", b);
     }
+}
+
+int demap_rm_launch(hipStream_t st, const ModTab &tab, int m, int rule, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
+                    float qscale, bool accumulate) {
+    if (rule == DEMAP_LOGMAP) return demap_rm_launch_r<DEMAP_LOGMAP>(st, tab, m, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+    return demap_rm_launch_r<DEMAP_MAXLOG>(st, tab, m, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+}
+
+int demap_rm_product_launch(hipStream_t st, const AxisTab &tab, int b, int rule, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr,
+                            int fmt, float qscale, bool accumulate) {
+    if (rule == DEMAP_LOGMAP) return demap_rm_product_launch_r<DEMAP_LOGMAP>(st, tab, b, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+    return demap_rm_product_launch_r<DEMAP_MAXLOG>(st, tab, b, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
 }
 
 int ratematch_llr_launch(hipStream_t st, const RmTab &rm, int batch, const float *d_llr_tx, void *d_llr, int fmt, float qscale, bool accumulate) {

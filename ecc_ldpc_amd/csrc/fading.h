@@ -18,9 +18,9 @@ struct FadeArg {
 
 // ldpc_demap_dev_il_csi: demap_il_launch / demap_il_product_launch (interleaver.h) with the LLRs of symbol s of frame f scaled by
 // inv_s = fl(inv d_gain[f][s])
-int demap_csi_launch(hipStream_t st, const ModTab &tab, int m, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
+int demap_csi_launch(hipStream_t st, const ModTab &tab, int m, int rule, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
                      float qscale);
-int demap_csi_product_launch(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
+int demap_csi_product_launch(hipStream_t st, const AxisTab &tab, int b, int rule, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
                              float qscale);
 // ldpc_sim_transmit_il_fading / ldpc_sim_generate_mod_il_fading: as mod_transmit_il_launch / mod_generate_il_launch and their product
 // forms; d_gain [batch][n_sym] may be null

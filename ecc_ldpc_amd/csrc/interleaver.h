@@ -23,8 +23,8 @@ struct IlTab {
 int interleaver_check(const char *what, int n_tx, int N, const int32_t *pos, std::vector<int32_t> &holes);
 
 // ldpc_demap_dev_il: d_llr [batch][N] <- the LLRs of d_sym [batch][n_sym][2] at their codeword positions, 0 at the holes
-int demap_il_launch(hipStream_t st, const ModTab &tab, int m, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
-int demap_il_product_launch(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
+int demap_il_launch(hipStream_t st, const ModTab &tab, int m, int rule, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
+int demap_il_product_launch(hipStream_t st, const AxisTab &tab, int b, int rule, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
 // the table alone.  Bits: rows of N (bytes) or ceil(N / 8) (packed) -> rows of n_tx or ceil(n_tx / 8); LLRs: [batch][n_tx] -> [batch][N]
 // elements of `elem` bytes (1, 2, 4)
 int interleave_bits_launch(hipStream_t st, const IlTab &il, int batch, const uint8_t *d_in, bool in_packed, uint8_t *d_out, bool out_packed);

@@ -96,6 +96,19 @@ ldpc_modulation *ldpc_modulation_create_builtin(int kind) {
     }
 }
 
+ldpc_modulation *ldpc_modulation_with_rule(const ldpc_modulation *mod, int rule) {
+    if (!mod || (rule != LDPC_DEMAP_MAXLOG && rule != LDPC_DEMAP_LOGMAP)) {
+        set_error(LDPC_EINVAL, "ldpc_modulation_with_rule: null modulation, or unknown rule %d (LDPC_DEMAP_MAXLOG = 0, LDPC_DEMAP_LOGMAP = 1)", rule);
+        return nullptr;
+    }
+    ldpc_modulation *copy = new (std::nothrow) ldpc_modulation(*mod);
+    if (!copy) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    copy->rule = rule;
+    return copy;
+}
+
+int ldpc_modulation_rule(const ldpc_modulation *mod) { return mod ? mod->rule : set_error(LDPC_EINVAL, "null modulation"); }
+
 void ldpc_modulation_destroy(ldpc_modulation *mod) { delete mod; }
 
 int ldpc_modulation_bits(const ldpc_modulation *mod) { return mod ? mod->m : set_error(LDPC_EINVAL, "null modulation"); }

@@ -34,9 +34,9 @@ static inline IlTab rm_as_il(const RmTab &rm) { return IlTab{rm.pos, nullptr, rm
 
 // ldpc_demap_dev_rm: d_llr [batch][N] <- (accumulate: +=) per position the left-to-right float32 sum of the LLRs of d_sym
 // [batch][ceil(E / m)][2] whose transmitted bits name it; d_gain [batch][n_sym] or null; inv = float32(1 / (2 sigma^2))
-int demap_rm_launch(hipStream_t st, const ModTab &tab, int m, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
+int demap_rm_launch(hipStream_t st, const ModTab &tab, int m, int rule, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
                     float qscale, bool accumulate);
-int demap_rm_product_launch(hipStream_t st, const AxisTab &tab, int b, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr,
+int demap_rm_product_launch(hipStream_t st, const AxisTab &tab, int b, int rule, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr,
                             int fmt, float qscale, bool accumulate);
 // ldpc_ratematch_llr_dev: the same with the LLR of transmitted bit t loaded from d_llr_tx [batch][E] float32
 int ratematch_llr_launch(hipStream_t st, const RmTab &rm, int batch, const float *d_llr_tx, void *d_llr, int fmt, float qscale, bool accumulate);

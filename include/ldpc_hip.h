@@ -548,11 +548,38 @@ int ldpc_modulation_axis_levels(const ldpc_modulation *mod, float *levels_i, flo
  *                 read for LDPC_LLR_I8 only; 0 = 4.0; negative or non-finite: LDPC_EINVAL.
  * A NaN sample gives NaN LLRs (int8: 0, an erasure).  Runs on the calling thread's device, enqueued on `stream`, not synchronised.
  * LDPC_EINVAL: a null pointer, batch <= 0, n_tx <= 0 or > N, an unknown format, such a noise_var or qscale, a misaligned buffer.
- * Exact log-MAP and fp16 samples are not provided; a bit interleaver between codeword order and transmitted order is
- * ldpc_demap_dev_il, below. */
+ * fp16 samples are not provided; the exact log-MAP rule is a property of the modulation object (THE LLR RULE, below); a bit interleaver
+ * between codeword order and transmitted order is ldpc_demap_dev_il, below. */
 enum { LDPC_LLR_F32 = 0, LDPC_LLR_F16 = 1, LDPC_LLR_I8 = 2 };   /* the values llr_f16 takes in the packed entry points */
 int ldpc_demap_dev(const ldpc_modulation *mod, int batch, int n_tx, int N, const float *d_sym, double noise_var, void *d_llr, int llr_fmt,
                    float qscale, void *stream);
+/* THE LLR RULE travels with the modulation object: every demapper entry point (ldpc_demap_dev, _il, _il_csi, _rm) picks it up and none
+ * takes a new argument.  LDPC_DEMAP_MAXLOG is the rule stated above, and the rule of every object created any other way.
+ * LDPC_DEMAP_LOGMAP is the exact rule.  For one sample and label bit j let d_p be the SAME float32 squared distances the max-log rule
+ * computes, from the same operations in the same order, m0 / m1 their minima over the points whose bit j is 0 / 1, and inv_s the
+ * symbol's float32(1 / (2 noise_var)) (times its gain where one is given: ldpc_demap_dev_il_csi).  Then
+ *   LLR_j = fl(fl(m0 - m1) inv_s)  +  (c1 - c0),   c_v = log(sum over the points p whose bit j is v of exp(-(d_p - m_v) inv_s))
+ * The first term is the max-log value, unchanged; c_v lies in [0, log 2^(m-1)], and every sum holds an exp(0) = 1, so nothing
+ * underflows to log 0 at any SNR.  For a product object the rule is applied per axis (2^b levels, the bits of that axis, e_l in place
+ * of d_p): exact, not an approximation, because the other axis's factor is common to both subsets and cancels.  The rule is restated
+ * in tests/demap_logmap_spec.py; the kernels evaluate exp and log with the hardware's base-2 instructions and stay within 2^-14 of
+ * it, plus two float32 ulps of the result.  Where c1 - c0 is zero the max-log value stands as it is, the sign of a zero included, so
+ *   one point a subset (m = 1; b = 1 per axis): the max-log result bit for bit;
+ *   high SNR, every (d_p - m_v) inv_s but the smallest above 104: every other term is 0 in float32 -- the max-log result bit for bit;
+ *   inv_s = 0 (a gain of 0): both sums are the same integer -- the max-log result, a zero;
+ *   a NaN sample or gain: NaN for exactly the elements that are NaN under max-log; an infinite coordinate: NaN (inf - inf), as there.
+ * The output formats, the interleaver, the gains and the sums of ldpc_demap_dev_rm treat the value as they treat a max-log one.
+ * COST: m 2^m exponentials a sample for a table object, 2 b 2^b for a product object; ldpc_demap_dev_rm, which evaluates a bit a lane,
+ * 2^m (2^b) a bit.
+ * ldpc_modulation_with_rule: a NEW object (destroy it as any other) with the constellation of `mod`, table or product, demapped by
+ * `rule`; `mod` is untouched.  NULL and LDPC_EINVAL for a null `mod` or any other rule value.  An LDPC_DEMAP_MAXLOG copy is selected and
+ * computed exactly as the object it came from.  The transmit-only calls (ldpc_sim_transmit*) ignore the rule.  The fused map + noise +
+ * demap calls (ldpc_sim_generate_mod, _il, _il_fading) return LDPC_EUNSUPPORTED for an LDPC_DEMAP_LOGMAP object, the message naming the
+ * rule: fusing them doubles the instance count of five more kernels and is left for later; the two-step route (ldpc_sim_transmit*,
+ * then a demapper) gives the same LLRs and serves every sweep in the meantime. */
+typedef enum { LDPC_DEMAP_MAXLOG = 0, LDPC_DEMAP_LOGMAP = 1 } ldpc_demap_rule;
+ldpc_modulation *ldpc_modulation_with_rule(const ldpc_modulation *mod, int rule);
+int ldpc_modulation_rule(const ldpc_modulation *mod);   /* LDPC_DEMAP_MAXLOG for every object created any other way */
 /* The frame source's modulated path.  sigma^2 per real dimension = Es / (2 R m 10^(dB/10)), R = k / n_tx, in double (for
  * LDPC_MOD_BPSK: the formula of ldpc_sim_generate). */
 double ldpc_sim_noise_var(const ldpc_sim *sim, const ldpc_modulation *mod, double ebn0_db);
@@ -572,7 +599,9 @@ int ldpc_sim_transmit(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, 
  * d_llr [batch][N] (llr_fmt, qscale: as ldpc_demap_dev) are bit for bit those of the two calls.  Unlike ldpc_sim_transmit it needs
  * sigma^2 > 0 with 1 / (2 sigma^2) inside a float32 (Eb/N0 below about 380 dB): LDPC_EINVAL otherwise.
  * NOTE on LDPC_MOD_BPSK: this path computes ((y + 1)^2 - (y - 1)^2) / (2 sigma^2), which is not bitwise ldpc_sim_generate's
- * (2 / sigma^2) (x + sigma z), and it draws its noise from stream 2.  It is not a replacement for ldpc_sim_generate. */
+ * (2 / sigma^2) (x + sigma z), and it draws its noise from stream 2.  It is not a replacement for ldpc_sim_generate.
+ * Max-log only: LDPC_EUNSUPPORTED for an LDPC_DEMAP_LOGMAP object (THE LLR RULE, above), as ldpc_sim_generate_mod_il and
+ * ldpc_sim_generate_mod_il_fading; use ldpc_sim_transmit* and a demapper. */
 int ldpc_sim_generate_mod(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db,
                           const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt, float qscale, uint8_t *d_msg, void *stream);
 /* ---- bit interleaver: a position table between codeword order and transmitted order, fused into the mapper and the demapper.
