@@ -24,6 +24,8 @@ MOD_BPSK, MOD_QPSK, MOD_8PSK, MOD_16QAM = 1, 2, 3, 4
 MOD_64QAM, MOD_256QAM, MOD_1024QAM, MOD_4096QAM = 6, 8, 10, 12   # product constellations: the kind number is m
 DEMAP_MAXLOG, DEMAP_LOGMAP = 0, 1   # ldpc_demap_rule
 LLR_F32, LLR_F16, LLR_I8 = 0, 1, 2   # LDPC_LLR_*: the output formats of the demapper
+SOFT_POSTERIOR, SOFT_EXTRINSIC = 0, 1   # LDPC_SOFT_*: the kinds of ldpc_decode_batch_dev_soft
+_SOFT_KINDS = {"posterior": SOFT_POSTERIOR, "extrinsic": SOFT_EXTRINSIC}
 
 
 class CtxConfig(C.Structure):   # ldpc_ctx_config
@@ -36,7 +38,7 @@ class FadingStruct(C.Structure):   # ldpc_fading
 
 # every symbol include/ldpc_hip.h declares (tests/test_abi.py checks the library exports them all)
 ABI_SYMBOLS = [
-    "ldpc_init", "ldpc_shutdown", "ldpc_current_device", "ldpc_ctx_create_on", "ldpc_sim_create_on", "ldpc_ctx_create_cfg", "ldpc_ctx_schedule", "ldpc_ctx_code", "ldpc_ctx_max_batch", "ldpc_ctx_device",
+    "ldpc_init", "ldpc_decode_batch_dev_soft", "ldpc_demap_dev_il_apriori", "ldpc_shutdown", "ldpc_current_device", "ldpc_ctx_create_on", "ldpc_sim_create_on", "ldpc_ctx_create_cfg", "ldpc_ctx_schedule", "ldpc_ctx_code", "ldpc_ctx_max_batch", "ldpc_ctx_device",
     "ldpc_batcher_create", "ldpc_batcher_destroy", "ldpc_batcher_decode_one", "ldpc_batcher_stats",
     "ldpc_ecc_create_replicas", "ldpc_ecc_replicas", "ldpc_ecc_ctx_at", "ldpc_ecc_sim_at", "ldpc_ecc_decode_on", "ldpc_ecc_set_coalescing", "ldpc_ecc_coalescing_stats", "ldpc_code_set_layers", "ldpc_code_layers", "ldpc_qc_layer_order", "ldpc_csr_layer_order", "ldpc_last_error", "ldpc_last_error_code", "ldpc_abi_version", "ldpc_device_count",
     "ldpc_code_create_qc", "ldpc_code_create_csr", "ldpc_code_destroy", "ldpc_code_dims", "ldpc_code_csr",
@@ -201,6 +203,7 @@ def lib():
     L.ldpc_decode_batch_dev_f16.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.ldpc_decode_batch_i8.argtypes = [vp, C.c_int, C.c_int, vp, u8p, i32p, u8p]
     L.ldpc_decode_batch_dev_i8.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.ldpc_decode_batch_dev_soft.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp]
     L.ldpc_ctx_llr_qscale.restype = C.c_float
     L.ldpc_ctx_llr_qscale.argtypes = [vp]
     L.ldpc_ctx_cn_scale.restype = C.c_float
@@ -285,6 +288,7 @@ def lib():
     L.ldpc_interleave_bits_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]
     L.ldpc_deinterleave_llr_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
     L.ldpc_demap_dev_il_csi.argtypes = [vp, vp, C.c_int, vp, vp, C.c_double, vp, C.c_int, C.c_float, vp]
+    L.ldpc_demap_dev_il_apriori.argtypes = [vp, vp, C.c_int, vp, vp, C.c_double, vp, vp, C.c_int, C.c_float, vp]
     L.ldpc_sim_transmit_il_fading.argtypes = [vp, vp, vp, C.POINTER(FadingStruct), C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp, vp]
     L.ldpc_sim_generate_mod_il_fading.argtypes = [vp, vp, vp, C.POINTER(FadingStruct), C.c_uint64, C.c_uint64, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, C.c_float, vp, vp, vp]
     L.ldpc_ratematch_create_on.restype = vp
@@ -665,6 +669,35 @@ class Decoder:
         fn = lib().ldpc_decode_batch_dev_i8 if llr_i8 else lib().ldpc_decode_batch_dev_f16 if llr_f16 else lib().ldpc_decode_batch_dev
         check(fn(self._h, int(max_iters), int(batch), d_llr_ptr, d_bits_ptr, d_iters_ptr, d_conv_ptr, stream))
 
+    def decode_batch_dev_soft(self, d_llr_ptr, d_bits_ptr, d_soft_ptr, batch, max_iters, kind="posterior", soft_fmt="f32", soft_qscale=0.0, d_iters_ptr=None,
+                              d_conv_ptr=None, stream=None, llr_fmt="f32"):
+        """ldpc_decode_batch_dev_soft: device pointers; d_llr [batch][N] of llr_fmt "f32" / "f16" / "i8"; d_soft [batch][N] of soft_fmt;
+        kind "posterior" (lam as it stands when the frame stops) or "extrinsic" (that less the channel LLR as the cell took it in).
+        Contexts of the on-chip layered min-sum kernel for any H only"""
+        k = _SOFT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        check(lib().ldpc_decode_batch_dev_soft(self._h, int(max_iters), int(batch), d_llr_ptr, _llr_fmt(llr_fmt), d_bits_ptr, d_iters_ptr, d_conv_ptr, d_soft_ptr,
+                                               _llr_fmt(soft_fmt), float(soft_qscale), k, stream))
+
+    def decode_batch_soft(self, llr, max_iters, kind="posterior", soft_fmt="f32", soft_qscale=0.0):
+        """llr [F][N] float32, float16 or (an "i8" decoder) int8, host -> bits [F][N], iters [F], converged [F], soft [F][N] of soft_fmt
+        (numpy float32 / float16 / int8).  The arrays travel through torch tensors on the context's device"""
+        import torch
+        llr = np.ascontiguousarray(llr)
+        fmt = {np.dtype(np.float32): "f32", np.dtype(np.float16): "f16", np.dtype(np.int8): "i8"}[llr.dtype]
+        F = llr.shape[0]
+        assert llr.shape == (F, self.code.N)
+        dev = torch.device("cuda", lib().ldpc_ctx_device(self._h))
+        d_llr = torch.from_numpy(llr).to(dev)
+        d_bits = torch.zeros((F, self.code.N), dtype=torch.uint8, device=dev)
+        d_iters = torch.zeros(F, dtype=torch.int32, device=dev)
+        d_conv = torch.zeros(F, dtype=torch.uint8, device=dev)
+        d_soft = torch.zeros((F, self.code.N), dtype={"f32": torch.float32, "f16": torch.float16, "i8": torch.int8}[soft_fmt], device=dev)
+        torch.cuda.synchronize(dev)
+        self.decode_batch_dev_soft(d_llr.data_ptr(), d_bits.data_ptr(), d_soft.data_ptr(), F, max_iters, kind, soft_fmt, soft_qscale, d_iters.data_ptr(),
+                                   d_conv.data_ptr(), None, fmt)
+        self.synchronize()
+        return d_bits.cpu().numpy(), d_iters.cpu().numpy(), d_conv.cpu().numpy(), d_soft.cpu().numpy()
+
     def synchronize(self):
         check(lib().ldpc_ctx_synchronize(self._h))
 
@@ -1011,6 +1044,14 @@ def demap_il_csi(mod: Modulation, il: Interleaver, batch, d_sym_ptr, d_gain_ptr,
     """ldpc_demap_dev_il_csi: demap_il() with the power gain of every symbol, d_gain [batch][n_sym] float32: the noise variance of symbol
     s is noise_var / gain, its LLRs are scaled by float32(1 / (2 noise_var)) * gain"""
     check(lib().ldpc_demap_dev_il_csi(_h(mod), _h(il), int(batch), d_sym_ptr, d_gain_ptr, float(noise_var), d_llr_ptr, _llr_fmt(llr_fmt), float(qscale), stream))
+
+
+def demap_il_apriori(mod: Modulation, il: Interleaver, batch, d_sym_ptr, d_gain_ptr, noise_var, d_apriori_ptr, d_llr_ptr, llr_fmt="f32", qscale=0.0, stream=None):
+    """ldpc_demap_dev_il_apriori: demap_il_csi() with bit knowledge, d_apriori [batch][N] float32 in codeword order (LLR > 0 <=> bit 1; the
+    extrinsic output of Decoder.decode_batch_dev_soft, or zeros).  d_gain_ptr may be None (gains of 1).  Table objects only; the LLRs
+    written are extrinsic: every bit's own a-priori value is taken out again"""
+    check(lib().ldpc_demap_dev_il_apriori(_h(mod), _h(il), int(batch), d_sym_ptr, d_gain_ptr, float(noise_var), d_apriori_ptr, d_llr_ptr, _llr_fmt(llr_fmt), float(qscale),
+                                          stream))
 
 
 class Fading:

@@ -861,6 +861,30 @@ int ldpc_decode_batch_dev_i8(ldpc_ctx *ctx, int max_iters, int batch, const int8
     return decode_dev_checked(ctx, max_iters, batch, d_llr, ldpc::LLR_I8, d_bits, d_iters, d_converged, stream);
 }
 
+int ldpc_decode_batch_dev_soft(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                               uint8_t *d_converged, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind, void *stream) {
+    int rc = check_call(ctx, max_iters, batch);
+    if (rc != LDPC_OK) return rc;
+    if (llr_fmt != LDPC_LLR_F32 && llr_fmt != LDPC_LLR_F16 && llr_fmt != LDPC_LLR_I8) return set_error(LDPC_EINVAL, "llr_fmt %d is not one of LDPC_LLR_F32, LDPC_LLR_F16, LDPC_LLR_I8", llr_fmt);
+    if (soft_fmt != LDPC_LLR_F32 && soft_fmt != LDPC_LLR_F16 && soft_fmt != LDPC_LLR_I8) return set_error(LDPC_EINVAL, "soft_fmt %d is not one of LDPC_LLR_F32, LDPC_LLR_F16, LDPC_LLR_I8", soft_fmt);
+    if (soft_kind != LDPC_SOFT_POSTERIOR && soft_kind != LDPC_SOFT_EXTRINSIC) return set_error(LDPC_EINVAL, "soft_kind %d is neither LDPC_SOFT_POSTERIOR nor LDPC_SOFT_EXTRINSIC", soft_kind);
+    const int fmt = packed_format(llr_fmt);
+    if ((rc = check_format(ctx, fmt)) != LDPC_OK) return rc;
+    if (!(soft_qscale >= 0.f) || !std::isfinite(soft_qscale)) return set_error(LDPC_EINVAL, "soft_qscale %g is negative or not finite (0 = 4.0)", (double)soft_qscale);
+    // an int8 cell's soft output in int8 is the cell's own integer: no other scale can be asked for
+    if (ctx->dtype == LDPC_I8 && soft_fmt == LDPC_LLR_I8 && soft_qscale != 0.f && soft_qscale != ldpc_ctx_llr_qscale(ctx))
+        return set_error(LDPC_EINVAL, "soft_qscale %g: the int8 soft output of an LDPC_I8 context has the context's scale %g (pass that, or 0)", (double)soft_qscale,
+                         (double)ldpc_ctx_llr_qscale(ctx));
+    if (batch == 0) return LDPC_OK;
+    if (!d_llr || !d_bits) return set_error(LDPC_EINVAL, "null d_llr/d_bits");
+    if (!d_soft) return set_error(LDPC_EINVAL, "null d_soft");
+    const size_t es = soft_fmt == LDPC_LLR_F32 ? 4 : soft_fmt == LDPC_LLR_F16 ? 2 : 1;
+    if ((uintptr_t)d_soft % es) return set_error(LDPC_EINVAL, "d_soft is not aligned to its %zu-byte elements", es);
+    if ((uintptr_t)d_llr % llr_bytes(fmt)) return set_error(LDPC_EINVAL, "d_llr is not aligned to its %zu-byte elements", llr_bytes(fmt));
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    return ctx->backend->decode_soft(st, max_iters, batch, d_llr, fmt, d_bits, d_iters, d_converged, d_soft, soft_fmt, soft_qscale == 0.f ? 4.0f : soft_qscale, soft_kind);
+}
+
 int ldpc_decode_batch_dev_packed(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int llr_f16, uint8_t *d_packed, int32_t *d_iters,
                                  uint8_t *d_converged, void *stream) {
     int rc = check_call(ctx, max_iters, batch);
@@ -1604,6 +1628,30 @@ int ldpc_demap_dev_il_csi(const ldpc_modulation *mod, const ldpc_interleaver *il
     if ((rc = il_device("ldpc_demap_dev_il_csi", il)) != LDPC_OK) return rc;
     if (mod->b) return ldpc::demap_csi_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
     return ldpc::demap_csi_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+}
+
+int ldpc_demap_dev_il_apriori(const ldpc_modulation *mod, const ldpc_interleaver *il, int batch, const float *d_sym, const float *d_gain, double noise_var,
+                              const float *d_apriori, void *d_llr, int llr_fmt, float qscale, void *stream) {
+    if (!mod || !il || !d_sym || !d_llr) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: null argument");
+    if (!d_apriori) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: null d_apriori (without bit knowledge: ldpc_demap_dev_il_csi)");
+    if (mod->b)
+        return set_error(LDPC_EUNSUPPORTED, "ldpc_demap_dev_il_apriori: a product constellation (%d bits per axis) has no demapper with a-priori input: its Gray-like "
+                         "per-axis labels gain little from iterating with the decoder; table objects (ldpc_modulation_create, m = 1..6) have one", mod->b);
+    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: bad dimensions (batch=%d)", batch);
+    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: noise_var must be finite and > 0");
+    int rc = check_llr_out("ldpc_demap_dev_il_apriori", llr_fmt, qscale);
+    if (rc != LDPC_OK) return rc;
+    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0 || (uintptr_t)d_apriori % 4 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0)
+        return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: samples must be 8-byte aligned, gains and a-priori values 4-byte aligned and LLRs aligned to their element");
+    {   // every lane reads the a-priori values of its symbol and writes its LLRs: the two buffers must not share a byte
+        const uintptr_t a0 = (uintptr_t)d_apriori, a1 = a0 + (size_t)batch * il->N * sizeof(float);
+        const uintptr_t l0 = (uintptr_t)d_llr, l1 = l0 + (size_t)batch * il->N * llr_elem(llr_fmt);
+        if (a0 < l1 && l0 < a1) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: d_apriori overlaps d_llr (no in-place operation)");
+    }
+    const float inv = (float)(1.0 / (2.0 * noise_var));
+    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
+    if ((rc = il_device("ldpc_demap_dev_il_apriori", il)) != LDPC_OK) return rc;
+    return ldpc::demap_apriori_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, il->tab, batch, d_sym, d_gain, d_apriori, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
 }
 
 int ldpc_sim_transmit_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, const ldpc_fading *fad, uint64_t seed, uint64_t first_frame, int batch,

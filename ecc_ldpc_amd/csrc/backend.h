@@ -21,6 +21,13 @@ struct Backend {
     // device outputs, all but d_bits may be null
     virtual int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                        uint8_t *d_conv, double *d_final, double *d_trace) = 0;
+    // decode() with the soft output of ldpc_decode_batch_dev_soft (validated by api.cc): d_soft [batch][N] of element type soft_fmt
+    // (LDPC_LLR_*), soft_kind LDPC_SOFT_POSTERIOR / _EXTRINSIC.  Served by csrc/layered_csr.hip alone; every other family answers
+    // LDPC_EUNSUPPORTED with its own name
+    virtual int decode_soft(hipStream_t, int, int, const void *, int, uint8_t *, int32_t *, uint8_t *, void *, int, float, int) {
+        return set_error(LDPC_EUNSUPPORTED, "no soft output from %s: ldpc_decode_batch_dev_soft is served by the on-chip layered min-sum kernel for any H "
+                         "(ldpc::layered_csr_kernel: min-sum, LDPC_SCHED_LAYERED, dtype LDPC_F16, LDPC_F32 or LDPC_I8, with or without a check-node rule)", kernel_name());
+    }
     // one teacher-forced iteration from given (lam, ne) in f64 (ldpc_debug_step), or LDPC_EUNSUPPORTED with the reason
     virtual int step(hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne, double *d_ne_out,
                      double *d_lam_out, uint8_t *d_syn) = 0;

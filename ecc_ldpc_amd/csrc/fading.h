@@ -22,6 +22,10 @@ int demap_csi_launch(hipStream_t st, const ModTab &tab, int m, int rule, const I
                      float qscale);
 int demap_csi_product_launch(hipStream_t st, const AxisTab &tab, int b, int rule, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
                              float qscale);
+// ldpc_demap_dev_il_apriori (demap_apriori.hip): demap_csi_launch for a table object with d_apriori [batch][N] float32, the bit knowledge in
+// codeword order; d_gain may be null (a = 1)
+int demap_apriori_launch(hipStream_t st, const ModTab &tab, int m, int rule, const IlTab &il, int batch, const float *d_sym, const float *d_gain, const float *d_apriori,
+                         float inv, void *d_llr, int fmt, float qscale);
 // ldpc_sim_transmit_il_fading / ldpc_sim_generate_mod_il_fading: as mod_transmit_il_launch / mod_generate_il_launch and their product
 // forms; d_gain [batch][n_sym] may be null
 int fading_transmit_launch(hipStream_t st, const ModTab &tab, int m, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed,

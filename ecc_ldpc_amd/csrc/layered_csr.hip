@@ -36,6 +36,12 @@
 //   int8 cells:  n = min(max(((a m + 8) >> 4) - b, 0), 511), a = clip(rint(16 alpha), 1, 16), b = rint(beta qscale): integers only.
 // Nothing per edge: a subtract and a select (int8: a max and a min) per minimum, two minima per row.  The nine layered_csr_kernel
 // plain instances are instruction for instruction what they were before the rule existed (profiles/r10_layered_rule_default_ab.txt).
+// THE SOFT OUTPUT (ldpc_decode_batch_dev_soft; specification tests/soft_output_spec.py, reproduced bit for bit).  In a layered schedule the
+// lam cells in LDS ARE the posterior, so the output is an epilogue of the frame: lam as it stands when the frame stops -- converged, out of
+// sweeps or vetoed alike --, or that less the channel LLR as the cell took it in, read from memory again; f32, fp16 or int8 out.  It lives in
+// instances of their own, layered_csr_soft_kernel<D, CELL>, which take one more argument.  The body of both kernels is text,
+// layered_csr_body.h, included twice: the eighteen layered_csr_kernel instances are compiled from what they were compiled from before and
+// are instruction for instruction and register for register what they were (profiles/r20_bicm_id.txt).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -44,6 +50,7 @@
 #include <numeric>
 #include <vector>
 
+#include "demap.h"
 #include "layered_qc.h"
 #include "ldpc_math.h"
 
@@ -81,6 +88,14 @@ struct CsrLayArgs {
     int batch, max_iters;
     int *work_counter;              // next frame to take = gridDim.x + atomicAdd(work_counter, 1)
     CsrRule rule;                   // (last: the Ruled instances alone read it; every other member sits where it sat without it)
+};
+
+// the soft output of layered_csr_soft_kernel (ldpc_decode_batch_dev_soft): an argument of its own, after the three every instance takes
+struct CsrSoftArgs {
+    void *out;                      // [batch][N] of element type fmt
+    int fmt;                        // MOD_LLR_F32 / _F16 / _I8 (= LDPC_LLR_*)
+    int kind;                       // LDPC_SOFT_POSTERIOR: lam as it stands; LDPC_SOFT_EXTRINSIC: lam - the channel LLR as the cell took it in
+    float qscale;                   // (float cells, fmt _I8) the scale of the output's quantiser
 };
 
 namespace {   // (the device helpers below are layered_lds.hip's, kept local to this file)
@@ -353,6 +368,34 @@ __device__ __forceinline__ void csr_row_at(const uint16_t *cp, int T, int wd, bo
     if constexpr (DCLASS >= 32) csr_row<LT, 27, false, FIRST, RULE>(cp, T, wd, lam0, in, out, odd, flip, rule);
 }
 
+// ---- the soft output's element: a float cell's value through the demappers' llr_out; an int8 cell's integer v as v / qscale (ONE
+// division), that float as fp16, or the integer clipped
+template <class F> __device__ __forceinline__ void with_soft_format(int fmt, F &&f) {
+    if (fmt == MOD_LLR_F16) f((__half *)nullptr);
+    else if (fmt == MOD_LLR_I8) f((int8_t *)nullptr);
+    else f((float *)nullptr);
+}
+template <typename OT> __device__ __forceinline__ OT soft_of_q(int v, float cq) {
+    if constexpr (std::is_same<OT, int8_t>::value) return (int8_t)min(max(v, -127), 127);
+    else return llr_out<OT>((float)v / cq, 0.f);
+}
+// eight consecutive elements: 16-byte stores (int8: one 8-byte store)
+template <typename OT> __device__ __forceinline__ void st_soft8(OT *p, const OT (&o)[8]) {
+    if constexpr (sizeof(OT) == 1) {
+        uint2 a;
+        __builtin_memcpy(&a, o, 8);
+        *reinterpret_cast<uint2 *>(p) = a;
+    } else {
+        uint4 a;
+        __builtin_memcpy(&a, o, 16);
+        *reinterpret_cast<uint4 *>(p) = a;
+        if constexpr (sizeof(OT) == 4) {
+            __builtin_memcpy(&a, o + 4, 16);
+            *reinterpret_cast<uint4 *>(p + 4) = a;
+        }
+    }
+}
+
 }  // namespace
 
 // block = T threads (a multiple of 64, at most csr_max_threads); grid = resident workgroups (persistent).  Rows above weight 20 keep
@@ -361,181 +404,16 @@ constexpr int csr_max_threads(int dclass) { return dclass > 20 ? 512 : 1024; }
 // CELL: the lam cell's type (the 3/4, A.rule is not read), or Ruled<that type> (the rule of A.rule)
 template <int DCLASS, typename CELL = _Float16>
 __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(CsrLayDev g, typename Cell<CELL>::Rec *rec_all, CsrLayArgs A) {
-    typedef typename CellOf<CELL>::type LT;
-    constexpr bool RULE = CellOf<CELL>::rule;
-    CsrRule rule{};
-    if constexpr (RULE) rule = A.rule;
-    typedef typename Cell<LT>::vec8 cell8;
-    typedef typename Cell<LT>::Rec Rec;               // the row record follows the lam cell: 12 bytes (fp16, f32), 8 bytes (int8)
-    constexpr bool kInt8 = std::is_same<LT, int8_t>::value;
-    constexpr bool kVeto = kVetoesNonFinite<float, LDPC_V_MINSUM> && sizeof(LT) == 4;    // (fp16 lam saturates by its own rule)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    LT *lam = reinterpret_cast<LT *>(smem);
-    // [0] next frame; [1..3] "sweep n moved" at 1 + n % 3 (cleared by thread 0 two sweeps before its use); [4] "the channel's hard
-    // decisions are not a codeword"; [5] (f32 lam) "some LLR of the frame that just stopped is not finite"
-    int *ctl = reinterpret_cast<int *>(smem + (((size_t)g.N * sizeof(LT) + 15) & ~(size_t)15));
-    const int T = g.T, tid = threadIdx.x;
-    const int W = T >> 6, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nslab = ((ctab_t)g.step_ptr)[g.nstep];
-    const uint32_t lam0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem;   // LDS byte address of lam
-    Rec *const rec = rec_all + (size_t)blockIdx.x * nslab * T + tid;        // this thread's record of slab s: rec[s T]
-    int frame = blockIdx.x;
-    while (frame < A.batch) {
-        const size_t fN = (size_t)frame * g.N;
-        // ---- lam <- channel LLRs, as stored: saturated, rounded to fp16 / the float (eight per lane and request when the frame is 16-byte aligned)
-        bool wide;
-        if constexpr (kInt8)    // (int8 LLRs: 8 cells are one 8-byte request)
-            wide = (g.N & 7) == 0 && A.llr_fmt != LLR_F64 && !A.final_lam && (((uintptr_t)A.bits + fN) & 7) == 0 &&
-                   (((uintptr_t)A.llr + fN * (A.llr_fmt == LLR_I8 ? 1 : A.llr_fmt == LLR_F16 ? 2 : 4)) & (A.llr_fmt == LLR_I8 ? 7 : 15)) == 0;
-        else
-            wide = (g.N & 7) == 0 && A.llr_fmt != LLR_F64 && !A.final_lam &&
-                          (((uintptr_t)A.llr + fN * (A.llr_fmt == LLR_F16 ? 2 : 4)) & 15) == 0 && (((uintptr_t)A.bits + fN) & 7) == 0;   // (uniform)
-        if constexpr (kInt8) {
-            // ---- lam <- the quantised channel LLRs (int8 LLRs as they are)
-            if (wide) {
-                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
-#pragma unroll 4
-                    for (int i = tid * 8; i < g.N; i += T * 8) *reinterpret_cast<uint2 *>(lam + i) = load_q8<decltype(fmt)::value>(A.llr, fN + i, A.qscale);
-                });
-            } else {
-                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
-#pragma unroll 8
-                    for (int i = tid; i < g.N; i += T) lam[i] = (int8_t)load_q<decltype(fmt)::value>(A.llr, fN + i, A.qscale);
-                });
-            }
-        } else if (wide) {
-            with_llr_format(A.llr_fmt, [&](auto fmt) {
-#pragma unroll 4
-                for (int i = tid * 8; i < g.N; i += T * 8) {
-                    cell8 h;
-                    load_llr8<LT, decltype(fmt)::value>(A.llr, fN + i, h);
-                    Cell<LT>::st8(lam + i, h);
-                }
-            });
-        } else {
-            with_llr_format(A.llr_fmt, [&](auto fmt) {
-#pragma unroll 8
-                for (int i = tid; i < g.N; i += T) lam[i] = Cell<LT>::llr(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
-            });
-        }
-        if (tid == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; ctl[4] = 0; if constexpr (kVeto) ctl[5] = 0; }
-        lds_barrier();
-        bool conv = false;
-        int n = 0;
-        {   // syndrome of the hard decisions before the first sweep (reads only: no barrier between steps)
-            bool odd = false;
-            for (int s = 0; s < nslab; s++) {
-                const int c0 = ((ctab_t)g.slab)[2 * s], wd = ((ctab_t)g.wdeg)[s * W + wave] & 0xFF;
-                const uint16_t *cp = g.cols + c0 + tid;
-                bool par = false;
-                for (int k = 0; k < wd; k++) {
-                    const uint32_t c = cp[(size_t)k * T];
-                    if (c != kNoEdge) par ^= *lds_cell<LT>(lam0 + (uint32_t)sizeof(LT) * c) > (LT)0;
-                }
-                odd |= par;
-            }
-            if (__builtin_amdgcn_ballot_w64(odd) != 0 && (tid & 63) == 0) ctl[4] = 1;
-            lds_barrier();
-            conv = ctl[4] == 0;
-        }
-        if (!conv) {
-            for (n = 1; n <= A.max_iters; n++) {
-                bool odd = false, flip = false;
-                if (tid == 0) ctl[1 + (n + 1) % 3] = 0;                 // the flag of the NEXT sweep (last read two sweeps ago)
-                for (int st = 0; st < g.nstep; st++) {
-                    const int s0 = ((ctab_t)g.step_ptr)[st], s1 = ((ctab_t)g.step_ptr)[st + 1];
-                    for (int s = s0; s < s1; s++) {
-                        const int c0 = ((ctab_t)g.slab)[2 * s], wv = ((ctab_t)g.wdeg)[s * W + wave];
-                        const uint16_t *cp = g.cols + c0 + tid;
-                        Rec out;
-                        if (n == 1) {
-                            const Rec none{};
-                            csr_row_at<LT, DCLASS, true, RULE>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, none, out, odd, flip, rule);
-                        } else {
-                            const Rec in = rec[(size_t)s * T];
-                            csr_row_at<LT, DCLASS, false, RULE>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, in, out, odd, flip, rule);
-                        }
-                        rec[(size_t)s * T] = out;
-                    }
-                    if (st == g.nstep - 1 && __builtin_amdgcn_ballot_w64(odd || flip) != 0 && (tid & 63) == 0) ctl[1 + n % 3] = 1;
-                    lds_barrier();
-                }
-                if (ctl[1 + n % 3] == 0) { conv = true; break; }
-            }
-            if (n > A.max_iters) n = A.max_iters;
-        }
-        if constexpr (kVeto) {
-            // LLRs that are not finite -- they left the float range, or the channel gave them: failed, not "converged" (ldpc_math.h),
-            // also for a frame whose channel decisions are a codeword before the first sweep.  Once per frame; `conv` comes from a
-            // control word every thread read after a barrier, so it is workgroup-uniform and every wave reaches the barrier below
-            if (conv) {
-                bool bad = false;
-                for (int i = tid; i < g.N; i += T) bad |= not_finite(lam[i]);
-                if (__builtin_amdgcn_ballot_w64(bad) != 0 && (tid & 63) == 0) ctl[5] = 1;
-                lds_barrier();
-                conv = ctl[5] == 0;
-            }
-        }
-        // ---- result: hard(lam) of a frame that stopped by the rule, the channel's decisions (as stored) otherwise (Orig.hs:69-70)
-        if constexpr (kInt8) {
-            // a frame out of sweeps quantises its channel LLRs again; no veto: the clip bounds the state
-            if (wide) {
-                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
-#pragma unroll 4
-                    for (int i = tid * 8; i < g.N; i += T * 8) {
-                        const uint2 w = conv ? *reinterpret_cast<const uint2 *>(lam + i) : load_q8<decltype(fmt)::value>(A.llr, fN + i, A.qscale);
-                        *reinterpret_cast<uint2 *>(A.bits + fN + i) = hard_q8(w);
-                    }
-                });
-            } else {
-                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
-#pragma unroll 4
-                    for (int i = tid; i < g.N; i += T) {
-                        const int v = conv ? (int)lam[i] : load_q<decltype(fmt)::value>(A.llr, fN + i, A.qscale);
-                        A.bits[fN + i] = v > 0 ? 1 : 0;
-                        if (A.final_lam) A.final_lam[fN + i] = (double)v / (double)A.qscale;
-                    }
-                });
-            }
-        } else if (wide) {
-            auto put = [&](int i, const cell8 &h) {
-                uint32_t lo = 0, hi = 0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) { lo |= (h[k] > (LT)0 ? 1u : 0u) << (8 * k); hi |= (h[k + 4] > (LT)0 ? 1u : 0u) << (8 * k); }
-                *reinterpret_cast<uint2 *>(A.bits + fN + i) = make_uint2(lo, hi);
-            };
-            if (conv) {
-#pragma unroll 4
-                for (int i = tid * 8; i < g.N; i += T * 8) put(i, Cell<LT>::ld8(lam + i));
-            } else {
-                with_llr_format(A.llr_fmt, [&](auto fmt) {
-#pragma unroll 4
-                    for (int i = tid * 8; i < g.N; i += T * 8) {
-                        cell8 h;
-                        load_llr8<LT, decltype(fmt)::value>(A.llr, fN + i, h);
-                        put(i, h);
-                    }
-                });
-            }
-        } else {
-            with_llr_format(A.llr_fmt, [&](auto fmt) {
-#pragma unroll 4
-                for (int i = tid; i < g.N; i += T) {
-                    const float v = conv ? (float)lam[i] : (float)Cell<LT>::llr(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
-                    A.bits[fN + i] = v > 0.f ? 1 : 0;
-                    if (A.final_lam) A.final_lam[fN + i] = (double)v;
-                }
-            });
-        }
-        if (tid == 0) {
-            if (A.iters) A.iters[frame] = conv ? n : A.max_iters;
-            if (A.conv) A.conv[frame] = conv ? 1 : 0;
-            ctl[0] = (int)gridDim.x + atomicAdd(A.work_counter, 1);
-        }
-        lds_barrier();   // also: every lam read of this frame is done before the next frame's LLRs are written over it
-        frame = ctl[0];
-        lds_barrier();   // (nobody still reads ctl[0] when thread 0 of a fast wave writes the next one)
-    }
+#define LAYERED_CSR_SOFT 0
+#include "layered_csr_body.h"
+#undef LAYERED_CSR_SOFT
+}
+// the same decode with the soft output S (ldpc_decode_batch_dev_soft): instances of their own beside the eighteen above
+template <int DCLASS, typename CELL = _Float16>
+__global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_soft_kernel(CsrLayDev g, typename Cell<CELL>::Rec *rec_all, CsrLayArgs A, CsrSoftArgs S) {
+#define LAYERED_CSR_SOFT 1
+#include "layered_csr_body.h"
+#undef LAYERED_CSR_SOFT
 }
 
 namespace {
@@ -557,6 +435,19 @@ template <typename LT> void launch(int dclass, bool rule, dim3 grid, dim3 block,
     else hipLaunchKernelGGL(kernel_for<LT>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a);
 }
 
+template <typename LT> using csr_soft_kernel_t = void (*)(CsrLayDev, typename Cell<LT>::Rec *, CsrLayArgs, CsrSoftArgs);
+template <typename LT> csr_soft_kernel_t<LT> soft_kernel_for(int dclass) {
+    return dclass == 8 ? layered_csr_soft_kernel<8, LT> : dclass == 20 ? layered_csr_soft_kernel<20, LT> : layered_csr_soft_kernel<32, LT>;
+}
+const void *pick_soft_kernel(int dclass, int dtype, bool rule) {
+    if (rule) return dtype == LDPC_F32 ? (const void *)soft_kernel_for<Ruled<float>>(dclass) : dtype == LDPC_I8 ? (const void *)soft_kernel_for<Ruled<int8_t>>(dclass) : (const void *)soft_kernel_for<Ruled<_Float16>>(dclass);
+    return dtype == LDPC_F32 ? (const void *)soft_kernel_for<float>(dclass) : dtype == LDPC_I8 ? (const void *)soft_kernel_for<int8_t>(dclass) : (const void *)soft_kernel_for<_Float16>(dclass);
+}
+template <typename LT> void launch_soft(int dclass, bool rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, void *rec, const CsrLayArgs &a, const CsrSoftArgs &so) {
+    if (rule) hipLaunchKernelGGL(soft_kernel_for<Ruled<LT>>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a, so);
+    else hipLaunchKernelGGL(soft_kernel_for<LT>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a, so);
+}
+
 // ------------------------------------------------------------------ host side
 struct LayeredCsrState : Backend {
     int max_batch = 0, dclass = 8, grid = 0, nslab = 0;
@@ -574,8 +465,12 @@ struct LayeredCsrState : Backend {
     ~LayeredCsrState() override {
         (void)hipFree(d_cols); (void)hipFree(d_slab); (void)hipFree(d_wdeg); (void)hipFree(d_step); (void)hipFree(d_counter); (void)hipFree(rec);
     }
+    char name_plain[sizeof(LaunchInfo::name)] = "", name_soft[sizeof(LaunchInfo::name)] = "";   // info.name is that of the last launch
+    int soft_grid = 0;          // resident workgroups of the soft instance (0: not asked yet)
     int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                uint8_t *d_conv, double *d_final, double *d_trace) override;
+    int decode_soft(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                    uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) override;
     int step(hipStream_t, int, const double *, const double *, const double *, double *, double *, uint8_t *) override {
         if (has_rule) return set_error(LDPC_EUNSUPPORTED, "no teacher-forced step with a check-node rule (cn_scale / cn_offset: the record kernels keep no per-edge messages)");
         return set_error(LDPC_EUNSUPPORTED, dtype == LDPC_I8 ? "no teacher-forced step with LDPC_I8 (fixed-point state; the record kernels keep no per-edge messages)"
@@ -701,6 +596,11 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
         s->g.cols = s->d_cols; s->g.slab = s->d_slab; s->g.wdeg = s->d_wdeg; s->g.step_ptr = s->d_step;
         if (s->has_rule) snprintf(s->info.name, sizeof(s->info.name), "ldpc::layered_csr_kernel<%d, ldpc::Ruled<%s>>", s->dclass, dtype == LDPC_I8 ? "signed char" : dtype == LDPC_F32 ? "float" : "_Float16");
         else snprintf(s->info.name, sizeof(s->info.name), dtype == LDPC_I8 ? "ldpc::layered_csr_kernel<%d, signed char>" : dtype == LDPC_F32 ? "ldpc::layered_csr_kernel<%d, float>" : "ldpc::layered_csr_kernel<%d>", s->dclass);
+        snprintf(s->name_plain, sizeof(s->name_plain), "%s", s->info.name);
+        {   // "ldpc::layered_csr_kernel<...>" -> "ldpc::layered_csr_soft_kernel<...>"
+            const char *lt = strchr(s->info.name, '<');
+            snprintf(s->name_soft, sizeof(s->name_soft), "ldpc::layered_csr_soft_kernel%s", lt ? lt : "");
+        }
         s->info.threads = T; s->info.frames_per_wg = 1;
         return s;
     } catch (...) { delete s; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
@@ -716,6 +616,7 @@ int LayeredCsrState::decode(hipStream_t st, int max_iters, int batch, const void
     hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(int), st);
     if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
     const dim3 grid(std::min(batch, this->grid)), block(g.T);
+    memcpy(info.name, name_plain, sizeof(info.name));
     if (timer) timer->begin(st);
     if (dtype == LDPC_I8) launch<int8_t>(dclass, has_rule, grid, block, lds, st, g, rec, a);
     else if (dtype == LDPC_F32) launch<float>(dclass, has_rule, grid, block, lds, st, g, rec, a);
@@ -723,6 +624,43 @@ int LayeredCsrState::decode(hipStream_t st, int max_iters, int batch, const void
     if (timer) timer->end(st);
     e = hipGetLastError();
     if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr launch: %s", hipGetErrorString(e));
+    return LDPC_OK;
+}
+
+// The soft instance of the context's kernel: same tables, records, counter and geometry.  It holds more registers than the plain one in
+// its epilogue only; its grid is bounded by the records the context owns (sized for the plain instance's resident workgroups) and by its
+// own residency, asked for once.
+int LayeredCsrState::decode_soft(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                                 uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) {
+    if (llr_fmt == LLR_I8 && dtype != LDPC_I8) return set_error(LDPC_EUNSUPPORTED, "int8 LLRs are taken by LDPC_I8 contexts only");
+    if (!soft_grid) {
+        const void *kern = pick_soft_kernel(dclass, dtype, has_rule);
+        int per_cu = 0, dev = 0;
+        hipDeviceProp_t prop;
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, g.T, lds);
+        if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr soft instance: %s", hipGetErrorString(e));
+        if (per_cu <= 0) return set_error(LDPC_EHIP, "layered_csr: no workgroup of %d threads and %zu B of LDS of the soft instance is resident", g.T, lds);
+        soft_grid = std::min(this->grid, per_cu * prop.multiProcessorCount);
+    }
+    CsrLayArgs a{};
+    a.llr = d_llr; a.llr_fmt = llr_fmt; a.qscale = qscale; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = nullptr;
+    a.batch = batch; a.max_iters = max_iters; a.work_counter = d_counter; a.rule = rule;
+    CsrSoftArgs so{};
+    so.out = d_soft; so.fmt = soft_fmt; so.kind = soft_kind; so.qscale = soft_qscale;
+    hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(int), st);
+    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
+    const dim3 grid(std::min(batch, soft_grid)), block(g.T);
+    memcpy(info.name, name_soft, sizeof(info.name));
+    if (timer) timer->begin(st);
+    if (dtype == LDPC_I8) launch_soft<int8_t>(dclass, has_rule, grid, block, lds, st, g, rec, a, so);
+    else if (dtype == LDPC_F32) launch_soft<float>(dclass, has_rule, grid, block, lds, st, g, rec, a, so);
+    else launch_soft<_Float16>(dclass, has_rule, grid, block, lds, st, g, rec, a, so);
+    if (timer) timer->end(st);
+    e = hipGetLastError();
+    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr soft launch: %s", hipGetErrorString(e));
     return LDPC_OK;
 }
 

@@ -276,7 +276,8 @@ int ldpc_ctx_path(const ldpc_ctx *ctx);
  *   3. LDPC_F32 min-sum -- every kernel family, both schedules, the 3/4 or a per-context rule: whatever comes back converged has
  *      finite final LLRs.  A frame with any non-finite channel LLR therefore FAILS: converged = 0, iters = max_iters, bits = llr > 0
  *      (a NaN of either sign and -inf give 0, +inf gives 1), final_lam = the channel LLRs as given -- also when the channel's hard
- *      decisions already are a codeword.
+ *      decisions already are a codeword.  The soft output of such a frame (ldpc_decode_batch_dev_soft) is lam as it stands when the
+ *      frame stopped, not the channel LLRs: it may then hold an infinity or a NaN.
  *   4. The tanh rule and LDPC_F64 (the parity modes): no parity with the oracle is claimed on non-finite input; 5 and 6 hold.
  *   5. Self-consistency, every context: a converged frame has H bits = 0 and bits = hard(final_lam); a frame that is not converged
  *      has iters = max_iters and bits = hard(channel LLR as taken in).
@@ -332,6 +333,34 @@ int ldpc_decode_batch_dev_packed(ldpc_ctx *ctx, int max_iters, int batch, const 
                                  int32_t *d_iters, uint8_t *d_converged, void *stream);
 int ldpc_decode_batch_packed(ldpc_ctx *ctx, int max_iters, int batch, const void *llr, int llr_f16, uint8_t *packed,
                              int32_t *iters, uint8_t *converged);
+/* SOFT OUTPUT: ldpc_decode_batch_dev with the decoder's LLRs out, for what follows a decoder in an iterative receiver (a demapper that
+ * takes bit knowledge back in, an outer code, a reliability measure).  Served by the on-chip layered min-sum kernel for any H
+ * (csrc/layered_csr.hip: LDPC_MINSUM, LDPC_SCHED_LAYERED, dtype LDPC_F16, LDPC_F32 or LDPC_I8, with or without cn_scale / cn_offset), in
+ * whose layered schedule the lam cells ARE the posterior: the output is an epilogue of the frame, in instances of their own
+ * (ldpc::layered_csr_soft_kernel<...>, what ldpc_ctx_kernel_name reports after this call; the other entry points launch what they launched).
+ * Specification: tests/soft_output_spec.py, reproduced bit for bit.
+ * All pointers are DEVICE pointers; enqueued on `stream`, not synchronised, ordered as ldpc_decode_batch_dev.  llr_fmt: LDPC_LLR_F32,
+ * LDPC_LLR_F16 or (LDPC_I8 contexts only) LDPC_LLR_I8.  d_bits, d_iters, d_converged are EXACTLY those of the matching
+ * ldpc_decode_batch_dev* call -- a frame out of sweeps still returns the channel's decisions there; d_iters, d_converged may be NULL.
+ * d_soft [batch][N] of element type soft_fmt (LDPC_LLR_*), aligned to that element; soft_kind:
+ *   LDPC_SOFT_POSTERIOR  P = lam as it stands when the frame stops, for EVERY frame: converged in sweep n -- lam after sweep n (final_lam
+ *                        of ldpc_decode_batch_f64); out of sweeps -- lam after sweep max_iters (final_lam gives the channel LLRs there);
+ *                        converged before the first sweep, or max_iters = 0 -- the channel LLRs as the cell took them in; an LDPC_F32
+ *                        frame failed by the non-finite veto -- lam as it stands, which may hold an infinity or a NaN.
+ *   LDPC_SOFT_EXTRINSIC  E = P - C, C the channel LLR as the cell took it in: fp16 cells, the LLR saturated and rounded to binary16 (a NaN
+ *                        as +0); f32 cells, the float; int8 cells, the quantised integer q.  ONE float32 subtraction for float cells, an
+ *                        integer subtraction for int8 cells.  What the decoder learned about a bit from all the others: the next
+ *                        a-priori input of an iterative receiver.
+ * Output formats.  Float cells: LDPC_LLR_F32 the value as it is; LDPC_LLR_F16 clamped to +-65504 and rounded to nearest even as the fp16
+ * store of ldpc_demap_dev (for the posterior of an fp16 cell: the cell's own bits); LDPC_LLR_I8 clip(rint(v * soft_qscale), -127, 127),
+ * a NaN as 0, soft_qscale 0 = 4.0 as in the demappers.  Int8 cells, integer v: LDPC_LLR_F32 fl(float(v) / llr_qscale), one division;
+ * LDPC_LLR_F16 that float as above; LDPC_LLR_I8 clip(v, -127, 127), where soft_qscale must be 0 or the context's scale.
+ * LDPC_EINVAL -- before the device is touched -- for a null d_soft, an unknown format or kind, a negative or non-finite soft_qscale (or one
+ * that is not the context's, above), a d_soft misaligned for its element type.  LDPC_EUNSUPPORTED on a context of any other kernel
+ * family; the message names the family that serves the context and the contexts that have a soft output. */
+enum { LDPC_SOFT_POSTERIOR = 0, LDPC_SOFT_EXTRINSIC = 1 };
+int ldpc_decode_batch_dev_soft(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                               uint8_t *d_converged, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind, void *stream);
 /* page-locked host memory for the host-pointer entry points.  With llr AND bits buffers from ldpc_host_alloc (or
  * registered with hipHostRegister) ldpc_decode_batch runs zero-copy: the decode kernel itself reads the LLRs and
  * writes the bits over PCIe (10-11 Gbit/s PCIe-inclusive on jpl.4096); pageable buffers go through a chunked
@@ -667,6 +696,27 @@ int ldpc_deinterleave_llr_dev(const ldpc_interleaver *il, int batch, const void 
  * LDPC_EINVAL as ldpc_demap_dev_il, and for a null or misaligned d_gain, all before the device is touched. */
 int ldpc_demap_dev_il_csi(const ldpc_modulation *mod, const ldpc_interleaver *il, int batch, const float *d_sym /* [batch][n_sym][2] */,
                           const float *d_gain /* [batch][n_sym] */, double noise_var, void *d_llr, int llr_fmt, float qscale, void *stream);
+/* THE DEMAPPER WITH A-PRIORI INPUT (csrc/demap_apriori.hip; restated in tests/demap_apriori_spec.py): ldpc_demap_dev_il_csi with bit
+ * knowledge, for a receiver that iterates between demapper and decoder (BICM-ID).  d_apriori [batch][N] float32 (4-byte aligned), in
+ * CODEWORD order, holds an LLR for every codeword bit -- log P(1) / P(0), positive means bit 1, the library's sign: the extrinsic output
+ * of ldpc_decode_batch_dev_soft is one, zeros are none.  d_gain may be NULL: a = 1.  Table objects, m = 1..6.  Everything not named here
+ * is ldpc_demap_dev_il_csi's: positions through the table, 0 at the punctured positions, pad bits not written, every element written
+ * exactly once, no memset, the three output formats.  The lane of a symbol gathers its m a-priori values through the m table entries it
+ * stores through: a-priori values at punctured positions are never read; the pad bits of a ragged last symbol have La = 0.
+ * THE RULE, all float32, one operation at a time, nothing fused.  d_p the squared distances of THE LLR RULE, inv_s as above.
+ *   a_p = the sum of La_j over the set label bits j of p, MSB first, left to right (a_0 = +0; one set bit: La_j itself)
+ *   u_p = fl(a_p - fl(d_p inv_s));  U1_j, U0_j = the max of u_p over the labels whose bit j is 1, 0
+ *   max-log:  LLR_j = fl(fl(U1_j - U0_j) - La_j) -- the EXTRINSIC value: the bit's own knowledge is taken out again
+ *   log-MAP (an LDPC_DEMAP_LOGMAP object):  fl(U1_j - U0_j) + (c1 - c0) - La_j, c_v = log(sum over the subset, in label order, of
+ *             exp(u_p - U_v)); a zero correction leaves the max-log term as it is, as in THE LLR RULE
+ * With La = 0 everywhere the result is ldpc_demap_dev_il_csi's up to rounding, not bit for bit -- fl(m0 inv_s) - fl(m1 inv_s) against
+ * fl(fl(m0 - m1) inv_s): within 2^-21 (m0 + m1) inv_s.
+ * LDPC_EUNSUPPORTED for a product object: its Gray-like per-axis labels gain little from iteration.  LDPC_EINVAL as ldpc_demap_dev_il_csi
+ * (a null d_gain excepted), for a null or misaligned d_apriori, and for a d_apriori that overlaps d_llr; all before the device is
+ * touched.  A NaN a-priori value is the caller's error; the other frames of the batch are not affected by it. */
+int ldpc_demap_dev_il_apriori(const ldpc_modulation *mod, const ldpc_interleaver *il, int batch, const float *d_sym /* [batch][n_sym][2] */,
+                              const float *d_gain /* [batch][n_sym] or NULL */, double noise_var, const float *d_apriori /* [batch][N] */, void *d_llr,
+                              int llr_fmt, float qscale, void *stream);
 /* The channel.  Symbol s of a frame lies in block q = s / block, and all symbols of a block share one gain (block >= n_sym: one gain
  * per frame; block = 1: independent per symbol).  DRAW: block pair Q = blocks 2Q and 2Q + 1 takes one Philox call with counter
  * (frame lo, frame hi, Q, stream 3) and key = seed, and the Box-Muller of the noise: (z0, z1) -> block 2Q, (z2, z3) -> block 2Q + 1.

@@ -24,7 +24,9 @@
 Decoded-information Gbit/s = frames x k / kernel time (HIP events around the decode kernel, the median of the timed launches);
 frames: the all-zero codeword + AWGN unless --codewords random, f32 LLRs generated on the device.
 
-usage: python tools/layered_csr_rate.py [--frames 16384] [--reps 3] [--quick] [--lam f32|f16|both|i8 [--lam-only]] [--asm FILE]
+  --soft: only the cost of the soft output (ldpc_decode_batch_dev_soft): on 1920.1280.3.303, for each lam cell, the context's plain decode and
+      its soft decode (posterior, extrinsic; float32 and fp16 out) on the same frames, kernel time by HIP events
+usage: python tools/layered_csr_rate.py [--frames 16384] [--reps 3] [--quick] [--lam f32|f16|both|i8 [--lam-only]] [--soft] [--asm FILE]
                                         [--cn-scale A [A ...]] [--cn-offset B [B ...]] [--codewords zero|random] [--codes NAME [NAME ...]]
 (profiles/r07_layered_csr_f32_rate.txt: --lam both --lam-only --reps 5; profiles/r09_layered_csr_i8_rate.txt: --lam i8 --lam-only --reps 5;
 profiles/r10_layered_rule_ber.txt: --cn-scale 0.75 0.8125 0.875 1 1 --cn-offset 0 0 0 0.25 0.5 --reps 5;
@@ -308,6 +310,45 @@ def lam_comparison(a, out):
             dec.close()
 
 
+def soft_comparison(a, out):
+    """--soft: the cost of the soft output.  One context per lam cell on 1920.1280.3.303; the plain decode (layered_csr_kernel) and the
+    soft decode (layered_csr_soft_kernel: posterior and extrinsic, float32 and fp16 out) on the same frames, HIP events around each call,
+    the five legs in turn inside a repetition; the median of --reps repetitions after one warm-up"""
+    from tests.helpers import load
+    c = load("1920.1280.3.303")
+    N, k, F, MI = c.N, c.k, a.frames, a.max_iters
+    code = E.Code.from_csr(c.graph.row_ptr, c.graph.col_idx, N)
+    out(f"# layered_csr soft output: 1920.1280.3.303, {F} frames, {MI} sweeps at most, all-zero codewords, {a.reps} timed repetitions (median), f32 LLRs on the device")
+    legs = (("plain", None, None), ("posterior f32", "posterior", "f32"), ("extrinsic f32", "extrinsic", "f32"), ("posterior f16", "posterior", "f16"), ("extrinsic f16", "extrinsic", "f16"))
+    for db in (2.0, 4.0):
+        llr = device_frames(F, N, k, db, 20)
+        bits = torch.empty((F, N), dtype=torch.uint8, device="cuda")
+        iters = torch.empty(F, dtype=torch.int32, device="cuda")
+        soft = torch.empty((F, N), dtype=torch.float32, device="cuda")
+        for cell in ("f16", "f32", "i8"):
+            dec = E.Decoder(code, "min", cell, F, schedule="layered", path="fused")
+            ms = {n: [] for n, _, _ in legs}
+            for rep in range(1 + a.reps):
+                for n, kind, fmt in legs:
+                    torch.cuda.synchronize()
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    dec.set_timing(True)
+                    if kind is None:
+                        dec.decode_batch_dev(llr.data_ptr(), bits.data_ptr(), F, MI, iters.data_ptr())
+                    else:
+                        dec.decode_batch_dev_soft(llr.data_ptr(), bits.data_ptr(), soft.data_ptr(), F, MI, kind, fmt, 0.0, iters.data_ptr())
+                    dec.synchronize()
+                    if rep:
+                        ms[n].append(dec.kernel_time()[1])
+                    else:
+                        dec.kernel_time()
+            base = float(np.median(ms["plain"]))
+            out(f"  {db} dB  cell {cell:3s}  mean sweeps {float(iters.float().mean()):5.2f}  " + "  ".join(f"{n} {float(np.median(v)):7.3f} ms ({float(np.median(v)) / base:4.2f}x)" for n, v in ms.items())
+                + f"   [{dec.kernel_name}]")
+            dec.close()
+    code.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16384)
@@ -322,6 +363,7 @@ def main():
                     help="what the error-rate comparisons transmit: the all-zero codeword, or codewords of random messages (encoder from H) under the same noise")
     ap.add_argument("--codes", nargs="+", choices=("1920.1280.3.303", "dvbs2-short", "dvbs2-natural"),
                     help="the --lam i8 and check-node rule comparisons on these codes only (default: all of theirs)")
+    ap.add_argument("--soft", action="store_true", help="only the soft-output comparison: a soft decode against the same context's plain decode")
     ap.add_argument("--asm", help="the device assembly of layered_csr.hip, where the build directory's copy is not at hand")
     a = ap.parse_args()
     if a.asm:
@@ -330,6 +372,10 @@ def main():
     E.init(0)
     F, MI = a.frames, a.max_iters
     out = lambda s: print(s, flush=True)   # noqa: E731
+    if a.soft:
+        soft_comparison(a, out)
+        E.close_all()
+        return
     if a.cn_scale or a.cn_offset:
         a.cn_scale, a.cn_offset = a.cn_scale or [0.75], a.cn_offset or [0.0]
         rule_comparison(a, out)
