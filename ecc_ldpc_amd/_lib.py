@@ -38,7 +38,7 @@ class FadingStruct(C.Structure):   # ldpc_fading
 
 # every symbol include/ldpc_hip.h declares (tests/test_abi.py checks the library exports them all)
 ABI_SYMBOLS = [
-    "ldpc_init", "ldpc_decode_batch_dev_soft", "ldpc_demap_dev_il_apriori", "ldpc_shutdown", "ldpc_current_device", "ldpc_ctx_create_on", "ldpc_sim_create_on", "ldpc_ctx_create_cfg", "ldpc_ctx_schedule", "ldpc_ctx_code", "ldpc_ctx_max_batch", "ldpc_ctx_device",
+    "ldpc_init", "ldpc_decode_batch_dev_soft", "ldpc_decode_state_create", "ldpc_decode_state_destroy", "ldpc_decode_state_frames", "ldpc_decode_state_bytes", "ldpc_decode_state_reset", "ldpc_decode_batch_dev_continue", "ldpc_demap_dev_il_apriori", "ldpc_shutdown", "ldpc_current_device", "ldpc_ctx_create_on", "ldpc_sim_create_on", "ldpc_ctx_create_cfg", "ldpc_ctx_schedule", "ldpc_ctx_code", "ldpc_ctx_max_batch", "ldpc_ctx_device",
     "ldpc_batcher_create", "ldpc_batcher_destroy", "ldpc_batcher_decode_one", "ldpc_batcher_stats",
     "ldpc_ecc_create_replicas", "ldpc_ecc_replicas", "ldpc_ecc_ctx_at", "ldpc_ecc_sim_at", "ldpc_ecc_decode_on", "ldpc_ecc_set_coalescing", "ldpc_ecc_coalescing_stats", "ldpc_code_set_layers", "ldpc_code_layers", "ldpc_qc_layer_order", "ldpc_csr_layer_order", "ldpc_last_error", "ldpc_last_error_code", "ldpc_abi_version", "ldpc_device_count",
     "ldpc_code_create_qc", "ldpc_code_create_csr", "ldpc_code_destroy", "ldpc_code_dims", "ldpc_code_csr",
@@ -85,7 +85,7 @@ _lib = None
 # the interpreter is finalising, __del__ does nothing: no hipFree / hipStreamDestroy ever runs from a finaliser during
 # shutdown, when the order against the HIP runtime's own exit handlers is not defined.
 _live = weakref.WeakSet()
-_CLOSE_ORDER = {"ECC": 0, "Batcher": 1, "Decoder": 2, "Sim": 3, "Code": 4, "Matrix": 5, "PinnedArray": 6, "Modulation": 7, "Interleaver": 8}
+_CLOSE_ORDER = {"ECC": 0, "Batcher": 1, "DecodeState": 1, "Decoder": 2, "Sim": 3, "Code": 4, "Matrix": 5, "PinnedArray": 6, "Modulation": 7, "Interleaver": 8}
 _closed_all = False
 
 
@@ -204,6 +204,15 @@ def lib():
     L.ldpc_decode_batch_i8.argtypes = [vp, C.c_int, C.c_int, vp, u8p, i32p, u8p]
     L.ldpc_decode_batch_dev_i8.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.ldpc_decode_batch_dev_soft.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp]
+    L.ldpc_decode_state_create.restype = vp
+    L.ldpc_decode_state_create.argtypes = [vp, C.c_int]
+    L.ldpc_decode_state_destroy.restype = None
+    L.ldpc_decode_state_destroy.argtypes = [vp]
+    L.ldpc_decode_state_frames.argtypes = [vp]
+    L.ldpc_decode_state_bytes.restype = C.c_size_t
+    L.ldpc_decode_state_bytes.argtypes = [vp]
+    L.ldpc_decode_state_reset.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.ldpc_decode_batch_dev_continue.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp]
     L.ldpc_ctx_llr_qscale.restype = C.c_float
     L.ldpc_ctx_llr_qscale.argtypes = [vp]
     L.ldpc_ctx_cn_scale.restype = C.c_float
@@ -698,6 +707,33 @@ class Decoder:
         self.synchronize()
         return d_bits.cpu().numpy(), d_iters.cpu().numpy(), d_conv.cpu().numpy(), d_soft.cpu().numpy()
 
+    def decode_batch_dev_continue(self, state, d_llr_ptr, d_bits_ptr, batch, max_iters, d_soft_ptr=None, kind="posterior", soft_fmt="f32", soft_qscale=0.0,
+                                  d_iters_ptr=None, d_conv_ptr=None, stream=None, llr_fmt="f32", first=0):
+        """ldpc_decode_batch_dev_continue: decode_batch_dev_soft that starts from slots first .. first + batch - 1 of `state` (a DecodeState made
+        for this decoder) and leaves the new state there; d_soft_ptr may be None.  From a reset state it is decode_batch_dev_soft"""
+        k = _SOFT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        check(lib().ldpc_decode_batch_dev_continue(self._h, state._h if state is not None else None, int(first), int(max_iters), int(batch), d_llr_ptr, _llr_fmt(llr_fmt),
+                                                   d_bits_ptr, d_iters_ptr, d_conv_ptr, d_soft_ptr, _llr_fmt(soft_fmt), float(soft_qscale), k, stream))
+
+    def decode_batch_continue(self, state, llr, max_iters, kind="posterior", soft_fmt="f32", soft_qscale=0.0, first=0):
+        """decode_batch_soft on slots first .. first + F - 1 of `state`: llr [F][N] host -> bits, iters, converged, soft (through torch tensors)"""
+        import torch
+        llr = np.ascontiguousarray(llr)
+        fmt = {np.dtype(np.float32): "f32", np.dtype(np.float16): "f16", np.dtype(np.int8): "i8"}[llr.dtype]
+        F = llr.shape[0]
+        assert llr.shape == (F, self.code.N)
+        dev = torch.device("cuda", lib().ldpc_ctx_device(self._h))
+        d_llr = torch.from_numpy(llr).to(dev)
+        d_bits = torch.zeros((F, self.code.N), dtype=torch.uint8, device=dev)
+        d_iters = torch.zeros(F, dtype=torch.int32, device=dev)
+        d_conv = torch.zeros(F, dtype=torch.uint8, device=dev)
+        d_soft = torch.zeros((F, self.code.N), dtype={"f32": torch.float32, "f16": torch.float16, "i8": torch.int8}[soft_fmt], device=dev)
+        torch.cuda.synchronize(dev)
+        self.decode_batch_dev_continue(state, d_llr.data_ptr(), d_bits.data_ptr(), F, max_iters, d_soft.data_ptr(), kind, soft_fmt, soft_qscale, d_iters.data_ptr(),
+                                       d_conv.data_ptr(), None, fmt, first)
+        self.synchronize()
+        return d_bits.cpu().numpy(), d_iters.cpu().numpy(), d_conv.cpu().numpy(), d_soft.cpu().numpy()
+
     def synchronize(self):
         check(lib().ldpc_ctx_synchronize(self._h))
 
@@ -746,6 +782,44 @@ class Decoder:
     def close(self):
         if self._h and self._owned:
             lib().ldpc_ctx_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        if _finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DecodeState:
+    """ldpc_decode_state: the check messages of `frames` frame slots of one Decoder, kept between Decoder.decode_batch_dev_continue calls;
+    all slots reset.  Bound to the decoder it was made for; close it before that decoder (close_all does)"""
+
+    def __init__(self, dec, frames):
+        self._h = lib().ldpc_decode_state_create(dec._h, int(frames))
+        if not self._h:
+            raise LdpcError(lib().ldpc_last_error_code(), last_error())
+        self.decoder = dec
+        _register(self)
+
+    @property
+    def frames(self):
+        return int(lib().ldpc_decode_state_frames(self._h))
+
+    @property
+    def nbytes(self):
+        """the device bytes the state holds"""
+        return int(lib().ldpc_decode_state_bytes(self._h))
+
+    def reset(self, first=0, count=None, stream=None):
+        """zero-fill slots first .. first + count - 1 (count None: to the last one); enqueued on `stream` (None: the decoder's), not synchronised"""
+        check(lib().ldpc_decode_state_reset(self._h, int(first), self.frames - int(first) if count is None else int(count), stream))
+
+    def close(self):
+        if self._h:
+            lib().ldpc_decode_state_destroy(self._h)
         self._h = None
 
     def __del__(self):

@@ -87,7 +87,17 @@ struct ldpc_ctx {
     int32_t *d_zc_iters = nullptr;
     uint8_t *d_zc_conv = nullptr;
     ldpc::KernelTimer timer;
+    // what a decode state remembers of the context it was made for: never reused, unlike the context's address
+    uint64_t serial = 0;
 };
+// the serials of the live contexts (under g_ctx_mu): a decode state asks here before it touches its context
+static std::mutex g_ctx_mu;
+static std::set<uint64_t> g_live_ctx;
+static uint64_t g_next_serial = 1;
+static bool ctx_alive(uint64_t serial) {
+    std::lock_guard<std::mutex> lk(g_ctx_mu);
+    return g_live_ctx.count(serial) != 0;
+}
 
 // Device selection.  ldpc_init(d) validates device d and makes it the CALLING THREAD's device (thread-local); the first
 // device any thread initialised is the process default for threads that never called ldpc_init.  Objects remember
@@ -462,6 +472,10 @@ static int code_upload(ldpc_code *c, int device, ldpc_code_dev *out) {
 // ------------------------------------------------------------------------------- contexts
 void ldpc_ctx_destroy(ldpc_ctx *ctx) {
     if (!ctx) return;
+    {
+        std::lock_guard<std::mutex> lk(g_ctx_mu);
+        g_live_ctx.erase(ctx->serial);
+    }
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     for (int i = 1; i < ldpc_ctx::kSlots; i++) if (ctx->pstream[i]) hipStreamSynchronize(ctx->pstream[i]);
@@ -571,6 +585,11 @@ ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cf
     const bool minsum = variant == LDPC_MINSUM;
     ctx->cn_scale = minsum ? rule.scale : 0.f; ctx->cn_offset = minsum ? rule.offset : 0.f;
     backend->timer = &ctx->timer;
+    {
+        std::lock_guard<std::mutex> lk(g_ctx_mu);
+        ctx->serial = g_next_serial++;
+        g_live_ctx.insert(ctx->serial);
+    }
     hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         set_error(e == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking): %s", hipGetErrorString(e));
@@ -861,28 +880,125 @@ int ldpc_decode_batch_dev_i8(ldpc_ctx *ctx, int max_iters, int batch, const int8
     return decode_dev_checked(ctx, max_iters, batch, d_llr, ldpc::LLR_I8, d_bits, d_iters, d_converged, stream);
 }
 
-int ldpc_decode_batch_dev_soft(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
-                               uint8_t *d_converged, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind, void *stream) {
-    int rc = check_call(ctx, max_iters, batch);
-    if (rc != LDPC_OK) return rc;
+// the argument checks ldpc_decode_batch_dev_soft and ldpc_decode_batch_dev_continue share: the formats, the kind and the scale (*fmt: the
+// kernels' format of llr_fmt), then -- for a call with frames -- the pointers, where d_soft may be null only if `soft_optional`
+static int check_soft_formats(ldpc_ctx *ctx, int llr_fmt, int soft_fmt, float soft_qscale, int soft_kind, int *fmt) {
     if (llr_fmt != LDPC_LLR_F32 && llr_fmt != LDPC_LLR_F16 && llr_fmt != LDPC_LLR_I8) return set_error(LDPC_EINVAL, "llr_fmt %d is not one of LDPC_LLR_F32, LDPC_LLR_F16, LDPC_LLR_I8", llr_fmt);
     if (soft_fmt != LDPC_LLR_F32 && soft_fmt != LDPC_LLR_F16 && soft_fmt != LDPC_LLR_I8) return set_error(LDPC_EINVAL, "soft_fmt %d is not one of LDPC_LLR_F32, LDPC_LLR_F16, LDPC_LLR_I8", soft_fmt);
     if (soft_kind != LDPC_SOFT_POSTERIOR && soft_kind != LDPC_SOFT_EXTRINSIC) return set_error(LDPC_EINVAL, "soft_kind %d is neither LDPC_SOFT_POSTERIOR nor LDPC_SOFT_EXTRINSIC", soft_kind);
-    const int fmt = packed_format(llr_fmt);
-    if ((rc = check_format(ctx, fmt)) != LDPC_OK) return rc;
+    *fmt = packed_format(llr_fmt);
+    int rc = check_format(ctx, *fmt);
+    if (rc != LDPC_OK) return rc;
     if (!(soft_qscale >= 0.f) || !std::isfinite(soft_qscale)) return set_error(LDPC_EINVAL, "soft_qscale %g is negative or not finite (0 = 4.0)", (double)soft_qscale);
     // an int8 cell's soft output in int8 is the cell's own integer: no other scale can be asked for
     if (ctx->dtype == LDPC_I8 && soft_fmt == LDPC_LLR_I8 && soft_qscale != 0.f && soft_qscale != ldpc_ctx_llr_qscale(ctx))
         return set_error(LDPC_EINVAL, "soft_qscale %g: the int8 soft output of an LDPC_I8 context has the context's scale %g (pass that, or 0)", (double)soft_qscale,
                          (double)ldpc_ctx_llr_qscale(ctx));
-    if (batch == 0) return LDPC_OK;
+    return LDPC_OK;
+}
+static int check_soft_pointers(const void *d_llr, int fmt, const uint8_t *d_bits, const void *d_soft, int soft_fmt, bool soft_optional) {
     if (!d_llr || !d_bits) return set_error(LDPC_EINVAL, "null d_llr/d_bits");
-    if (!d_soft) return set_error(LDPC_EINVAL, "null d_soft");
+    if (!d_soft && !soft_optional) return set_error(LDPC_EINVAL, "null d_soft");
     const size_t es = soft_fmt == LDPC_LLR_F32 ? 4 : soft_fmt == LDPC_LLR_F16 ? 2 : 1;
     if ((uintptr_t)d_soft % es) return set_error(LDPC_EINVAL, "d_soft is not aligned to its %zu-byte elements", es);
     if ((uintptr_t)d_llr % llr_bytes(fmt)) return set_error(LDPC_EINVAL, "d_llr is not aligned to its %zu-byte elements", llr_bytes(fmt));
+    return LDPC_OK;
+}
+
+int ldpc_decode_batch_dev_soft(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                               uint8_t *d_converged, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind, void *stream) {
+    int rc = check_call(ctx, max_iters, batch), fmt = 0;
+    if (rc != LDPC_OK) return rc;
+    if ((rc = check_soft_formats(ctx, llr_fmt, soft_fmt, soft_qscale, soft_kind, &fmt)) != LDPC_OK) return rc;
+    if (batch == 0) return LDPC_OK;
+    if ((rc = check_soft_pointers(d_llr, fmt, d_bits, d_soft, soft_fmt, false)) != LDPC_OK) return rc;
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     return ctx->backend->decode_soft(st, max_iters, batch, d_llr, fmt, d_bits, d_iters, d_converged, d_soft, soft_fmt, soft_qscale == 0.f ? 4.0f : soft_qscale, soft_kind);
+}
+
+// ---- a decode state: the check messages of `frames` frame slots, kept between calls (csrc/backend.h decode_state_bytes / decode_continue)
+struct ldpc_decode_state {
+    ldpc_ctx *ctx = nullptr;            // the context it was made for: its records are laid out in that context's geometry
+    uint64_t ctx_serial = 0;            // ... and that context's serial: an address can be a later context's, a serial cannot
+    int frames = 0, device = 0;
+    size_t rec_bytes = 0, sum_bytes = 0;   // per slot
+    void *rec = nullptr, *sum = nullptr;   // [frames] x each
+};
+
+ldpc_decode_state *ldpc_decode_state_create(ldpc_ctx *ctx, int max_frames) {
+    if (!ctx) { set_error(LDPC_EINVAL, "null ctx"); return nullptr; }
+    if (max_frames < 1) { set_error(LDPC_EINVAL, "max_frames %d < 1", max_frames); return nullptr; }
+    size_t rb = 0, sb = 0;
+    if (ctx->backend->decode_state_bytes(&rb, &sb) != LDPC_OK) return nullptr;
+    HIPCHK_NULL(hipSetDevice(ctx->device));
+    ldpc_decode_state *s = new (std::nothrow) ldpc_decode_state();
+    if (!s) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    s->ctx = ctx; s->ctx_serial = ctx->serial; s->frames = max_frames; s->device = ctx->device; s->rec_bytes = rb; s->sum_bytes = sb;
+    const size_t total = (rb + sb) * (size_t)max_frames;
+    hipError_t e = hipMalloc(&s->rec, rb * (size_t)max_frames);
+    if (e == hipSuccess) e = hipMalloc(&s->sum, sb * (size_t)max_frames);
+    // all slots reset when this returns: the fills go to the context's own stream, where the decodes run by default, and are waited for
+    if (e == hipSuccess) e = hipMemsetAsync(s->rec, 0, rb * (size_t)max_frames, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->sum, 0, sb * (size_t)max_frames, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error(e == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "ldpc_decode_state_create: %zu bytes of device memory for %d frames (%zu + %zu per frame): %s", total,
+                  max_frames, rb, sb, hipGetErrorString(e));
+        (void)hipFree(s->rec); (void)hipFree(s->sum);
+        delete s;
+        return nullptr;
+    }
+    return s;
+}
+
+void ldpc_decode_state_destroy(ldpc_decode_state *st) {
+    if (!st) return;
+    (void)hipSetDevice(st->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(st->rec); (void)hipFree(st->sum);
+    delete st;
+}
+
+int ldpc_decode_state_frames(const ldpc_decode_state *st) { return st ? st->frames : set_error(LDPC_EINVAL, "null state"); }
+size_t ldpc_decode_state_bytes(const ldpc_decode_state *st) { return st ? (st->rec_bytes + st->sum_bytes) * (size_t)st->frames : 0; }
+
+static int check_state_range(const ldpc_decode_state *st, int first, int count) {
+    if (!st) return set_error(LDPC_EINVAL, "null state");
+    if (first < 0 || count < 0 || (long long)first + count > st->frames)
+        return set_error(LDPC_EINVAL, "slots [%d, %d + %d) outside the state's %d frames", first, first, count, st->frames);
+    return LDPC_OK;
+}
+
+int ldpc_decode_state_reset(ldpc_decode_state *st, int first, int count, void *stream) {
+    int rc = check_state_range(st, first, count);
+    if (rc != LDPC_OK) return rc;
+    if (count == 0) return LDPC_OK;
+    if (!stream && !ctx_alive(st->ctx_serial)) return set_error(LDPC_EINVAL, "the state's context was destroyed: no stream of its own to reset on (pass one)");
+    HIPCHK(hipSetDevice(st->device));
+    hipStream_t s = stream ? (hipStream_t)stream : st->ctx->stream;
+    HIPCHK(hipMemsetAsync((char *)st->rec + st->rec_bytes * (size_t)first, 0, st->rec_bytes * (size_t)count, s));
+    HIPCHK(hipMemsetAsync((char *)st->sum + st->sum_bytes * (size_t)first, 0, st->sum_bytes * (size_t)count, s));
+    return LDPC_OK;
+}
+
+int ldpc_decode_batch_dev_continue(ldpc_ctx *ctx, ldpc_decode_state *state, int first, int max_iters, int batch, const void *d_llr, int llr_fmt,
+                                   uint8_t *d_bits, int32_t *d_iters, uint8_t *d_converged, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind,
+                                   void *stream) {
+    if (!ctx) return set_error(LDPC_EINVAL, "null ctx");
+    size_t rb = 0, sb = 0;
+    int rc = ctx->backend->decode_state_bytes(&rb, &sb), fmt = 0;      // (another kernel family: LDPC_EUNSUPPORTED with its name)
+    if (rc != LDPC_OK) return rc;
+    if (!state) return set_error(LDPC_EINVAL, "null state");
+    if (state->ctx != ctx || state->ctx_serial != ctx->serial) return set_error(LDPC_EINVAL, "the state was made for another context (its records are laid out in that context's geometry)");
+    if ((rc = check_state_range(state, first, batch)) != LDPC_OK) return rc;
+    if ((rc = check_call(ctx, max_iters, batch)) != LDPC_OK) return rc;
+    if ((rc = check_soft_formats(ctx, llr_fmt, soft_fmt, soft_qscale, soft_kind, &fmt)) != LDPC_OK) return rc;
+    if (batch == 0) return LDPC_OK;
+    if ((rc = check_soft_pointers(d_llr, fmt, d_bits, d_soft, soft_fmt, true)) != LDPC_OK) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    return ctx->backend->decode_continue(st, state->rec, state->sum, first, max_iters, batch, d_llr, fmt, d_bits, d_iters, d_converged, d_soft, soft_fmt,
+                                         soft_qscale == 0.f ? 4.0f : soft_qscale, soft_kind);
 }
 
 int ldpc_decode_batch_dev_packed(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int llr_f16, uint8_t *d_packed, int32_t *d_iters,

@@ -28,6 +28,20 @@ struct Backend {
         return set_error(LDPC_EUNSUPPORTED, "no soft output from %s: ldpc_decode_batch_dev_soft is served by the on-chip layered min-sum kernel for any H "
                          "(ldpc::layered_csr_kernel: min-sum, LDPC_SCHED_LAYERED, dtype LDPC_F16, LDPC_F32 or LDPC_I8, with or without a check-node rule)", kernel_name());
     }
+    // A DECODE STATE (ldpc_decode_state, api.cc): per frame slot, the check-to-variable messages -- as the row records of the family that
+    // serves it -- and the sum of check messages per column.  decode_state_bytes: the device bytes of one slot's records and of its sums
+    // (api.cc allocates slots x each; a zero fill is a reset slot).  decode_continue: decode_soft() that starts from slots first .. first +
+    // batch - 1 of that memory and leaves the new state there (ldpc_decode_batch_dev_continue, validated by api.cc); d_soft may be null.
+    // Served by csrc/layered_csr.hip alone; every other family answers both with LDPC_EUNSUPPORTED and its own name
+    virtual int decode_state_bytes(size_t *, size_t *) { return no_decode_state(); }
+    virtual int decode_continue(hipStream_t, void *, void *, int, int, int, const void *, int, uint8_t *, int32_t *, uint8_t *, void *, int, float, int) {
+        return no_decode_state();
+    }
+    int no_decode_state() const {
+        return set_error(LDPC_EUNSUPPORTED, "no decode state on %s: ldpc_decode_state_create and ldpc_decode_batch_dev_continue are served by the on-chip layered "
+                         "min-sum kernel for any H (ldpc::layered_csr_kernel: min-sum, LDPC_SCHED_LAYERED, dtype LDPC_F16, LDPC_F32 or LDPC_I8, with or without a "
+                         "check-node rule)", kernel_name());
+    }
     // one teacher-forced iteration from given (lam, ne) in f64 (ldpc_debug_step), or LDPC_EUNSUPPORTED with the reason
     virtual int step(hipStream_t st, int batch, const double *d_orig, const double *d_lam, const double *d_ne, double *d_ne_out,
                      double *d_lam_out, uint8_t *d_syn) = 0;

@@ -39,9 +39,17 @@
 // THE SOFT OUTPUT (ldpc_decode_batch_dev_soft; specification tests/soft_output_spec.py, reproduced bit for bit).  In a layered schedule the
 // lam cells in LDS ARE the posterior, so the output is an epilogue of the frame: lam as it stands when the frame stops -- converged, out of
 // sweeps or vetoed alike --, or that less the channel LLR as the cell took it in, read from memory again; f32, fp16 or int8 out.  It lives in
-// instances of their own, layered_csr_soft_kernel<D, CELL>, which take one more argument.  The body of both kernels is text,
-// layered_csr_body.h, included twice: the eighteen layered_csr_kernel instances are compiled from what they were compiled from before and
+// instances of their own, layered_csr_soft_kernel<D, CELL>, which take one more argument.  The body of the kernels is text,
+// layered_csr_body.h, included once per kernel: the eighteen layered_csr_kernel instances are compiled from what they were compiled from before and
 // are instruction for instruction and register for register what they were (profiles/r20_bicm_id.txt).
+// THE DECODE THAT CONTINUES (ldpc_decode_state_*, ldpc_decode_batch_dev_continue; specification tests/decode_continue_spec.py, reproduced bit
+// for bit).  The row records ARE a frame's check-to-variable messages, and with the per-column sum S of those messages they are all a decode
+// needs to go on from where it stopped.  A decode state keeps both per frame slot in device memory -- [slot][nslab][T] records in the
+// context's geometry, [slot][N] sums as float (int16 for int8 cells): 12 nslab T + 4 N bytes a slot, 8 nslab T + 2 N for int8 --, read once
+// and written once per call on top of the plain decode's traffic.  layered_csr_cont_kernel<D, CELL> is the third inclusion of the body:
+// lam <- cell(C' + S) in the prologue (a reset slot adds +0), the syndrome before the first sweep is that lam's, every sweep reads its
+// records (a zero record is "no old message": t = l - (+0) is l bit for bit), the epilogue writes S <- lam - C' for every frame and the soft
+// output when asked.  The 36 other instances are what they were (profiles/r21_decode_continue.txt).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -96,6 +104,13 @@ struct CsrSoftArgs {
     int fmt;                        // MOD_LLR_F32 / _F16 / _I8 (= LDPC_LLR_*)
     int kind;                       // LDPC_SOFT_POSTERIOR: lam as it stands; LDPC_SOFT_EXTRINSIC: lam - the channel LLR as the cell took it in
     float qscale;                   // (float cells, fmt _I8) the scale of the output's quantiser
+};
+
+// the decode state of layered_csr_cont_kernel (ldpc_decode_batch_dev_continue): frame f of the call lives in slot first + f
+struct CsrContArgs {
+    void *rec;                      // [slots][nslab][T] row records (CsrRec, or CsrRecI8 with int8 lam), in the context's own geometry
+    void *sum;                      // [slots][N] the sum of check messages per column: float (fp16 and f32 cells) or int16 (int8 cells)
+    int first;
 };
 
 namespace {   // (the device helpers below are layered_lds.hip's, kept local to this file)
@@ -207,6 +222,28 @@ __device__ __forceinline__ uint2 hard_q8(uint2 w) {
 #pragma unroll
     for (int k = 0; k < 4; k++) { b.x |= ((int8_t)(w.x >> (8 * k)) > 0 ? 1u : 0u) << (8 * k); b.y |= ((int8_t)(w.y >> (8 * k)) > 0 ? 1u : 0u) << (8 * k); }
     return b;
+}
+
+// (a continuing decode) eight int8 cells plus eight int16 sums of check messages, clipped to +-127; and eight cells less eight cells as int16
+__device__ __forceinline__ uint2 add_sum_q8(uint2 w, uint4 s) {
+    const uint32_t sw[4] = {s.x, s.y, s.z, s.w};
+    uint2 r = make_uint2(0u, 0u);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int lo = min(max((int)(int8_t)(w.x >> (8 * k)) + (int)(int16_t)(sw[k >> 1] >> (16 * (k & 1))), -127), 127);
+        const int hi = min(max((int)(int8_t)(w.y >> (8 * k)) + (int)(int16_t)(sw[2 + (k >> 1)] >> (16 * (k & 1))), -127), 127);
+        r.x |= ((uint32_t)lo & 0xFFu) << (8 * k); r.y |= ((uint32_t)hi & 0xFFu) << (8 * k);
+    }
+    return r;
+}
+__device__ __forceinline__ uint4 diff_q8(uint2 w, uint2 c) {
+    uint32_t d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int lo = (int)(int8_t)(w.x >> (8 * k)) - (int)(int8_t)(c.x >> (8 * k)), hi = (int)(int8_t)(w.y >> (8 * k)) - (int)(int8_t)(c.y >> (8 * k));
+        d[k >> 1] |= ((uint32_t)lo & 0xFFFFu) << (16 * (k & 1)); d[2 + (k >> 1)] |= ((uint32_t)hi & 0xFFFFu) << (16 * (k & 1));
+    }
+    return make_uint4(d[0], d[1], d[2], d[3]);
 }
 
 // a message magnitude under the rule (alpha, beta), float cells: the product rounded, then the difference rounded -- never one fused
@@ -405,14 +442,29 @@ constexpr int csr_max_threads(int dclass) { return dclass > 20 ? 512 : 1024; }
 template <int DCLASS, typename CELL = _Float16>
 __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_kernel(CsrLayDev g, typename Cell<CELL>::Rec *rec_all, CsrLayArgs A) {
 #define LAYERED_CSR_SOFT 0
+#define LAYERED_CSR_CONT 0
 #include "layered_csr_body.h"
+#undef LAYERED_CSR_CONT
 #undef LAYERED_CSR_SOFT
 }
 // the same decode with the soft output S (ldpc_decode_batch_dev_soft): instances of their own beside the eighteen above
 template <int DCLASS, typename CELL = _Float16>
 __global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_soft_kernel(CsrLayDev g, typename Cell<CELL>::Rec *rec_all, CsrLayArgs A, CsrSoftArgs S) {
 #define LAYERED_CSR_SOFT 1
+#define LAYERED_CSR_CONT 0
 #include "layered_csr_body.h"
+#undef LAYERED_CSR_CONT
+#undef LAYERED_CSR_SOFT
+}
+// the decode that CONTINUES from a decode state and leaves the new state behind (ldpc_decode_batch_dev_continue): a third family of
+// instances.  Records are the slot's (K.rec), the prologue adds the slot's sums (K.sum), every sweep reads its records -- the "first sweep
+// writes only" branch is not instantiated --, the epilogue writes the new sums for every frame and the soft output when S.out is not null
+template <int DCLASS, typename CELL = _Float16>
+__global__ __launch_bounds__(csr_max_threads(DCLASS)) void layered_csr_cont_kernel(CsrLayDev g, CsrLayArgs A, CsrSoftArgs S, CsrContArgs K) {
+#define LAYERED_CSR_SOFT 1
+#define LAYERED_CSR_CONT 1
+#include "layered_csr_body.h"
+#undef LAYERED_CSR_CONT
 #undef LAYERED_CSR_SOFT
 }
 
@@ -448,6 +500,19 @@ template <typename LT> void launch_soft(int dclass, bool rule, dim3 grid, dim3 b
     else hipLaunchKernelGGL(soft_kernel_for<LT>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a, so);
 }
 
+template <typename LT> using csr_cont_kernel_t = void (*)(CsrLayDev, CsrLayArgs, CsrSoftArgs, CsrContArgs);
+template <typename LT> csr_cont_kernel_t<LT> cont_kernel_for(int dclass) {
+    return dclass == 8 ? layered_csr_cont_kernel<8, LT> : dclass == 20 ? layered_csr_cont_kernel<20, LT> : layered_csr_cont_kernel<32, LT>;
+}
+const void *pick_cont_kernel(int dclass, int dtype, bool rule) {
+    if (rule) return dtype == LDPC_F32 ? (const void *)cont_kernel_for<Ruled<float>>(dclass) : dtype == LDPC_I8 ? (const void *)cont_kernel_for<Ruled<int8_t>>(dclass) : (const void *)cont_kernel_for<Ruled<_Float16>>(dclass);
+    return dtype == LDPC_F32 ? (const void *)cont_kernel_for<float>(dclass) : dtype == LDPC_I8 ? (const void *)cont_kernel_for<int8_t>(dclass) : (const void *)cont_kernel_for<_Float16>(dclass);
+}
+template <typename LT> void launch_cont(int dclass, bool rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, const CsrLayArgs &a, const CsrSoftArgs &so, const CsrContArgs &k) {
+    if (rule) hipLaunchKernelGGL(cont_kernel_for<Ruled<LT>>(dclass), grid, block, lds, st, g, a, so, k);
+    else hipLaunchKernelGGL(cont_kernel_for<LT>(dclass), grid, block, lds, st, g, a, so, k);
+}
+
 // ------------------------------------------------------------------ host side
 struct LayeredCsrState : Backend {
     int max_batch = 0, dclass = 8, grid = 0, nslab = 0;
@@ -465,8 +530,16 @@ struct LayeredCsrState : Backend {
     ~LayeredCsrState() override {
         (void)hipFree(d_cols); (void)hipFree(d_slab); (void)hipFree(d_wdeg); (void)hipFree(d_step); (void)hipFree(d_counter); (void)hipFree(rec);
     }
-    char name_plain[sizeof(LaunchInfo::name)] = "", name_soft[sizeof(LaunchInfo::name)] = "";   // info.name is that of the last launch
+    char name_plain[sizeof(LaunchInfo::name)] = "", name_soft[sizeof(LaunchInfo::name)] = "", name_cont[sizeof(LaunchInfo::name)] = "";   // info.name is that of the last launch
     int soft_grid = 0;          // resident workgroups of the soft instance (0: not asked yet)
+    int cont_grid = 0;          // ... of the continuing instance, whose records are the state's: not bounded by `grid`
+    int decode_state_bytes(size_t *rec_b, size_t *sum_b) override {
+        *rec_b = rec_bytes(dtype) * (size_t)std::max(nslab, 1) * g.T;
+        *sum_b = (dtype == LDPC_I8 ? sizeof(int16_t) : sizeof(float)) * (size_t)g.N;
+        return LDPC_OK;
+    }
+    int decode_continue(hipStream_t st, void *st_rec, void *st_sum, int first, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits,
+                        int32_t *d_iters, uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) override;
     int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                uint8_t *d_conv, double *d_final, double *d_trace) override;
     int decode_soft(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
@@ -600,6 +673,7 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
         {   // "ldpc::layered_csr_kernel<...>" -> "ldpc::layered_csr_soft_kernel<...>"
             const char *lt = strchr(s->info.name, '<');
             snprintf(s->name_soft, sizeof(s->name_soft), "ldpc::layered_csr_soft_kernel%s", lt ? lt : "");
+            snprintf(s->name_cont, sizeof(s->name_cont), "ldpc::layered_csr_cont_kernel%s", lt ? lt : "");
         }
         s->info.threads = T; s->info.frames_per_wg = 1;
         return s;
@@ -661,6 +735,44 @@ int LayeredCsrState::decode_soft(hipStream_t st, int max_iters, int batch, const
     if (timer) timer->end(st);
     e = hipGetLastError();
     if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr soft launch: %s", hipGetErrorString(e));
+    return LDPC_OK;
+}
+
+// The continuing instance of the context's kernel: same tables, counter and geometry; its records and sums are the state's slots
+// first .. first + batch - 1 (st_rec, st_sum: slot 0), so its grid is bounded by its own residency alone, asked for once.
+int LayeredCsrState::decode_continue(hipStream_t st, void *st_rec, void *st_sum, int first, int max_iters, int batch, const void *d_llr, int llr_fmt,
+                                     uint8_t *d_bits, int32_t *d_iters, uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) {
+    if (llr_fmt == LLR_I8 && dtype != LDPC_I8) return set_error(LDPC_EUNSUPPORTED, "int8 LLRs are taken by LDPC_I8 contexts only");
+    if (!cont_grid) {
+        const void *kern = pick_cont_kernel(dclass, dtype, has_rule);
+        int per_cu = 0, dev = 0;
+        hipDeviceProp_t prop;
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, g.T, lds);
+        if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr continuing instance: %s", hipGetErrorString(e));
+        if (per_cu <= 0) return set_error(LDPC_EHIP, "layered_csr: no workgroup of %d threads and %zu B of LDS of the continuing instance is resident", g.T, lds);
+        cont_grid = per_cu * prop.multiProcessorCount;
+    }
+    CsrLayArgs a{};
+    a.llr = d_llr; a.llr_fmt = llr_fmt; a.qscale = qscale; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = nullptr;
+    a.batch = batch; a.max_iters = max_iters; a.work_counter = d_counter; a.rule = rule;
+    CsrSoftArgs so{};
+    so.out = d_soft; so.fmt = soft_fmt; so.kind = soft_kind; so.qscale = soft_qscale;
+    CsrContArgs k{};
+    k.rec = st_rec; k.sum = st_sum; k.first = first;
+    hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(int), st);
+    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
+    const dim3 grid(std::min(batch, cont_grid)), block(g.T);
+    memcpy(info.name, name_cont, sizeof(info.name));
+    if (timer) timer->begin(st);
+    if (dtype == LDPC_I8) launch_cont<int8_t>(dclass, has_rule, grid, block, lds, st, g, a, so, k);
+    else if (dtype == LDPC_F32) launch_cont<float>(dclass, has_rule, grid, block, lds, st, g, a, so, k);
+    else launch_cont<_Float16>(dclass, has_rule, grid, block, lds, st, g, a, so, k);
+    if (timer) timer->end(st);
+    e = hipGetLastError();
+    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr continuing launch: %s", hipGetErrorString(e));
     return LDPC_OK;
 }
 

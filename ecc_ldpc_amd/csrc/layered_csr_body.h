@@ -1,8 +1,12 @@
-// layered_csr_body.h -- the body of layered_csr_kernel (layered_csr.hip), as TEXT: that file includes it twice, once into
+// layered_csr_body.h -- the body of layered_csr_kernel (layered_csr.hip), as TEXT: that file includes it three times, once into
 // layered_csr_kernel with LAYERED_CSR_SOFT 0 and once into layered_csr_soft_kernel with LAYERED_CSR_SOFT 1, where the frame's epilogue also
 // writes the soft output S (ldpc_decode_batch_dev_soft).  Text and not a function template, so that the eighteen instances without a
 // soft output are compiled from exactly what they were compiled from before the soft output existed: they are instruction for instruction
 // and register for register what they were.  No include guard.  In scope: DCLASS, CELL, g, rec_all, A, and (soft) S.
+// A third inclusion, with LAYERED_CSR_CONT 1 (and LAYERED_CSR_SOFT 1), is layered_csr_cont_kernel (ldpc_decode_batch_dev_continue): the frame's
+// records are those of its slot of a decode state (K.rec; no rec_all), the prologue adds the slot's sum of check messages K.sum to the channel
+// LLRs, every sweep reads its records, the epilogue writes the new sum for every frame and the soft output only when S.out is not null.
+// The other two inclusions define LAYERED_CSR_CONT as 0: their preprocessed text is what it was.  In scope there: K, and no rec_all.
     typedef typename CellOf<CELL>::type LT;
     constexpr bool RULE = CellOf<CELL>::rule;
     CsrRule rule{};
@@ -20,10 +24,20 @@
     const int W = T >> 6, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nslab = ((ctab_t)g.step_ptr)[g.nstep];
     const uint32_t lam0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem;   // LDS byte address of lam
+#if !LAYERED_CSR_CONT
     Rec *const rec = rec_all + (size_t)blockIdx.x * nslab * T + tid;        // this thread's record of slab s: rec[s T]
+#else
+    typedef typename std::conditional<kInt8, int16_t, float>::type ST;      // a cell of the state's sum of check messages
+#endif
     int frame = blockIdx.x;
     while (frame < A.batch) {
         const size_t fN = (size_t)frame * g.N;
+#if LAYERED_CSR_CONT
+        // the frame's slot of the state: its records (this thread's of slab s: rec[s T]) and its row of sums
+        const size_t slot = (size_t)K.first + (size_t)frame;
+        Rec *const rec = reinterpret_cast<Rec *>(K.rec) + slot * nslab * T + tid;
+        ST *const sum = reinterpret_cast<ST *>(K.sum) + slot * g.N;
+#endif
         // ---- lam <- channel LLRs, as stored: saturated, rounded to fp16 / the float (eight per lane and request when the frame is 16-byte aligned)
         bool wide;
         if constexpr (kInt8)    // (int8 LLRs: 8 cells are one 8-byte request)
@@ -32,6 +46,42 @@
         else
             wide = (g.N & 7) == 0 && A.llr_fmt != LLR_F64 && !A.final_lam &&
                           (((uintptr_t)A.llr + fN * (A.llr_fmt == LLR_F16 ? 2 : 4)) & 15) == 0 && (((uintptr_t)A.bits + fN) & 7) == 0;   // (uniform)
+#if LAYERED_CSR_CONT
+        wide = wide && ((uintptr_t)sum & 15) == 0;      // (the slot's row of sums is read and written eight cells per lane as well; uniform)
+        // ---- lam <- the channel LLRs as the cell takes them in, plus the slot's sum of check messages, as the cell stores that:
+        // fl32(C' + S) (f32), that saturated and rounded to fp16, or clip(q + S, +-127) (int8).  A reset slot adds +0
+        if constexpr (kInt8) {
+            if (wide) {
+                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 4
+                    for (int i = tid * 8; i < g.N; i += T * 8)
+                        *reinterpret_cast<uint2 *>(lam + i) = add_sum_q8(load_q8<decltype(fmt)::value>(A.llr, fN + i, A.qscale), *reinterpret_cast<const uint4 *>(sum + i));
+                });
+            } else {
+                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 8
+                    for (int i = tid; i < g.N; i += T) lam[i] = (int8_t)min(max(load_q<decltype(fmt)::value>(A.llr, fN + i, A.qscale) + (int)sum[i], -127), 127);
+                });
+            }
+        } else if (wide) {
+            with_llr_format(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 4
+                for (int i = tid * 8; i < g.N; i += T * 8) {
+                    cell8 h;
+                    load_llr8<LT, decltype(fmt)::value>(A.llr, fN + i, h);
+                    const float4 a = *reinterpret_cast<const float4 *>(sum + i), b = *reinterpret_cast<const float4 *>(sum + i + 4);
+                    h[0] = Cell<LT>::of((float)h[0] + a.x); h[1] = Cell<LT>::of((float)h[1] + a.y); h[2] = Cell<LT>::of((float)h[2] + a.z); h[3] = Cell<LT>::of((float)h[3] + a.w);
+                    h[4] = Cell<LT>::of((float)h[4] + b.x); h[5] = Cell<LT>::of((float)h[5] + b.y); h[6] = Cell<LT>::of((float)h[6] + b.z); h[7] = Cell<LT>::of((float)h[7] + b.w);
+                    Cell<LT>::st8(lam + i, h);
+                }
+            });
+        } else {
+            with_llr_format(A.llr_fmt, [&](auto fmt) {
+#pragma unroll 8
+                for (int i = tid; i < g.N; i += T) lam[i] = Cell<LT>::of((float)Cell<LT>::llr(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i)) + sum[i]);
+            });
+        }
+#else
         if constexpr (kInt8) {
             // ---- lam <- the quantised channel LLRs (int8 LLRs as they are)
             if (wide) {
@@ -60,6 +110,7 @@
                 for (int i = tid; i < g.N; i += T) lam[i] = Cell<LT>::llr(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
             });
         }
+#endif
         if (tid == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; ctl[4] = 0; if constexpr (kVeto) ctl[5] = 0; }
         lds_barrier();
         bool conv = false;
@@ -90,6 +141,12 @@
                         const int c0 = ((ctab_t)g.slab)[2 * s], wv = ((ctab_t)g.wdeg)[s * W + wave];
                         const uint16_t *cp = g.cols + c0 + tid;
                         Rec out;
+#if LAYERED_CSR_CONT
+                        {   // every sweep subtracts the stored messages: the first one those the slot holds (all +0 in a reset slot)
+                            const Rec in = rec[(size_t)s * T];
+                            csr_row_at<LT, DCLASS, false, RULE>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, in, out, odd, flip, rule);
+                        }
+#else
                         if (n == 1) {
                             const Rec none{};
                             csr_row_at<LT, DCLASS, true, RULE>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, none, out, odd, flip, rule);
@@ -97,6 +154,7 @@
                             const Rec in = rec[(size_t)s * T];
                             csr_row_at<LT, DCLASS, false, RULE>(cp, T, wv & 0xFF, (wv & 0x100) != 0, lam0, in, out, odd, flip, rule);
                         }
+#endif
                         rec[(size_t)s * T] = out;
                     }
                     if (st == g.nstep - 1 && __builtin_amdgcn_ballot_w64(odd || flip) != 0 && (tid & 63) == 0) ctl[1 + n % 3] = 1;
@@ -169,6 +227,41 @@
                 }
             });
         }
+#if LAYERED_CSR_CONT
+        {
+            // ---- the slot's new sum of check messages: lam as it stands less the channel LLR as the cell took it in, read from memory again --
+            // the extrinsic value before its output format --, for EVERY frame however it stopped.  (The records are already the slot's.)
+            if constexpr (kInt8) {
+                with_llr_format_i8(A.llr_fmt, [&](auto fmt) {
+                    if (wide) {
+#pragma unroll 2
+                        for (int i = tid * 8; i < g.N; i += T * 8)
+                            *reinterpret_cast<uint4 *>(sum + i) = diff_q8(*reinterpret_cast<const uint2 *>(lam + i), load_q8<decltype(fmt)::value>(A.llr, fN + i, A.qscale));
+                    } else {
+#pragma unroll 4
+                        for (int i = tid; i < g.N; i += T) sum[i] = (int16_t)((int)lam[i] - load_q<decltype(fmt)::value>(A.llr, fN + i, A.qscale));
+                    }
+                });
+            } else {
+                with_llr_format(A.llr_fmt, [&](auto fmt) {
+                    if (wide) {
+#pragma unroll 2
+                        for (int i = tid * 8; i < g.N; i += T * 8) {
+                            const cell8 h = Cell<LT>::ld8(lam + i);
+                            cell8 c;
+                            load_llr8<LT, decltype(fmt)::value>(A.llr, fN + i, c);
+                            *reinterpret_cast<float4 *>(sum + i) = make_float4((float)h[0] - (float)c[0], (float)h[1] - (float)c[1], (float)h[2] - (float)c[2], (float)h[3] - (float)c[3]);
+                            *reinterpret_cast<float4 *>(sum + i + 4) = make_float4((float)h[4] - (float)c[4], (float)h[5] - (float)c[5], (float)h[6] - (float)c[6], (float)h[7] - (float)c[7]);
+                        }
+                    } else {
+#pragma unroll 4
+                        for (int i = tid; i < g.N; i += T) sum[i] = (float)lam[i] - (float)Cell<LT>::llr(load_llr_as<float, decltype(fmt)::value>(A.llr, fN + i));
+                    }
+                });
+            }
+        }
+        if (S.out != nullptr)                           // (the soft output is optional here; workgroup-uniform)
+#endif
 #if LAYERED_CSR_SOFT
         {
             // ---- soft output: lam as it stands -- whether the frame converged, ran out of sweeps or was vetoed --, less (extrinsic) the

@@ -278,6 +278,10 @@ int ldpc_ctx_path(const ldpc_ctx *ctx);
  *      (a NaN of either sign and -inf give 0, +inf gives 1), final_lam = the channel LLRs as given -- also when the channel's hard
  *      decisions already are a codeword.  The soft output of such a frame (ldpc_decode_batch_dev_soft) is lam as it stands when the
  *      frame stopped, not the channel LLRs: it may then hold an infinity or a NaN.
+ *   3a. A decode state (ldpc_decode_batch_dev_continue) of an LDPC_F32 context: the veto also looks at the starting lam C' + S.  A slot whose
+ *      frame diverged, or was given a non-finite LLR, holds an S that is not finite: it stays failed (converged = 0) in every later call,
+ *      whatever LLRs it gets, until ldpc_decode_state_reset.  LDPC_F16 and LDPC_I8 states cannot get there: the cell saturates, S is finite.
+ *      Rule 6 holds for slots: the finite frames' results and new state do not depend on what the other slots hold.
  *   4. The tanh rule and LDPC_F64 (the parity modes): no parity with the oracle is claimed on non-finite input; 5 and 6 hold.
  *   5. Self-consistency, every context: a converged frame has H bits = 0 and bits = hard(final_lam); a frame that is not converged
  *      has iters = max_iters and bits = hard(channel LLR as taken in).
@@ -361,6 +365,48 @@ int ldpc_decode_batch_packed(ldpc_ctx *ctx, int max_iters, int batch, const void
 enum { LDPC_SOFT_POSTERIOR = 0, LDPC_SOFT_EXTRINSIC = 1 };
 int ldpc_decode_batch_dev_soft(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                                uint8_t *d_converged, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind, void *stream);
+/* A DECODE THAT CONTINUES: the check-to-variable messages of a frame kept between calls, for a receiver that comes back to a frame with new
+ * channel LLRs -- the next outer iteration of an iterative receiver (BICM-ID), the next HARQ round after combining -- or with the same ones
+ * ("a few sweeps, look at the CRC, a few more").  Served by exactly the contexts that serve ldpc_decode_batch_dev_soft, in instances of their
+ * own (ldpc::layered_csr_cont_kernel<...>, what ldpc_ctx_kernel_name reports after a continuing call; the other entry points launch what they
+ * launched).  Specification: tests/decode_continue_spec.py, reproduced bit for bit.
+ * THE STATE holds, per frame slot, the message on every edge -- as the kernel's row records {mag1, mag2, signs | arg-min}, in the geometry of
+ * the context it was made for, so it is bound to that context -- and S, the sum of the check messages per column: float32 for LDPC_F16 and
+ * LDPC_F32 cells, an integer in -254 .. 254 (int16) for LDPC_I8 cells.  Device bytes per slot: 12 nslab T + 4 N, or 8 nslab T + 2 N for
+ * LDPC_I8 (nslab T: the context's rows, each barrier step rounded up to whole workgroups); ldpc_decode_state_bytes reports the total.  A reset
+ * slot has all messages and S zero.  ldpc_decode_state_create returns a state of max_frames reset slots (NULL + LDPC_ENOMEM with the byte
+ * count in the message); destroy it BEFORE its context -- a state that outlives its context can only be destroyed: every context, one created
+ * later at the same address included, refuses it with LDPC_EINVAL, and so does a reset on the NULL stream.  ldpc_decode_state_reset zero-fills slots first .. first + count - 1: enqueued on
+ * `stream` (NULL = the context's own), not synchronised.
+ * ONE CALL, ldpc_decode_batch_dev_continue, decodes `batch` frames of channel LLRs; frame f uses slot first + f.  With C' the channel LLR as
+ * the cell takes it in (as in ldpc_decode_batch_dev_soft):
+ *   - the starting lam is fl32(C' + S) (LDPC_F32), that saturated and rounded to binary16 (LDPC_F16), clip(C' + S, -127, 127) (LDPC_I8);
+ *   - the stopping rule before the first sweep is the syndrome of hard(that lam), not of the channel's decisions: a frame that had converged
+ *     in the previous call and gets compatible LLRs stops with 0 sweeps;
+ *   - the sweeps, the stop rule after a sweep, the LDPC_F32 non-finite veto and the context's check-node rule are unchanged, but the first
+ *     sweep subtracts the stored messages;
+ *   - d_bits, d_iters, d_converged follow ldpc_decode_batch_dev_soft with C' as "the channel": a frame out of sweeps or vetoed returns hard(C')
+ *     and max_iters; the receiver's best guess is hard(P) of the soft output;
+ *   - the soft output is optional (d_soft may be NULL): P = lam as it stands when the frame stops, E = P - C', formats as above;
+ *   - the new state: S <- P - C' for every frame however it stopped, the messages as the last sweep left them (a frame that ran no sweep
+ *     keeps its messages).
+ * From a reset slot a call IS ldpc_decode_batch_dev_soft on the same LLRs, bit for bit -- except that a channel LLR of -0.0 enters as +0.0
+ * (x + (+0) is x for every x but -0).  A split decode is NOT an unsplit one: n1 sweeps and then n2 more on the same LLRs are not n1 + n2 sweeps
+ * in one call (fl(C + fl(P - C)) is not P, and the syndrome before the second call's first sweep can stop a frame that the "nothing moved" rule
+ * would have sent round once more).  Non-finite values: see rule 3a above.
+ * Ordering as ldpc_decode_batch_dev; calls on overlapping slots must be ordered by the caller.  LDPC_EINVAL -- before the device is touched --
+ * for a null state, a state made for another context, first < 0, batch < 0, first + batch above the state's frames, and every argument error
+ * of ldpc_decode_batch_dev_soft but the null d_soft.  LDPC_EUNSUPPORTED from create and from the call on a context of any other kernel
+ * family; the message names the family that serves the context and the contexts that have the call. */
+typedef struct ldpc_decode_state ldpc_decode_state;
+ldpc_decode_state *ldpc_decode_state_create(ldpc_ctx *ctx, int max_frames);
+void ldpc_decode_state_destroy(ldpc_decode_state *st);
+int ldpc_decode_state_frames(const ldpc_decode_state *st);
+size_t ldpc_decode_state_bytes(const ldpc_decode_state *st);
+int ldpc_decode_state_reset(ldpc_decode_state *st, int first, int count, void *stream);
+int ldpc_decode_batch_dev_continue(ldpc_ctx *ctx, ldpc_decode_state *st, int first, int max_iters, int batch, const void *d_llr, int llr_fmt,
+                                   uint8_t *d_bits, int32_t *d_iters, uint8_t *d_converged, void *d_soft, int soft_fmt, float soft_qscale,
+                                   int soft_kind, void *stream);
 /* page-locked host memory for the host-pointer entry points.  With llr AND bits buffers from ldpc_host_alloc (or
  * registered with hipHostRegister) ldpc_decode_batch runs zero-copy: the decode kernel itself reads the LLRs and
  * writes the bits over PCIe (10-11 Gbit/s PCIe-inclusive on jpl.4096); pageable buffers go through a chunked

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """tools/bicm_id_fer.py [--code 1920.1280.3.303] [--labels gray|nongray|FILE.npy] [--ebn0 3.5,4,4.5,5] [--outer 4] [--sweeps 10] [--frames 4096]
-[--batch 1024] [--rule maxlog|logmap] [--cell f32|f16|i8] -- the frame error rate of the iterative receiver (BICM-ID) after 1 .. R outer
-iterations, over Eb/N0.
+[--batch 1024] [--rule maxlog|logmap] [--cell f32|f16|i8] [--decoder restart|continue] -- the frame error rate of the iterative receiver
+(BICM-ID) after 1 .. R outer iterations, over Eb/N0.
+--decoder continue: the decoder keeps its check messages across the outer iterations (one ldpc_decode_state for the batch, reset once per
+batch of frames, ldpc_decode_batch_dev_continue in place of the soft call); the default, restart, is everything said below.
 
 One outer iteration: ldpc_demap_dev_il_apriori, then ldpc_decode_batch_dev_soft with the extrinsic kind and float32 output, whose output is the
 next a-priori buffer.  The first iteration's a-priori values are zeros; the decoder is restarted each time (it keeps no check-node messages
@@ -42,6 +44,7 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--rule", default="maxlog", choices=("maxlog", "logmap"))
     ap.add_argument("--cell", default="f32", choices=("f32", "f16", "i8"))
+    ap.add_argument("--decoder", default="restart", choices=("restart", "continue"))
     a = ap.parse_args()
     from tests.helpers import load
     E.init(0)
@@ -53,6 +56,7 @@ def main():
     mod = E.Modulation(labelling(a.labels)).with_rule(a.rule)
     il = E.Interleaver(np.random.default_rng(9).permutation(N).astype(np.int32), N)
     dec = E.Decoder(code, "min", a.cell, B, schedule="layered", path="fused")
+    state = E.DecodeState(dec, B) if a.decoder == "continue" else None
     n_sym = mod.symbols(N)
     sym = torch.empty((B, n_sym, 2), dtype=torch.float32, device=dev)
     llr, zeros = torch.empty((B, N), dtype=torch.float32, device=dev), torch.zeros((B, N), dtype=torch.float32, device=dev)
@@ -60,7 +64,7 @@ def main():
     bits = torch.empty((B, N), dtype=torch.uint8, device=dev)
     iters = torch.empty(B, dtype=torch.int32, device=dev)
     print(f"# {a.code} (K = {sim.k}, N = {N}), {a.labels} labels of {1 << mod.bits} points, rule {a.rule}, cells {a.cell}, {a.outer} outer iterations of {a.sweeps} sweeps, "
-          f"{a.frames} frames a point in batches of {B}", flush=True)
+          f"{a.frames} frames a point in batches of {B}" + (", the decoder continues from its state of the previous outer iteration" if state is not None else ""), flush=True)
     print("# Eb/N0 dB   " + "   ".join(f"FER after {r + 1}" for r in range(a.outer)) + "    frame errors", flush=True)
     for db in [float(x) for x in a.ebn0.split(",")]:
         nv = sim.noise_var(mod, db)
@@ -73,7 +77,12 @@ def main():
             for r in range(a.outer):
                 E.demap_il_apriori(mod, il, n, sym.data_ptr(), None, nv, la.data_ptr(), llr.data_ptr(), "f32", 0.0, None)
                 torch.cuda.synchronize()                  # (the decoder runs on the context's own stream)
-                dec.decode_batch_dev_soft(llr.data_ptr(), bits.data_ptr(), ext[r & 1].data_ptr(), n, a.sweeps, "extrinsic", "f32", 0.0, iters.data_ptr())
+                if state is None:
+                    dec.decode_batch_dev_soft(llr.data_ptr(), bits.data_ptr(), ext[r & 1].data_ptr(), n, a.sweeps, "extrinsic", "f32", 0.0, iters.data_ptr())
+                else:
+                    if r == 0:
+                        state.reset()                     # once per batch of frames (on the decoder's stream, before its first call)
+                    dec.decode_batch_dev_continue(state, llr.data_ptr(), bits.data_ptr(), n, a.sweeps, ext[r & 1].data_ptr(), "extrinsic", "f32", 0.0, iters.data_ptr())
                 dec.synchronize()
                 sim.tally(n, bits.data_ptr(), iters.data_ptr(), tally[r].data_ptr())
                 la = ext[r & 1]
@@ -81,7 +90,9 @@ def main():
         t = tally.cpu().numpy()
         assert (t[:, 0] == a.frames).all()
         print(f"{db:9.2f}   " + "   ".join(f"{t[r, 1] / t[r, 0]:11.3e}" for r in range(a.outer)) + "    " + " ".join(str(int(t[r, 1])) for r in range(a.outer)), flush=True)
-    assert "layered_csr_soft_kernel" in dec.kernel_name, dec.kernel_name
+    assert ("layered_csr_soft_kernel" if state is None else "layered_csr_cont_kernel") in dec.kernel_name, dec.kernel_name
+    if state is not None:
+        state.close()
     for o in (dec, il, mod, sim, code):
         o.close()
 

@@ -26,7 +26,9 @@ frames: the all-zero codeword + AWGN unless --codewords random, f32 LLRs generat
 
   --soft: only the cost of the soft output (ldpc_decode_batch_dev_soft): on 1920.1280.3.303, for each lam cell, the context's plain decode and
       its soft decode (posterior, extrinsic; float32 and fp16 out) on the same frames, kernel time by HIP events
-usage: python tools/layered_csr_rate.py [--frames 16384] [--reps 3] [--quick] [--lam f32|f16|both|i8 [--lam-only]] [--soft] [--asm FILE]
+  --continue: only the cost of a continuing call (ldpc_decode_batch_dev_continue) from a reset state, with and without a soft output, against the
+      soft call of the same context on the same frames, same method (profiles/r21_decode_continue.txt)
+usage: python tools/layered_csr_rate.py [--frames 16384] [--reps 3] [--quick] [--lam f32|f16|both|i8 [--lam-only]] [--soft] [--continue] [--asm FILE]
                                         [--cn-scale A [A ...]] [--cn-offset B [B ...]] [--codewords zero|random] [--codes NAME [NAME ...]]
 (profiles/r07_layered_csr_f32_rate.txt: --lam both --lam-only --reps 5; profiles/r09_layered_csr_i8_rate.txt: --lam i8 --lam-only --reps 5;
 profiles/r10_layered_rule_ber.txt: --cn-scale 0.75 0.8125 0.875 1 1 --cn-offset 0 0 0 0.25 0.5 --reps 5;
@@ -349,6 +351,53 @@ def soft_comparison(a, out):
     code.close()
 
 
+def continue_comparison(a, out):
+    """--continue: the cost of a continuing call (ldpc_decode_batch_dev_continue) from a reset state against the soft call on the same frames.
+    One context per lam cell on 1920.1280.3.303; layered_csr_soft_kernel (extrinsic, float32 out), layered_csr_cont_kernel with the same
+    output, and the latter without a soft output; the state is reset before every continuing call, outside the timed bracket; HIP events
+    around each kernel, the legs in turn inside a repetition; the median of --reps repetitions after one warm-up"""
+    from tests.helpers import load
+    c = load("1920.1280.3.303")
+    N, k, F, MI = c.N, c.k, a.frames, a.max_iters
+    code = E.Code.from_csr(c.graph.row_ptr, c.graph.col_idx, N)
+    out(f"# layered_csr continuing decode from a reset state: 1920.1280.3.303, {F} frames, {MI} sweeps at most, all-zero codewords, {a.reps} timed repetitions (median), f32 LLRs on the device")
+    legs = ("soft extrinsic f32", "continue extrinsic f32", "continue, no soft output")
+    for db in (2.0, 4.0):
+        llr = device_frames(F, N, k, db, 20)
+        bits = [torch.empty((F, N), dtype=torch.uint8, device="cuda") for _ in legs]
+        iters = [torch.empty(F, dtype=torch.int32, device="cuda") for _ in legs]
+        conv = [torch.empty(F, dtype=torch.uint8, device="cuda") for _ in legs]
+        soft = [torch.empty((F, N), dtype=torch.float32, device="cuda") for _ in range(2)]
+        for cell in ("f16", "f32", "i8"):
+            dec = E.Decoder(code, "min", cell, F, schedule="layered", path="fused")
+            state = E.DecodeState(dec, F)
+            ms = {n: [] for n in legs}
+            for rep in range(1 + a.reps):
+                for j, n in enumerate(legs):
+                    if j:
+                        state.reset()
+                        dec.synchronize()
+                    torch.cuda.synchronize()
+                    dec.set_timing(True)
+                    if j == 0:
+                        dec.decode_batch_dev_soft(llr.data_ptr(), bits[0].data_ptr(), soft[0].data_ptr(), F, MI, "extrinsic", "f32", 0.0, iters[0].data_ptr(), conv[0].data_ptr())
+                    else:
+                        dec.decode_batch_dev_continue(state, llr.data_ptr(), bits[j].data_ptr(), F, MI, soft[1].data_ptr() if j == 1 else None, "extrinsic", "f32", 0.0, iters[j].data_ptr(),
+                                                      conv[j].data_ptr())
+                    dec.synchronize()
+                    if rep:
+                        ms[n].append(dec.kernel_time()[1])
+                    else:
+                        dec.kernel_time()
+            same = bool(all(torch.equal(x[0], x[j]) for x in (bits, iters, conv) for j in (1, 2)) and torch.equal(soft[0].view(torch.int32), soft[1].view(torch.int32)))
+            base = float(np.median(ms[legs[0]]))
+            out(f"  {db} dB  cell {cell:3s}  mean sweeps {float(iters[0].float().mean()):5.2f}  " + "  ".join(f"{n} {float(np.median(v)):7.3f} ms ({float(np.median(v)) / base:4.2f}x)" for n, v in ms.items())
+                + f"   state {state.nbytes / F:.0f} B/frame  bits, sweeps, flags and soft output identical: {same}   [{dec.kernel_name}]")
+            state.close()
+            dec.close()
+    code.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16384)
@@ -364,6 +413,7 @@ def main():
     ap.add_argument("--codes", nargs="+", choices=("1920.1280.3.303", "dvbs2-short", "dvbs2-natural"),
                     help="the --lam i8 and check-node rule comparisons on these codes only (default: all of theirs)")
     ap.add_argument("--soft", action="store_true", help="only the soft-output comparison: a soft decode against the same context's plain decode")
+    ap.add_argument("--continue", dest="cont", action="store_true", help="only the continuing-decode comparison: a continuing call from a reset state against the same context's soft call")
     ap.add_argument("--asm", help="the device assembly of layered_csr.hip, where the build directory's copy is not at hand")
     a = ap.parse_args()
     if a.asm:
@@ -374,6 +424,10 @@ def main():
     out = lambda s: print(s, flush=True)   # noqa: E731
     if a.soft:
         soft_comparison(a, out)
+        E.close_all()
+        return
+    if a.cont:
+        continue_comparison(a, out)
         E.close_all()
         return
     if a.cn_scale or a.cn_offset:
