@@ -1482,21 +1482,36 @@ static int check_llr_out(const char *what, int llr_fmt, float qscale) {
     return LDPC_OK;
 }
 
+static int llr_elem(int llr_fmt) { return llr_fmt == LDPC_LLR_F32 ? 4 : llr_fmt == LDPC_LLR_F16 ? 2 : 1; }
+
+// what every demapper entry point checks after its null pointers, in the one order they all have: batch, accumulate (0 where there is
+// none), noise_var, the output format, `misaligned` (the entry point's own complaint about its buffers, null if it has none), and
+// 1 / (2 noise_var) as a float32.  Gives the kernels' two scales: inv, and qs = the int8 scale with its default
+static int demap_args(const char *what, int batch, int accumulate, double noise_var, int llr_fmt, float qscale, const char *misaligned, float &inv, float &qs) {
+    if (batch <= 0) return set_error(LDPC_EINVAL, "%s: bad dimensions (batch=%d)", what, batch);
+    if (accumulate != 0 && accumulate != 1) return set_error(LDPC_EINVAL, "%s: accumulate must be 0 or 1", what);
+    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "%s: noise_var must be finite and > 0", what);
+    const int rc = check_llr_out(what, llr_fmt, qscale);
+    if (rc != LDPC_OK) return rc;
+    if (misaligned) return set_error(LDPC_EINVAL, "%s: %s", what, misaligned);
+    inv = (float)(1.0 / (2.0 * noise_var));
+    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "%s: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", what, noise_var);
+    qs = qscale == 0.f ? 4.0f : qscale;
+    return LDPC_OK;
+}
+
 int ldpc_demap_dev(const ldpc_modulation *mod, int batch, int n_tx, int N, const float *d_sym, double noise_var, void *d_llr, int llr_fmt, float qscale, void *stream) {
     if (!mod || !d_sym || !d_llr) return set_error(LDPC_EINVAL, "ldpc_demap_dev: null argument");
     if (batch <= 0 || n_tx <= 0 || n_tx > N) return set_error(LDPC_EINVAL, "ldpc_demap_dev: bad dimensions (batch=%d n_tx=%d N=%d)", batch, n_tx, N);
-    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "ldpc_demap_dev: noise_var must be finite and > 0");
-    const int rc = check_llr_out("ldpc_demap_dev", llr_fmt, qscale);
+    const bool bad = (uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0;
+    float inv, qs;
+    const int rc = demap_args("ldpc_demap_dev", batch, 0, noise_var, llr_fmt, qscale, bad ? "samples must be 8-byte aligned and LLRs aligned to their element" : nullptr, inv, qs);
     if (rc != LDPC_OK) return rc;
-    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_llr % (llr_fmt == LDPC_LLR_F32 ? 4 : llr_fmt == LDPC_LLR_F16 ? 2 : 1) != 0)
-        return set_error(LDPC_EINVAL, "ldpc_demap_dev: samples must be 8-byte aligned and LLRs aligned to their element");
-    const float inv = (float)(1.0 / (2.0 * noise_var));
-    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
     const int device = current_device();
     if (device < 0) return set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded");
     HIPCHK(hipSetDevice(device));
-    if (mod->b) return ldpc::demap_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
-    return ldpc::demap_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    if (mod->b) return ldpc::demap_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qs);
+    return ldpc::demap_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, batch, n_tx, N, d_sym, inv, d_llr, llr_fmt, qs);
 }
 
 double ldpc_sim_noise_var(const ldpc_sim *sim, const ldpc_modulation *mod, double ebn0_db) {
@@ -1531,7 +1546,8 @@ static int sim_mod_codewords(const char *what, ldpc_sim *sim, uint64_t seed, uin
     return ldpc::pack_bits(st, sim->d_stage, sim->d_cw, batch, n_tx);
 }
 
-static int sim_mod_check(const char *what, const ldpc_sim *sim, const ldpc_modulation *mod, int batch, const void *d_msg_in, int msg_fmt, const void *d_out) {
+// fused: the entry point's kernel maps, adds noise and demaps in one; those hold the max-log rule only (include/ldpc_hip.h, THE LLR RULE)
+static int sim_mod_check(const char *what, const ldpc_sim *sim, const ldpc_modulation *mod, int batch, const void *d_msg_in, int msg_fmt, const void *d_out, bool fused = false) {
     if (!sim || !mod || !d_out) return set_error(LDPC_EINVAL, "%s: null argument", what);
     if (batch <= 0 || batch > sim->max_batch) return set_error(LDPC_EINVAL, "%s: batch %d outside 1..%d", what, batch, sim->max_batch);
     if (d_msg_in) {
@@ -1539,14 +1555,41 @@ static int sim_mod_check(const char *what, const ldpc_sim *sim, const ldpc_modul
         if (ldpc_sim_encoder(sim) == LDPC_ENCODER_NONE)
             return set_error(LDPC_EUNSUPPORTED, "%s: this frame source has no encoder (msg ++ zeros is not a codeword); create it with a generator or from H", what);
     }
+    if (fused && mod->rule != LDPC_DEMAP_MAXLOG)
+        return set_error(LDPC_EUNSUPPORTED, "%s: no fused kernel for the log-MAP rule (LDPC_DEMAP_LOGMAP); use ldpc_sim_transmit* and a demapper", what);
     return LDPC_OK;
 }
 
-// the fused map + noise + demap kernels hold the max-log rule only (include/ldpc_hip.h, THE LLR RULE)
-static int sim_mod_maxlog_only(const char *what, const ldpc_modulation *mod) {
-    if (mod->rule != LDPC_DEMAP_MAXLOG)
-        return set_error(LDPC_EUNSUPPORTED, "%s: no fused kernel for the log-MAP rule (LDPC_DEMAP_LOGMAP); use ldpc_sim_transmit* and a demapper", what);
+// the output of a fused entry point: the format, then the alignment of d_llr and of the optional gain buffer
+static int sim_mod_llr_out(const char *what, int llr_fmt, float qscale, const void *d_llr, const float *d_gain, bool has_gain, float &qs) {
+    const int rc = check_llr_out(what, llr_fmt, qscale);
+    if (rc != LDPC_OK) return rc;
+    if ((uintptr_t)d_llr % llr_elem(llr_fmt) != 0 || (uintptr_t)d_gain % 4 != 0)
+        return set_error(LDPC_EINVAL, has_gain ? "%s: LLRs must be aligned to their element, gains 4-byte aligned" : "%s: LLRs must be aligned to their element", what);
+    qs = qscale == 0.f ? 4.0f : qscale;
     return LDPC_OK;
+}
+
+// what the launchers of the modulated path take beside the entry point's own buffers
+struct SimModRun {
+    hipStream_t st;
+    int PB;          // bytes of a packed codeword row
+    float sg, inv;   // float32(sigma); float32(1 / (2 sigma^2)), for the fused kernels
+};
+
+// the back of every entry point of the modulated path, once its arguments are checked: the noise variance nv (ldpc_sim_noise_var*)
+// must be finite and >= 0, for a fused kernel (`fused`) > 0 with 1 / (2 nv) a float32; then the device, and the codewords into sim->d_cw
+static int sim_mod_run(const char *what, ldpc_sim *sim, double nv, bool fused, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg_in,
+                       int msg_fmt, uint8_t *d_msg, void *stream, SimModRun &run) {
+    if (!fused && (!(nv >= 0.0) || !std::isfinite(nv))) return set_error(LDPC_EINVAL, "%s: Eb/N0 gives no finite noise variance", what);
+    if (fused && (!(nv > 0.0) || !std::isfinite(nv))) return set_error(LDPC_EINVAL, "%s: Eb/N0 gives no finite noise variance > 0", what);
+    run.inv = (float)(1.0 / (2.0 * nv));
+    if (fused && !std::isfinite(run.inv)) return set_error(LDPC_EINVAL, "%s: 1 / (2 sigma^2) does not fit a float32 at %g dB", what, ebn0_db);
+    run.sg = (float)sqrt(nv);
+    run.st = (hipStream_t)stream;
+    run.PB = (sim->dev.n_tx + 7) / 8;
+    HIPCHK(hipSetDevice(sim->device));
+    return sim_mod_codewords(what, sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, run.st);
 }
 
 int ldpc_sim_transmit(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg_in, int msg_fmt,
@@ -1554,34 +1597,22 @@ int ldpc_sim_transmit(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, 
     int rc = sim_mod_check("ldpc_sim_transmit", sim, mod, batch, d_msg_in, msg_fmt, d_sym);
     if (rc != LDPC_OK) return rc;
     if ((uintptr_t)d_sym % 8 != 0) return set_error(LDPC_EINVAL, "ldpc_sim_transmit: samples must be 8-byte aligned");
-    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
-    if (!(nv >= 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_transmit: Eb/N0 gives no finite noise variance");
-    HIPCHK(hipSetDevice(sim->device));
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = sim_mod_codewords("ldpc_sim_transmit", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
-    if (mod->b) return ldpc::product_transmit_launch(st, mod->ax, mod->b, batch, sim->dev.n_tx, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv), d_sym);
-    return ldpc::mod_transmit_launch(st, mod->tab, mod->m, batch, sim->dev.n_tx, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv), d_sym);
+    SimModRun r;
+    if ((rc = sim_mod_run("ldpc_sim_transmit", sim, ldpc_sim_noise_var(sim, mod, ebn0_db), false, seed, first_frame, batch, ebn0_db, d_msg_in, msg_fmt, d_msg, stream, r)) != LDPC_OK) return rc;
+    if (mod->b) return ldpc::product_transmit_launch(r.st, mod->ax, mod->b, batch, sim->dev.n_tx, sim->d_cw, r.PB, seed, first_frame, r.sg, d_sym);
+    return ldpc::mod_transmit_launch(r.st, mod->tab, mod->m, batch, sim->dev.n_tx, sim->d_cw, r.PB, seed, first_frame, r.sg, d_sym);
 }
 
 int ldpc_sim_generate_mod(ldpc_sim *sim, const ldpc_modulation *mod, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db, const void *d_msg_in, int msg_fmt,
                           void *d_llr, int llr_fmt, float qscale, uint8_t *d_msg, void *stream) {
-    int rc = sim_mod_check("ldpc_sim_generate_mod", sim, mod, batch, d_msg_in, msg_fmt, d_llr);
+    int rc = sim_mod_check("ldpc_sim_generate_mod", sim, mod, batch, d_msg_in, msg_fmt, d_llr, true);
     if (rc != LDPC_OK) return rc;
-    if ((rc = sim_mod_maxlog_only("ldpc_sim_generate_mod", mod)) != LDPC_OK) return rc;
-    if ((rc = check_llr_out("ldpc_sim_generate_mod", llr_fmt, qscale)) != LDPC_OK) return rc;
-    if ((uintptr_t)d_llr % (llr_fmt == LDPC_LLR_F32 ? 4 : llr_fmt == LDPC_LLR_F16 ? 2 : 1) != 0) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod: LLRs must be aligned to their element");
-    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
-    if (!(nv > 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod: Eb/N0 gives no finite noise variance > 0");
-    const float inv = (float)(1.0 / (2.0 * nv));
-    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod: 1 / (2 sigma^2) does not fit a float32 at %g dB", ebn0_db);
-    HIPCHK(hipSetDevice(sim->device));
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = sim_mod_codewords("ldpc_sim_generate_mod", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
-    if (mod->b)
-        return ldpc::product_generate_launch(st, mod->ax, mod->b, batch, sim->dev.n_tx, sim->dev.N, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv),
-                                             inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
-    return ldpc::mod_generate_launch(st, mod->tab, mod->m, batch, sim->dev.n_tx, sim->dev.N, sim->d_cw, (sim->dev.n_tx + 7) / 8, seed, first_frame, (float)sqrt(nv),
-                                     inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    float qs;
+    if ((rc = sim_mod_llr_out("ldpc_sim_generate_mod", llr_fmt, qscale, d_llr, nullptr, false, qs)) != LDPC_OK) return rc;
+    SimModRun r;
+    if ((rc = sim_mod_run("ldpc_sim_generate_mod", sim, ldpc_sim_noise_var(sim, mod, ebn0_db), true, seed, first_frame, batch, ebn0_db, d_msg_in, msg_fmt, d_msg, stream, r)) != LDPC_OK) return rc;
+    if (mod->b) return ldpc::product_generate_launch(r.st, mod->ax, mod->b, batch, sim->dev.n_tx, sim->dev.N, sim->d_cw, r.PB, seed, first_frame, r.sg, r.inv, d_llr, llr_fmt, qs);
+    return ldpc::mod_generate_launch(r.st, mod->tab, mod->m, batch, sim->dev.n_tx, sim->dev.N, sim->d_cw, r.PB, seed, first_frame, r.sg, r.inv, d_llr, llr_fmt, qs);
 }
 
 // ---- the bit interleaver (csrc/interleaver.h): the object, the demapper and the modulated path through it, the table alone
@@ -1614,8 +1645,6 @@ void ldpc_interleaver_destroy(ldpc_interleaver *il) {
     delete il;
 }
 
-static int llr_elem(int llr_fmt) { return llr_fmt == LDPC_LLR_F32 ? 4 : llr_fmt == LDPC_LLR_F16 ? 2 : 1; }
-
 // the calling thread's device, which must be the table's
 static int il_device(const char *what, const ldpc_interleaver *il) {
     const int device = current_device();
@@ -1628,17 +1657,13 @@ static int il_device(const char *what, const ldpc_interleaver *il) {
 int ldpc_demap_dev_il(const ldpc_modulation *mod, const ldpc_interleaver *il, int batch, const float *d_sym, double noise_var, void *d_llr, int llr_fmt, float qscale,
                       void *stream) {
     if (!mod || !il || !d_sym || !d_llr) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: null argument");
-    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: bad dimensions (batch=%d)", batch);
-    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: noise_var must be finite and > 0");
-    int rc = check_llr_out("ldpc_demap_dev_il", llr_fmt, qscale);
+    const bool bad = (uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0;
+    float inv, qs;
+    int rc = demap_args("ldpc_demap_dev_il", batch, 0, noise_var, llr_fmt, qscale, bad ? "samples must be 8-byte aligned and LLRs aligned to their element" : nullptr, inv, qs);
     if (rc != LDPC_OK) return rc;
-    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0)
-        return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: samples must be 8-byte aligned and LLRs aligned to their element");
-    const float inv = (float)(1.0 / (2.0 * noise_var));
-    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
     if ((rc = il_device("ldpc_demap_dev_il", il)) != LDPC_OK) return rc;
-    if (mod->b) return ldpc::demap_il_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, il->tab, batch, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
-    return ldpc::demap_il_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, il->tab, batch, d_sym, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    if (mod->b) return ldpc::demap_il_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, il->tab, batch, d_sym, inv, d_llr, llr_fmt, qs);
+    return ldpc::demap_il_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, il->tab, batch, d_sym, inv, d_llr, llr_fmt, qs);
 }
 
 int ldpc_interleave_bits_dev(const ldpc_interleaver *il, int batch, const void *d_codewords, int cw_fmt, void *d_tx_bits, int tx_fmt, void *stream) {
@@ -1681,37 +1706,23 @@ int ldpc_sim_transmit_il(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_i
     if (rc != LDPC_OK) return rc;
     if ((rc = sim_il_check("ldpc_sim_transmit_il", sim, il)) != LDPC_OK) return rc;
     if ((uintptr_t)d_sym % 8 != 0) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il: samples must be 8-byte aligned");
-    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
-    if (!(nv >= 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il: Eb/N0 gives no finite noise variance");
-    HIPCHK(hipSetDevice(sim->device));
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = sim_mod_codewords("ldpc_sim_transmit_il", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
-    const int PB = (sim->dev.n_tx + 7) / 8;
-    if (mod->b) return ldpc::product_transmit_il_launch(st, mod->ax, mod->b, il->tab, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), d_sym);
-    return ldpc::mod_transmit_il_launch(st, mod->tab, mod->m, il->tab, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), d_sym);
+    SimModRun r;
+    if ((rc = sim_mod_run("ldpc_sim_transmit_il", sim, ldpc_sim_noise_var(sim, mod, ebn0_db), false, seed, first_frame, batch, ebn0_db, d_msg_in, msg_fmt, d_msg, stream, r)) != LDPC_OK) return rc;
+    if (mod->b) return ldpc::product_transmit_il_launch(r.st, mod->ax, mod->b, il->tab, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, d_sym);
+    return ldpc::mod_transmit_il_launch(r.st, mod->tab, mod->m, il->tab, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, d_sym);
 }
 
 int ldpc_sim_generate_mod_il(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, uint64_t seed, uint64_t first_frame, int batch, double ebn0_db,
                              const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt, float qscale, uint8_t *d_msg, void *stream) {
-    int rc = sim_mod_check("ldpc_sim_generate_mod_il", sim, mod, batch, d_msg_in, msg_fmt, d_llr);
+    int rc = sim_mod_check("ldpc_sim_generate_mod_il", sim, mod, batch, d_msg_in, msg_fmt, d_llr, true);
     if (rc != LDPC_OK) return rc;
-    if ((rc = sim_mod_maxlog_only("ldpc_sim_generate_mod_il", mod)) != LDPC_OK) return rc;
     if ((rc = sim_il_check("ldpc_sim_generate_mod_il", sim, il)) != LDPC_OK) return rc;
-    if ((rc = check_llr_out("ldpc_sim_generate_mod_il", llr_fmt, qscale)) != LDPC_OK) return rc;
-    if ((uintptr_t)d_llr % llr_elem(llr_fmt) != 0) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il: LLRs must be aligned to their element");
-    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
-    if (!(nv > 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il: Eb/N0 gives no finite noise variance > 0");
-    const float inv = (float)(1.0 / (2.0 * nv));
-    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il: 1 / (2 sigma^2) does not fit a float32 at %g dB", ebn0_db);
-    HIPCHK(hipSetDevice(sim->device));
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = sim_mod_codewords("ldpc_sim_generate_mod_il", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
-    const int PB = (sim->dev.n_tx + 7) / 8;
-    if (mod->b)
-        return ldpc::product_generate_il_launch(st, mod->ax, mod->b, il->tab, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), inv, d_llr, llr_fmt,
-                                                qscale == 0.f ? 4.0f : qscale);
-    return ldpc::mod_generate_il_launch(st, mod->tab, mod->m, il->tab, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), inv, d_llr, llr_fmt,
-                                        qscale == 0.f ? 4.0f : qscale);
+    float qs;
+    if ((rc = sim_mod_llr_out("ldpc_sim_generate_mod_il", llr_fmt, qscale, d_llr, nullptr, false, qs)) != LDPC_OK) return rc;
+    SimModRun r;
+    if ((rc = sim_mod_run("ldpc_sim_generate_mod_il", sim, ldpc_sim_noise_var(sim, mod, ebn0_db), true, seed, first_frame, batch, ebn0_db, d_msg_in, msg_fmt, d_msg, stream, r)) != LDPC_OK) return rc;
+    if (mod->b) return ldpc::product_generate_il_launch(r.st, mod->ax, mod->b, il->tab, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, r.inv, d_llr, llr_fmt, qs);
+    return ldpc::mod_generate_il_launch(r.st, mod->tab, mod->m, il->tab, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, r.inv, d_llr, llr_fmt, qs);
 }
 
 // ---- the fading channel and the per-symbol channel state (csrc/fading.h): the demapper with a gain per symbol, the modulated path
@@ -1733,17 +1744,14 @@ static int fade_arg(const char *what, const ldpc_fading *fad, ldpc::FadeArg &out
 int ldpc_demap_dev_il_csi(const ldpc_modulation *mod, const ldpc_interleaver *il, int batch, const float *d_sym, const float *d_gain, double noise_var, void *d_llr,
                           int llr_fmt, float qscale, void *stream) {
     if (!mod || !il || !d_sym || !d_gain || !d_llr) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: null argument");
-    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: bad dimensions (batch=%d)", batch);
-    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: noise_var must be finite and > 0");
-    int rc = check_llr_out("ldpc_demap_dev_il_csi", llr_fmt, qscale);
+    const bool bad = (uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0;
+    float inv, qs;
+    int rc = demap_args("ldpc_demap_dev_il_csi", batch, 0, noise_var, llr_fmt, qscale,
+                        bad ? "samples must be 8-byte aligned, gains 4-byte aligned and LLRs aligned to their element" : nullptr, inv, qs);
     if (rc != LDPC_OK) return rc;
-    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0)
-        return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: samples must be 8-byte aligned, gains 4-byte aligned and LLRs aligned to their element");
-    const float inv = (float)(1.0 / (2.0 * noise_var));
-    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
     if ((rc = il_device("ldpc_demap_dev_il_csi", il)) != LDPC_OK) return rc;
-    if (mod->b) return ldpc::demap_csi_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
-    return ldpc::demap_csi_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    if (mod->b) return ldpc::demap_csi_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qs);
+    return ldpc::demap_csi_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, il->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qs);
 }
 
 int ldpc_demap_dev_il_apriori(const ldpc_modulation *mod, const ldpc_interleaver *il, int batch, const float *d_sym, const float *d_gain, double noise_var,
@@ -1753,21 +1761,19 @@ int ldpc_demap_dev_il_apriori(const ldpc_modulation *mod, const ldpc_interleaver
     if (mod->b)
         return set_error(LDPC_EUNSUPPORTED, "ldpc_demap_dev_il_apriori: a product constellation (%d bits per axis) has no demapper with a-priori input: its Gray-like "
                          "per-axis labels gain little from iterating with the decoder; table objects (ldpc_modulation_create, m = 1..6) have one", mod->b);
-    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: bad dimensions (batch=%d)", batch);
-    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: noise_var must be finite and > 0");
-    int rc = check_llr_out("ldpc_demap_dev_il_apriori", llr_fmt, qscale);
-    if (rc != LDPC_OK) return rc;
-    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0 || (uintptr_t)d_apriori % 4 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0)
-        return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: samples must be 8-byte aligned, gains and a-priori values 4-byte aligned and LLRs aligned to their element");
-    {   // every lane reads the a-priori values of its symbol and writes its LLRs: the two buffers must not share a byte
+    const char *bad = nullptr;
+    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0 || (uintptr_t)d_apriori % 4 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0) {
+        bad = "samples must be 8-byte aligned, gains and a-priori values 4-byte aligned and LLRs aligned to their element";
+    } else if (batch > 0) {   // every lane reads the a-priori values of its symbol and writes its LLRs: the two buffers must not share a byte
         const uintptr_t a0 = (uintptr_t)d_apriori, a1 = a0 + (size_t)batch * il->N * sizeof(float);
         const uintptr_t l0 = (uintptr_t)d_llr, l1 = l0 + (size_t)batch * il->N * llr_elem(llr_fmt);
-        if (a0 < l1 && l0 < a1) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: d_apriori overlaps d_llr (no in-place operation)");
+        if (a0 < l1 && l0 < a1) bad = "d_apriori overlaps d_llr (no in-place operation)";
     }
-    const float inv = (float)(1.0 / (2.0 * noise_var));
-    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
+    float inv, qs;
+    int rc = demap_args("ldpc_demap_dev_il_apriori", batch, 0, noise_var, llr_fmt, qscale, bad, inv, qs);
+    if (rc != LDPC_OK) return rc;
     if ((rc = il_device("ldpc_demap_dev_il_apriori", il)) != LDPC_OK) return rc;
-    return ldpc::demap_apriori_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, il->tab, batch, d_sym, d_gain, d_apriori, inv, d_llr, llr_fmt, qscale == 0.f ? 4.0f : qscale);
+    return ldpc::demap_apriori_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, il->tab, batch, d_sym, d_gain, d_apriori, inv, d_llr, llr_fmt, qs);
 }
 
 int ldpc_sim_transmit_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, const ldpc_fading *fad, uint64_t seed, uint64_t first_frame, int batch,
@@ -1778,41 +1784,27 @@ int ldpc_sim_transmit_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const
     ldpc::FadeArg fa;
     if ((rc = fade_arg("ldpc_sim_transmit_il_fading", fad, fa)) != LDPC_OK) return rc;
     if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il_fading: samples must be 8-byte aligned, gains 4-byte aligned");
-    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
-    if (!(nv >= 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il_fading: Eb/N0 gives no finite noise variance");
-    HIPCHK(hipSetDevice(sim->device));
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = sim_mod_codewords("ldpc_sim_transmit_il_fading", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
-    const int PB = (sim->dev.n_tx + 7) / 8;
-    if (mod->b) return ldpc::fading_product_transmit_launch(st, mod->ax, mod->b, il->tab, fa, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), d_sym, d_gain);
-    return ldpc::fading_transmit_launch(st, mod->tab, mod->m, il->tab, fa, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), d_sym, d_gain);
+    SimModRun r;
+    if ((rc = sim_mod_run("ldpc_sim_transmit_il_fading", sim, ldpc_sim_noise_var(sim, mod, ebn0_db), false, seed, first_frame, batch, ebn0_db, d_msg_in, msg_fmt, d_msg, stream, r)) != LDPC_OK) return rc;
+    if (mod->b) return ldpc::fading_product_transmit_launch(r.st, mod->ax, mod->b, il->tab, fa, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, d_sym, d_gain);
+    return ldpc::fading_transmit_launch(r.st, mod->tab, mod->m, il->tab, fa, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, d_sym, d_gain);
 }
 
 int ldpc_sim_generate_mod_il_fading(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_interleaver *il, const ldpc_fading *fad, uint64_t seed, uint64_t first_frame,
                                     int batch, double ebn0_db, const void *d_msg_in, int msg_fmt, void *d_llr, int llr_fmt, float qscale, float *d_gain, uint8_t *d_msg,
                                     void *stream) {
-    int rc = sim_mod_check("ldpc_sim_generate_mod_il_fading", sim, mod, batch, d_msg_in, msg_fmt, d_llr);
+    int rc = sim_mod_check("ldpc_sim_generate_mod_il_fading", sim, mod, batch, d_msg_in, msg_fmt, d_llr, true);
     if (rc != LDPC_OK) return rc;
-    if ((rc = sim_mod_maxlog_only("ldpc_sim_generate_mod_il_fading", mod)) != LDPC_OK) return rc;
     if ((rc = sim_il_check("ldpc_sim_generate_mod_il_fading", sim, il)) != LDPC_OK) return rc;
     ldpc::FadeArg fa;
     if ((rc = fade_arg("ldpc_sim_generate_mod_il_fading", fad, fa)) != LDPC_OK) return rc;
-    if ((rc = check_llr_out("ldpc_sim_generate_mod_il_fading", llr_fmt, qscale)) != LDPC_OK) return rc;
-    if ((uintptr_t)d_llr % llr_elem(llr_fmt) != 0 || (uintptr_t)d_gain % 4 != 0)
-        return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il_fading: LLRs must be aligned to their element, gains 4-byte aligned");
-    const double nv = ldpc_sim_noise_var(sim, mod, ebn0_db);
-    if (!(nv > 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il_fading: Eb/N0 gives no finite noise variance > 0");
-    const float inv = (float)(1.0 / (2.0 * nv));
-    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il_fading: 1 / (2 sigma^2) does not fit a float32 at %g dB", ebn0_db);
-    HIPCHK(hipSetDevice(sim->device));
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = sim_mod_codewords("ldpc_sim_generate_mod_il_fading", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
-    const int PB = (sim->dev.n_tx + 7) / 8;
+    float qs;
+    if ((rc = sim_mod_llr_out("ldpc_sim_generate_mod_il_fading", llr_fmt, qscale, d_llr, d_gain, true, qs)) != LDPC_OK) return rc;
+    SimModRun r;
+    if ((rc = sim_mod_run("ldpc_sim_generate_mod_il_fading", sim, ldpc_sim_noise_var(sim, mod, ebn0_db), true, seed, first_frame, batch, ebn0_db, d_msg_in, msg_fmt, d_msg, stream, r)) != LDPC_OK) return rc;
     if (mod->b)
-        return ldpc::fading_product_generate_launch(st, mod->ax, mod->b, il->tab, fa, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), inv, d_llr, llr_fmt,
-                                                    qscale == 0.f ? 4.0f : qscale, d_gain);
-    return ldpc::fading_generate_launch(st, mod->tab, mod->m, il->tab, fa, batch, sim->d_cw, PB, seed, first_frame, (float)sqrt(nv), inv, d_llr, llr_fmt,
-                                        qscale == 0.f ? 4.0f : qscale, d_gain);
+        return ldpc::fading_product_generate_launch(r.st, mod->ax, mod->b, il->tab, fa, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, r.inv, d_llr, llr_fmt, qs, d_gain);
+    return ldpc::fading_generate_launch(r.st, mod->tab, mod->m, il->tab, fa, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, r.inv, d_llr, llr_fmt, qs, d_gain);
 }
 
 // ---- rate matching and HARQ (csrc/ratematch.h): the table whose entries may repeat, the demapper summing through it, the table alone,
@@ -1862,17 +1854,12 @@ static int rm_device(const char *what, const ldpc_ratematch *rm) {
 int ldpc_demap_dev_rm(const ldpc_modulation *mod, const ldpc_ratematch *rm, int batch, const float *d_sym, const float *d_gain, double noise_var, void *d_llr, int llr_fmt,
                       float qscale, int accumulate, void *stream) {
     if (!mod || !rm || !d_sym || !d_llr) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: null argument");
-    if (batch <= 0) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: bad dimensions (batch=%d)", batch);
-    if (accumulate != 0 && accumulate != 1) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: accumulate must be 0 or 1");
-    if (!(noise_var > 0.0) || !std::isfinite(noise_var)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: noise_var must be finite and > 0");
-    int rc = check_llr_out("ldpc_demap_dev_rm", llr_fmt, qscale);
+    const bool bad = (uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0;
+    float inv, qs;
+    int rc = demap_args("ldpc_demap_dev_rm", batch, accumulate, noise_var, llr_fmt, qscale,
+                        bad ? "samples must be 8-byte aligned, gains 4-byte aligned and LLRs aligned to their element" : nullptr, inv, qs);
     if (rc != LDPC_OK) return rc;
-    if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0 || (uintptr_t)d_llr % llr_elem(llr_fmt) != 0)
-        return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: samples must be 8-byte aligned, gains 4-byte aligned and LLRs aligned to their element");
-    const float inv = (float)(1.0 / (2.0 * noise_var));
-    if (!std::isfinite(inv)) return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: 1 / (2 noise_var) does not fit a float32 (noise_var %g)", noise_var);
     if ((rc = rm_device("ldpc_demap_dev_rm", rm)) != LDPC_OK) return rc;
-    const float qs = qscale == 0.f ? 4.0f : qscale;
     if (mod->b) return ldpc::demap_rm_product_launch((hipStream_t)stream, mod->ax, mod->b, mod->rule, rm->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qs, accumulate != 0);
     return ldpc::demap_rm_launch((hipStream_t)stream, mod->tab, mod->m, mod->rule, rm->tab, batch, d_sym, d_gain, inv, d_llr, llr_fmt, qs, accumulate != 0);
 }
@@ -1919,22 +1906,17 @@ int ldpc_sim_transmit_rm(ldpc_sim *sim, const ldpc_modulation *mod, const ldpc_r
     ldpc::FadeArg fa{};
     if (fad && (rc = fade_arg("ldpc_sim_transmit_rm", fad, fa)) != LDPC_OK) return rc;
     if ((uintptr_t)d_sym % 8 != 0 || (uintptr_t)d_gain % 4 != 0) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: samples must be 8-byte aligned, gains 4-byte aligned");
-    if ((size_t)batch * (size_t)rm->E > ldpc::kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: batch * E is more than one launch holds");
-    const double nv = ldpc_sim_noise_var_rm(sim, mod, rm, ebn0_db);
-    if (!(nv >= 0.0) || !std::isfinite(nv)) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: Eb/N0 gives no finite noise variance");
-    HIPCHK(hipSetDevice(sim->device));
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = sim_mod_codewords("ldpc_sim_transmit_rm", sim, seed, first_frame, batch, d_msg_in, msg_fmt, d_msg, st)) != LDPC_OK) return rc;
+    if ((size_t)batch * (size_t)rm->E > ldpc::kLaneMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_rm: batch * E is more than one launch holds");
+    SimModRun r;
+    if ((rc = sim_mod_run("ldpc_sim_transmit_rm", sim, ldpc_sim_noise_var_rm(sim, mod, rm, ebn0_db), false, seed, first_frame, batch, ebn0_db, d_msg_in, msg_fmt, d_msg, stream, r)) != LDPC_OK) return rc;
     // the interleaved path's kernels with n_tx = E: they read pos alone, through il_positions / il_label, which gather
-    const int PB = (sim->dev.n_tx + 7) / 8;
     const ldpc::IlTab il = ldpc::rm_as_il(rm->tab);
-    const float sg = (float)sqrt(nv);
     if (fad) {
-        if (mod->b) return ldpc::fading_product_transmit_launch(st, mod->ax, mod->b, il, fa, batch, sim->d_cw, PB, seed, first_frame, sg, d_sym, d_gain);
-        return ldpc::fading_transmit_launch(st, mod->tab, mod->m, il, fa, batch, sim->d_cw, PB, seed, first_frame, sg, d_sym, d_gain);
+        if (mod->b) return ldpc::fading_product_transmit_launch(r.st, mod->ax, mod->b, il, fa, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, d_sym, d_gain);
+        return ldpc::fading_transmit_launch(r.st, mod->tab, mod->m, il, fa, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, d_sym, d_gain);
     }
-    if (mod->b) return ldpc::product_transmit_il_launch(st, mod->ax, mod->b, il, batch, sim->d_cw, PB, seed, first_frame, sg, d_sym);
-    return ldpc::mod_transmit_il_launch(st, mod->tab, mod->m, il, batch, sim->d_cw, PB, seed, first_frame, sg, d_sym);
+    if (mod->b) return ldpc::product_transmit_il_launch(r.st, mod->ax, mod->b, il, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, d_sym);
+    return ldpc::mod_transmit_il_launch(r.st, mod->tab, mod->m, il, batch, sim->d_cw, r.PB, seed, first_frame, r.sg, d_sym);
 }
 
 // ---- CRC attach and check (csrc/crc.h): the object, the two kernels on messages, the check on decoded codewords, the tally

@@ -16,6 +16,9 @@ struct ModTab {
     float pt[kModMaxPoints][2];   // [label]: I, Q; entries >= 2^m are not read
 };
 enum { MOD_LLR_F32 = 0, MOD_LLR_F16 = 1, MOD_LLR_I8 = 2 };   // = LDPC_LLR_*
+// most kernels of the modulation files work ONE item a lane, with no grid-stride loop (demap_product.hip says why): their launch grid is
+// ceil(items / 256) blocks, and their launchers refuse more items than a grid of 2^32 - 1 lanes holds (mod_dispatch.h check_items)
+constexpr size_t kLaneMaxItems = 0xffffffffull - 255;
 // a product constellation (I-axis levels x Q-axis levels, label = I-label << b | Q-label) as a kernel argument: the two level tables,
 // 512 bytes as ModTab, for up to 6 bits an axis (4096 points).  Its device functions and kernels: demap_product.h, demap_product.hip,
 // sim_mod_product.hip

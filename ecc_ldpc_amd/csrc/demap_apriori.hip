@@ -18,6 +18,7 @@
 // Product objects are refused by the entry point (api.cc): their Gray-like per-axis labels gain little from iteration.
 #include "demap_product.h"
 #include "fading.h"
+#include "mod_dispatch.h"
 
 namespace ldpc {
 
@@ -115,48 +116,20 @@ __global__ __launch_bounds__(256) void demap_apriori_kernel(ModTab tab, IlTab il
     }
 }
 
-template <int M, typename OT, int RULE>
-static int demap_apriori_as(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const float *d_sym, const float *d_gain, const float *d_apriori, float inv,
-                            void *d_llr, float qs) {
-    const int n_sym = (il.n_tx + M - 1) / M, lanes = n_sym + (il.n_holes + M - 1) / M;
-    const size_t total = (size_t)batch * lanes;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((demap_apriori_kernel<M, OT, RULE>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tab, il, d_sym, d_gain, d_apriori, (OT *)d_llr, n_sym, lanes,
-                       total, inv, qs);
-    return LDPC_OK;
-}
-
-template <int M, int RULE>
-static int demap_apriori_m(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const float *d_sym, const float *d_gain, const float *d_apriori, float inv, void *d_llr,
-                           int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) return demap_apriori_as<M, int8_t, RULE>(st, tab, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, qs);
-    if (fmt == MOD_LLR_F16) return demap_apriori_as<M, __half, RULE>(st, tab, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, qs);
-    return demap_apriori_as<M, float, RULE>(st, tab, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, qs);
-}
-
-template <int RULE>
-static int demap_apriori_launch_r(hipStream_t st, const ModTab &tab, int m, const IlTab &il, int batch, const float *d_sym, const float *d_gain, const float *d_apriori,
-                                  float inv, void *d_llr, int fmt, float qscale) {
-    int rc;
-    switch (m) {
-        case 1: rc = demap_apriori_m<1, RULE>(st, tab, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, fmt, qscale); break;
-        case 2: rc = demap_apriori_m<2, RULE>(st, tab, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, fmt, qscale); break;
-        case 3: rc = demap_apriori_m<3, RULE>(st, tab, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, fmt, qscale); break;
-        case 4: rc = demap_apriori_m<4, RULE>(st, tab, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, fmt, qscale); break;
-        case 5: rc = demap_apriori_m<5, RULE>(st, tab, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, fmt, qscale); break;
-        case 6: rc = demap_apriori_m<6, RULE>(st, tab, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, fmt, qscale); break;
-        default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_apriori: %d bits per symbol", m);
-    }
-    if (rc != LDPC_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "ldpc_demap_dev_il_apriori: %s", hipGetErrorString(e));
-    return LDPC_OK;
-}
-
 int demap_apriori_launch(hipStream_t st, const ModTab &tab, int m, int rule, const IlTab &il, int batch, const float *d_sym, const float *d_gain, const float *d_apriori,
                          float inv, void *d_llr, int fmt, float qscale) {
-    if (rule == DEMAP_LOGMAP) return demap_apriori_launch_r<DEMAP_LOGMAP>(st, tab, m, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, fmt, qscale);
-    return demap_apriori_launch_r<DEMAP_MAXLOG>(st, tab, m, il, batch, d_sym, d_gain, d_apriori, inv, d_llr, fmt, qscale);
+    const char *what = "ldpc_demap_dev_il_apriori";
+    return launched(what, dispatch_rule_bits_fmt(what, rule, m, fmt, [&](auto r, auto k, auto t) {
+        constexpr int M = decltype(k)::value, RULE = decltype(r)::value;
+        typedef typename decltype(t)::type OT;
+        const int n_sym = mod_symbols(il.n_tx, M), lanes = mod_lanes(n_sym, il.n_holes, M);
+        const size_t total = (size_t)batch * lanes;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((demap_apriori_kernel<M, OT, RULE>), grid_lanes(total), dim3(256), 0, st, tab, il, d_sym, d_gain, d_apriori, (OT *)d_llr, n_sym, lanes, total, inv,
+                               qscale);
+        return rc;
+    }));
 }
 
 }  // namespace ldpc

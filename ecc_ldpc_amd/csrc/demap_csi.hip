@@ -8,11 +8,9 @@
 // The LLR rule (demap.h DEMAP_MAXLOG / DEMAP_LOGMAP) is a template argument of both kernels; the log-MAP sums use inv_s as the minima do.
 #include "demap_product.h"
 #include "fading.h"
+#include "mod_dispatch.h"
 
 namespace ldpc {
-
-// lanes per frame: the symbols, then ceil(n_holes / K) lanes of K holes each
-static int csi_lanes(int items, int n_holes, int K) { return items + (n_holes + K - 1) / K; }
 
 template <int M, typename OT, int RULE>
 __global__ __launch_bounds__(256) void demap_csi_kernel(ModTab tab, IlTab il, const float *__restrict__ sym, const float *__restrict__ gain, OT *__restrict__ llr, int n_sym,
@@ -70,90 +68,34 @@ __global__ __launch_bounds__(256) void demap_csi_product_kernel(AxisTab tab, IlT
     }
 }
 
-template <int M, typename OT, int RULE>
-static int demap_csi_as(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, float qs) {
-    const int n_sym = (il.n_tx + M - 1) / M, lanes = csi_lanes(n_sym, il.n_holes, M);
-    const size_t total = (size_t)batch * lanes;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((demap_csi_kernel<M, OT, RULE>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tab, il, d_sym, d_gain, (OT *)d_llr, n_sym, lanes, total, inv, qs);
-    return LDPC_OK;
-}
-
-template <int B, typename OT, int RULE>
-static int demap_csi_product_as(hipStream_t st, const AxisTab &tab, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, float qs) {
-    constexpr int M = 2 * B;
-    const int n_sym = (il.n_tx + M - 1) / M, lanes = csi_lanes(n_sym, il.n_holes, M);
-    const size_t total = (size_t)batch * lanes;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((demap_csi_product_kernel<B, OT, RULE>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tab, il, d_sym, d_gain, (OT *)d_llr, n_sym, lanes, total,
-                       inv, qs);
-    return LDPC_OK;
-}
-
-template <int M, int RULE>
-static int demap_csi_m(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) return demap_csi_as<M, int8_t, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, qs);
-    if (fmt == MOD_LLR_F16) return demap_csi_as<M, __half, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, qs);
-    return demap_csi_as<M, float, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, qs);
-}
-
-template <int B, int RULE>
-static int demap_csi_product_b(hipStream_t st, const AxisTab &tab, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
-                               float qs) {
-    if (fmt == MOD_LLR_I8) return demap_csi_product_as<B, int8_t, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, qs);
-    if (fmt == MOD_LLR_F16) return demap_csi_product_as<B, __half, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, qs);
-    return demap_csi_product_as<B, float, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, qs);
-}
-
-static int csi_launched(int rc) {
-    if (rc != LDPC_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "ldpc_demap_dev_il_csi: %s", hipGetErrorString(e));
-    return LDPC_OK;
-}
-
-template <int RULE>
-static int demap_csi_launch_r(hipStream_t st, const ModTab &tab, int m, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
-                              float qscale) {
-    int rc;
-    switch (m) {
-        case 1: rc = demap_csi_m<1, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        case 2: rc = demap_csi_m<2, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        case 3: rc = demap_csi_m<3, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        case 4: rc = demap_csi_m<4, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        case 5: rc = demap_csi_m<5, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        case 6: rc = demap_csi_m<6, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: %d bits per symbol", m);
-    }
-    return csi_launched(rc);
-}
-
-template <int RULE>
-static int demap_csi_product_launch_r(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr,
-                                      int fmt, float qscale) {
-    int rc;
-    switch (b) {
-        case 1: rc = demap_csi_product_b<1, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        case 2: rc = demap_csi_product_b<2, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        case 3: rc = demap_csi_product_b<3, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        case 4: rc = demap_csi_product_b<4, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        case 5: rc = demap_csi_product_b<5, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        case 6: rc = demap_csi_product_b<6, RULE>(st, tab, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale); break;
-        default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_il_csi: %d bits per axis", b);
-    }
-    return csi_launched(rc);
-}
-
 int demap_csi_launch(hipStream_t st, const ModTab &tab, int m, int rule, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
                      float qscale) {
-    if (rule == DEMAP_LOGMAP) return demap_csi_launch_r<DEMAP_LOGMAP>(st, tab, m, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale);
-    return demap_csi_launch_r<DEMAP_MAXLOG>(st, tab, m, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale);
+    const char *what = "ldpc_demap_dev_il_csi";
+    return launched(what, dispatch_rule_bits_fmt(what, rule, m, fmt, [&](auto r, auto k, auto t) {
+        constexpr int M = decltype(k)::value, RULE = decltype(r)::value;
+        typedef typename decltype(t)::type OT;
+        const int n_sym = mod_symbols(il.n_tx, M), lanes = mod_lanes(n_sym, il.n_holes, M);
+        const size_t total = (size_t)batch * lanes;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((demap_csi_kernel<M, OT, RULE>), grid_lanes(total), dim3(256), 0, st, tab, il, d_sym, d_gain, (OT *)d_llr, n_sym, lanes, total, inv, qscale);
+        return rc;
+    }));
 }
 
 int demap_csi_product_launch(hipStream_t st, const AxisTab &tab, int b, int rule, const IlTab &il, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr,
                              int fmt, float qscale) {
-    if (rule == DEMAP_LOGMAP) return demap_csi_product_launch_r<DEMAP_LOGMAP>(st, tab, b, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale);
-    return demap_csi_product_launch_r<DEMAP_MAXLOG>(st, tab, b, il, batch, d_sym, d_gain, inv, d_llr, fmt, qscale);
+    const char *what = "ldpc_demap_dev_il_csi";
+    return launched(what, dispatch_rule_bits_fmt(what, rule, b, fmt, [&](auto r, auto k, auto t) {
+        constexpr int B = decltype(k)::value, M = 2 * B, RULE = decltype(r)::value;
+        typedef typename decltype(t)::type OT;
+        const int n_sym = mod_symbols(il.n_tx, M), lanes = mod_lanes(n_sym, il.n_holes, M);
+        const size_t total = (size_t)batch * lanes;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((demap_csi_product_kernel<B, OT, RULE>), grid_lanes(total), dim3(256), 0, st, tab, il, d_sym, d_gain, (OT *)d_llr, n_sym, lanes, total, inv, qscale);
+        return rc;
+    }));
 }
 
 }  // namespace ldpc

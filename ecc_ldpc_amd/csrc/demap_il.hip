@@ -11,12 +11,9 @@
 // The LLR rule (demap.h DEMAP_MAXLOG / DEMAP_LOGMAP) is a template argument of the two demapper kernels.
 #include "demap_product.h"
 #include "interleaver.h"
-#include <algorithm>
+#include "mod_dispatch.h"
 
 namespace ldpc {
-
-// lanes per frame: the symbols, then ceil(n_holes / K) lanes of K holes each
-static int il_lanes(int items, int n_holes, int K) { return items + (n_holes + K - 1) / K; }
 
 template <int M, typename OT, int RULE>
 __global__ __launch_bounds__(256) void demap_il_kernel(ModTab tab, IlTab il, const float *__restrict__ sym, OT *__restrict__ llr, int n_sym, int lanes, size_t total,
@@ -71,85 +68,30 @@ __global__ __launch_bounds__(256) void demap_il_product_kernel(AxisTab tab, IlTa
     }
 }
 
-template <int M, typename OT, int RULE>
-static int demap_il_as(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, float qs) {
-    const int n_sym = (il.n_tx + M - 1) / M, lanes = il_lanes(n_sym, il.n_holes, M);
-    const size_t total = (size_t)batch * lanes;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((demap_il_kernel<M, OT, RULE>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tab, il, d_sym, (OT *)d_llr, n_sym, lanes, total, inv, qs);
-    return LDPC_OK;
-}
-
-template <int B, typename OT, int RULE>
-static int demap_il_product_as(hipStream_t st, const AxisTab &tab, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, float qs) {
-    constexpr int M = 2 * B;
-    const int n_sym = (il.n_tx + M - 1) / M, lanes = il_lanes(n_sym, il.n_holes, M);
-    const size_t total = (size_t)batch * lanes;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((demap_il_product_kernel<B, OT, RULE>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tab, il, d_sym, (OT *)d_llr, n_sym, lanes, total, inv,
-                       qs);
-    return LDPC_OK;
-}
-
-template <int M, int RULE>
-static int demap_il_m(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) return demap_il_as<M, int8_t, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
-    if (fmt == MOD_LLR_F16) return demap_il_as<M, __half, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
-    return demap_il_as<M, float, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
-}
-
-template <int B, int RULE>
-static int demap_il_product_b(hipStream_t st, const AxisTab &tab, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) return demap_il_product_as<B, int8_t, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
-    if (fmt == MOD_LLR_F16) return demap_il_product_as<B, __half, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
-    return demap_il_product_as<B, float, RULE>(st, tab, il, batch, d_sym, inv, d_llr, qs);
-}
-
-static int il_launched(const char *what, int rc) {
-    if (rc != LDPC_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "%s: %s", what, hipGetErrorString(e));
-    return LDPC_OK;
-}
-
-template <int RULE>
-static int demap_il_launch_r(hipStream_t st, const ModTab &tab, int m, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
-    int rc;
-    switch (m) {
-        case 1: rc = demap_il_m<1, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 2: rc = demap_il_m<2, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 3: rc = demap_il_m<3, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 4: rc = demap_il_m<4, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 5: rc = demap_il_m<5, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 6: rc = demap_il_m<6, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: %d bits per symbol", m);
-    }
-    return il_launched("ldpc_demap_dev_il", rc);
-}
-
-template <int RULE>
-static int demap_il_product_launch_r(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
-    int rc;
-    switch (b) {
-        case 1: rc = demap_il_product_b<1, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 2: rc = demap_il_product_b<2, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 3: rc = demap_il_product_b<3, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 4: rc = demap_il_product_b<4, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 5: rc = demap_il_product_b<5, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        case 6: rc = demap_il_product_b<6, RULE>(st, tab, il, batch, d_sym, inv, d_llr, fmt, qscale); break;
-        default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_il: %d bits per axis", b);
-    }
-    return il_launched("ldpc_demap_dev_il", rc);
-}
-
 int demap_il_launch(hipStream_t st, const ModTab &tab, int m, int rule, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
-    if (rule == DEMAP_LOGMAP) return demap_il_launch_r<DEMAP_LOGMAP>(st, tab, m, il, batch, d_sym, inv, d_llr, fmt, qscale);
-    return demap_il_launch_r<DEMAP_MAXLOG>(st, tab, m, il, batch, d_sym, inv, d_llr, fmt, qscale);
+    const char *what = "ldpc_demap_dev_il";
+    return launched(what, dispatch_rule_bits_fmt(what, rule, m, fmt, [&](auto r, auto k, auto t) {
+        constexpr int M = decltype(k)::value, RULE = decltype(r)::value;
+        typedef typename decltype(t)::type OT;
+        const int n_sym = mod_symbols(il.n_tx, M), lanes = mod_lanes(n_sym, il.n_holes, M);
+        const size_t total = (size_t)batch * lanes;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK) hipLaunchKernelGGL((demap_il_kernel<M, OT, RULE>), grid_lanes(total), dim3(256), 0, st, tab, il, d_sym, (OT *)d_llr, n_sym, lanes, total, inv, qscale);
+        return rc;
+    }));
 }
 
 int demap_il_product_launch(hipStream_t st, const AxisTab &tab, int b, int rule, const IlTab &il, int batch, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
-    if (rule == DEMAP_LOGMAP) return demap_il_product_launch_r<DEMAP_LOGMAP>(st, tab, b, il, batch, d_sym, inv, d_llr, fmt, qscale);
-    return demap_il_product_launch_r<DEMAP_MAXLOG>(st, tab, b, il, batch, d_sym, inv, d_llr, fmt, qscale);
+    const char *what = "ldpc_demap_dev_il";
+    return launched(what, dispatch_rule_bits_fmt(what, rule, b, fmt, [&](auto r, auto k, auto t) {
+        constexpr int B = decltype(k)::value, M = 2 * B, RULE = decltype(r)::value;
+        typedef typename decltype(t)::type OT;
+        const int n_sym = mod_symbols(il.n_tx, M), lanes = mod_lanes(n_sym, il.n_holes, M);
+        const size_t total = (size_t)batch * lanes;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK) hipLaunchKernelGGL((demap_il_product_kernel<B, OT, RULE>), grid_lanes(total), dim3(256), 0, st, tab, il, d_sym, (OT *)d_llr, n_sym, lanes, total, inv, qscale);
+        return rc;
+    }));
 }
 
 // ---- the table alone
@@ -191,26 +133,24 @@ __global__ __launch_bounds__(256) void deinterleave_kernel(IlTab il, const T *__
     }
 }
 
-static unsigned il_grid(size_t total) { return (unsigned)std::min<size_t>((total + 255) / 256, (size_t)1 << 20); }
-
 int interleave_bits_launch(hipStream_t st, const IlTab &il, int batch, const uint8_t *d_in, bool in_packed, uint8_t *d_out, bool out_packed) {
     const int in_row = in_packed ? (il.N + 7) / 8 : il.N, out_row = out_packed ? (il.n_tx + 7) / 8 : il.n_tx;
     const size_t total = (size_t)batch * out_row;
-    const dim3 grid(il_grid(total));
+    const dim3 grid = grid_stride(total);
     if (in_packed && out_packed) hipLaunchKernelGGL((interleave_bits_kernel<true, true>), grid, dim3(256), 0, st, il, d_in, d_out, in_row, out_row, total);
     else if (in_packed) hipLaunchKernelGGL((interleave_bits_kernel<true, false>), grid, dim3(256), 0, st, il, d_in, d_out, in_row, out_row, total);
     else if (out_packed) hipLaunchKernelGGL((interleave_bits_kernel<false, true>), grid, dim3(256), 0, st, il, d_in, d_out, in_row, out_row, total);
     else hipLaunchKernelGGL((interleave_bits_kernel<false, false>), grid, dim3(256), 0, st, il, d_in, d_out, in_row, out_row, total);
-    return il_launched("ldpc_interleave_bits_dev", LDPC_OK);
+    return launched("ldpc_interleave_bits_dev");
 }
 
 int deinterleave_llr_launch(hipStream_t st, const IlTab &il, int batch, const void *d_in, void *d_out, int elem) {
     const size_t total = (size_t)batch * il.N;
-    const dim3 grid(il_grid(total));
+    const dim3 grid = grid_stride(total);
     if (elem == 4) hipLaunchKernelGGL((deinterleave_kernel<uint32_t>), grid, dim3(256), 0, st, il, (const uint32_t *)d_in, (uint32_t *)d_out, total);
     else if (elem == 2) hipLaunchKernelGGL((deinterleave_kernel<uint16_t>), grid, dim3(256), 0, st, il, (const uint16_t *)d_in, (uint16_t *)d_out, total);
     else hipLaunchKernelGGL((deinterleave_kernel<uint8_t>), grid, dim3(256), 0, st, il, (const uint8_t *)d_in, (uint8_t *)d_out, total);
-    return il_launched("ldpc_deinterleave_llr_dev", LDPC_OK);
+    return launched("ldpc_deinterleave_llr_dev");
 }
 
 }  // namespace ldpc

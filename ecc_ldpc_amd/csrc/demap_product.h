@@ -9,10 +9,6 @@
 #ifdef __HIPCC__
 namespace ldpc {
 
-// the kernels of product constellations work ONE item a lane, with no grid-stride loop (demap_product.hip says why): the launch grid is
-// ceil(items / 256) blocks, and the launchers refuse more items than a grid of 2^32 - 1 lanes holds
-constexpr size_t kProductMaxItems = 0xffffffffull - 255;
-
 // level of a per-lane axis label: a binary select tree over the uniform table (2^B - 1 selects), label bit 0 first, as mod_point
 template <int B>
 __device__ __forceinline__ float axis_level(const float (&lev)[kAxisMaxLevels], uint32_t idx) {
@@ -131,6 +127,9 @@ __device__ __forceinline__ void axis_llrs_by(const float (&lev)[kAxisMaxLevels],
     if constexpr (RULE == DEMAP_LOGMAP) axis_llrs_logmap<B>(lev, y, inv, llr);
     else axis_llrs<B>(lev, y, inv, llr);
 }
+
+// (The kernels that hold more than one sample work AXIS-MAJOR, in a loop of two turns that is not unrolled -- sim_mod_product.hip says
+// why.  That loop has no helper here on purpose: as a device function every kernel that has one compiled to other code)
 
 // store_slot's rule for any even M: a slot's M sizeof(OT) bytes go out in the largest 16 / 8 / 4-byte pieces that divide them
 // (0: no such piece -- int8 with M = 2, 6, 10)

@@ -3,6 +3,7 @@
 // dispatch by rule) and demap_product_logmap.hip.  What the kernel does and why it has no grid-stride loop: demap_product.hip.
 #pragma once
 #include "demap_product.h"
+#include "mod_dispatch.h"
 
 namespace ldpc {
 
@@ -30,46 +31,29 @@ __global__ __launch_bounds__(256) void demap_product_kernel(AxisTab tab, const f
     }
 }
 
-template <int B, typename OT, int RULE>
-static void demap_product_as(hipStream_t st, const AxisTab &tab, int batch, int n_tx, int N, const float *d_sym, float inv, void *d_llr, float qs) {
-    constexpr int M = 2 * B;
-    const int n_sym = (n_tx + M - 1) / M, slots = (N + M - 1) / M;
-    const size_t total = (size_t)batch * slots;
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if constexpr (kSlotPiece<M, OT> != 0) {
-        if (N % M == 0 && (uintptr_t)d_llr % kSlotPiece<M, OT> == 0) {
-            hipLaunchKernelGGL((demap_product_kernel<B, OT, true, RULE>), grid, dim3(256), 0, st, tab, d_sym, (OT *)d_llr, n_tx, N, n_sym, slots, total, inv, qs);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((demap_product_kernel<B, OT, false, RULE>), grid, dim3(256), 0, st, tab, d_sym, (OT *)d_llr, n_tx, N, n_sym, slots, total, inv, qs);
-}
-
-template <int B, int RULE>
-static void demap_product_b(hipStream_t st, const AxisTab &tab, int batch, int n_tx, int N, const float *d_sym, float inv, void *d_llr, int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) demap_product_as<B, int8_t, RULE>(st, tab, batch, n_tx, N, d_sym, inv, d_llr, qs);
-    else if (fmt == MOD_LLR_F16) demap_product_as<B, __half, RULE>(st, tab, batch, n_tx, N, d_sym, inv, d_llr, qs);
-    else demap_product_as<B, float, RULE>(st, tab, batch, n_tx, N, d_sym, inv, d_llr, qs);
-}
-
+// the instances of one rule: each of the two translation units calls this with its own
 template <int RULE>
 static int demap_product_launch_r(hipStream_t st, const AxisTab &tab, int b, int batch, int n_tx, int N, const float *d_sym, float inv, void *d_llr, int fmt, float qscale) {
-    if ((size_t)batch * (size_t)N > kProductMaxItems) return set_error(LDPC_EINVAL, "demap: batch * N = %zu is more than one launch holds", (size_t)batch * (size_t)N);
-    switch (b) {
-        case 1: demap_product_b<1, RULE>(st, tab, batch, n_tx, N, d_sym, inv, d_llr, fmt, qscale); break;
-        case 2: demap_product_b<2, RULE>(st, tab, batch, n_tx, N, d_sym, inv, d_llr, fmt, qscale); break;
-        case 3: demap_product_b<3, RULE>(st, tab, batch, n_tx, N, d_sym, inv, d_llr, fmt, qscale); break;
-        case 4: demap_product_b<4, RULE>(st, tab, batch, n_tx, N, d_sym, inv, d_llr, fmt, qscale); break;
-        case 5: demap_product_b<5, RULE>(st, tab, batch, n_tx, N, d_sym, inv, d_llr, fmt, qscale); break;
-        case 6: demap_product_b<6, RULE>(st, tab, batch, n_tx, N, d_sym, inv, d_llr, fmt, qscale); break;
-        default: return set_error(LDPC_EINVAL, "demap: %d bits per axis", b);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "demap: %s", hipGetErrorString(e));
-    return LDPC_OK;
+    const int rc = check_items("demap", (size_t)batch * (size_t)N, "batch * N");
+    if (rc != LDPC_OK) return rc;
+    return launched("demap", dispatch_bits_fmt("demap", b, fmt, [&](auto k, auto t) {
+        constexpr int B = decltype(k)::value, M = 2 * B;
+        typedef typename decltype(t)::type OT;
+        const int n_sym = mod_symbols(n_tx, M), slots = mod_symbols(N, M);
+        const size_t total = (size_t)batch * slots;
+        if constexpr (kSlotPiece<M, OT> != 0) {
+            if (grant_slot_store(N, M, d_llr, kSlotPiece<M, OT>)) {
+                hipLaunchKernelGGL((demap_product_kernel<B, OT, true, RULE>), grid_lanes(total), dim3(256), 0, st, tab, d_sym, (OT *)d_llr, n_tx, N, n_sym, slots, total, inv, qscale);
+                return LDPC_OK;
+            }
+        }
+        hipLaunchKernelGGL((demap_product_kernel<B, OT, false, RULE>), grid_lanes(total), dim3(256), 0, st, tab, d_sym, (OT *)d_llr, n_tx, N, n_sym, slots, total, inv, qscale);
+        return LDPC_OK;
+    }));
 }
 
 // the log-MAP instances (demap_product_logmap.hip)
 int demap_product_logmap_launch(hipStream_t st, const AxisTab &tab, int b, int batch, int n_tx, int N, const float *d_sym, float inv, void *d_llr, int fmt, float qscale);
 
 }  // namespace ldpc
+

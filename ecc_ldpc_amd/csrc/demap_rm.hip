@@ -24,8 +24,8 @@
 // exponentials of the bit's two subsets, 2^m (2^b) a bit; the value then enters the sum and the store exactly as a max-log one.
 #include "demap_product.h"
 #include "fading.h"
+#include "mod_dispatch.h"
 #include "ratematch.h"
-#include <algorithm>
 
 namespace ldpc {
 
@@ -185,69 +185,34 @@ __global__ __launch_bounds__(256) void rm_gather_kernel(RULE rule, RmTab rm, OT 
 
 template <class RULE>
 static int rm_launch(const char *what, hipStream_t st, const RULE &rule, const RmTab &rm, int batch, void *d_llr, int fmt, float qs, bool acc) {
-    const size_t total = (size_t)batch * (size_t)rm.N, widest = (size_t)batch * (size_t)std::max(rm.E, rm.N);
-    if (widest > kIlMaxItems) return set_error(LDPC_EINVAL, "%s: %zu items are more than one launch holds", what, widest);
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (fmt == MOD_LLR_I8) hipLaunchKernelGGL((rm_gather_kernel<RULE, int8_t>), grid, dim3(256), 0, st, rule, rm, (int8_t *)d_llr, total, qs, (int)acc);
-    else if (fmt == MOD_LLR_F16) hipLaunchKernelGGL((rm_gather_kernel<RULE, __half>), grid, dim3(256), 0, st, rule, rm, (__half *)d_llr, total, qs, (int)acc);
-    else hipLaunchKernelGGL((rm_gather_kernel<RULE, float>), grid, dim3(256), 0, st, rule, rm, (float *)d_llr, total, qs, (int)acc);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "%s: %s", what, hipGetErrorString(e));
-    return LDPC_OK;
-}
-
-template <int M, int RULE>
-static int demap_rm_m(hipStream_t st, const ModTab &tab, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt, float qs,
-                      bool acc) {
-    const RmTableRule<M, RULE> rule{tab, d_sym, d_gain, (rm.E + M - 1) / M, inv};
-    return rm_launch("ldpc_demap_dev_rm", st, rule, rm, batch, d_llr, fmt, qs, acc);
-}
-
-template <int B, int RULE>
-static int demap_rm_b(hipStream_t st, const AxisTab &tab, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt, float qs,
-                      bool acc) {
-    const RmProductRule<B, RULE> rule{tab, d_sym, d_gain, (rm.E + 2 * B - 1) / (2 * B), inv};
-    return rm_launch("ldpc_demap_dev_rm", st, rule, rm, batch, d_llr, fmt, qs, acc);
-}
-
-template <int RULE>
-static int demap_rm_launch_r(hipStream_t st, const ModTab &tab, int m, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
-                             float qscale, bool accumulate) {
-    switch (m) {
-        case 1: return demap_rm_m<1, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 2: return demap_rm_m<2, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 3: return demap_rm_m<3, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 4: return demap_rm_m<4, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 5: return demap_rm_m<5, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 6: return demap_rm_m<6, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: %d bits per symbol", m);
-    }
-}
-
-template <int RULE>
-static int demap_rm_product_launch_r(hipStream_t st, const AxisTab &tab, int b, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr,
-                                     int fmt, float qscale, bool accumulate) {
-    switch (b) {
-        case 1: return demap_rm_b<1, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 2: return demap_rm_b<2, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 3: return demap_rm_b<3, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 4: return demap_rm_b<4, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 5: return demap_rm_b<5, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        case 6: return demap_rm_b<6, RULE>(st, tab, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-        default: return set_error(LDPC_EINVAL, "ldpc_demap_dev_rm: %d bits per axis", b);
-    }
+    const size_t total = (size_t)batch * (size_t)rm.N;
+    const int rc = check_items(what, (size_t)batch * (size_t)std::max(rm.E, rm.N));
+    if (rc != LDPC_OK) return rc;
+    return launched(what, dispatch_fmt(fmt, [&](auto t) {
+        typedef typename decltype(t)::type OT;
+        hipLaunchKernelGGL((rm_gather_kernel<RULE, OT>), grid_lanes(total), dim3(256), 0, st, rule, rm, (OT *)d_llr, total, qs, (int)acc);
+        return LDPC_OK;
+    }));
 }
 
 int demap_rm_launch(hipStream_t st, const ModTab &tab, int m, int rule, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr, int fmt,
                     float qscale, bool accumulate) {
-    if (rule == DEMAP_LOGMAP) return demap_rm_launch_r<DEMAP_LOGMAP>(st, tab, m, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-    return demap_rm_launch_r<DEMAP_MAXLOG>(st, tab, m, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+    const char *what = "ldpc_demap_dev_rm";
+    return dispatch_rule(rule, [&](auto r) { return dispatch_bits(what, m, [&](auto k) {
+        constexpr int M = decltype(k)::value;
+        const RmTableRule<M, decltype(r)::value> lane{tab, d_sym, d_gain, mod_symbols(rm.E, M), inv};
+        return rm_launch(what, st, lane, rm, batch, d_llr, fmt, qscale, accumulate);
+    }); });
 }
 
 int demap_rm_product_launch(hipStream_t st, const AxisTab &tab, int b, int rule, const RmTab &rm, int batch, const float *d_sym, const float *d_gain, float inv, void *d_llr,
                             int fmt, float qscale, bool accumulate) {
-    if (rule == DEMAP_LOGMAP) return demap_rm_product_launch_r<DEMAP_LOGMAP>(st, tab, b, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
-    return demap_rm_product_launch_r<DEMAP_MAXLOG>(st, tab, b, rm, batch, d_sym, d_gain, inv, d_llr, fmt, qscale, accumulate);
+    const char *what = "ldpc_demap_dev_rm";
+    return dispatch_rule(rule, [&](auto r) { return dispatch_bits(what, b, [&](auto k) {
+        constexpr int B = decltype(k)::value;
+        const RmProductRule<B, decltype(r)::value> lane{tab, d_sym, d_gain, mod_symbols(rm.E, 2 * B), inv};
+        return rm_launch(what, st, lane, rm, batch, d_llr, fmt, qscale, accumulate);
+    }); });
 }
 
 int ratematch_llr_launch(hipStream_t st, const RmTab &rm, int batch, const float *d_llr_tx, void *d_llr, int fmt, float qscale, bool accumulate) {

@@ -40,10 +40,6 @@ int product_transmit_il_launch(hipStream_t st, const AxisTab &tab, int b, const 
 int product_generate_il_launch(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
                                float sg, float inv, void *d_llr, int fmt, float qscale);
 
-// the kernels below work ONE item a lane, with no grid-stride loop (demap_product.hip says why): the launchers refuse more items than a
-// grid of 2^32 - 1 lanes holds
-constexpr size_t kIlMaxItems = 0xffffffffull - 255;
-
 #ifdef __HIPCC__
 // the M table entries of a symbol from src = pos + M s (transmitted bits M s .. M s + M - 1), in the largest 16 / 8 / 4-byte loads that
 // divide 4 M bytes: the table is 16-byte aligned, so entry M s is aligned to that piece.  Reads up to entry M s + M - 1 <= n_tx + kIlPad - 1
@@ -67,6 +63,17 @@ __device__ __forceinline__ void il_positions(const int32_t *__restrict__ src, in
 #pragma unroll
         for (int j = 0; j < M; j++) p[j] = src[j];
     }
+}
+
+// the same of the symbol PAIR g of the frame source's kernels: src = pos + M 2g, rem = n_tx - M 2g (> 0).  Symbol 2g + 1 is at src + M
+// with rem - M, which is <= 0 from n_sym on (the second of the last pair when n_sym is odd): such a symbol has no entries, none are
+// loaded and none looked at
+template <int M>
+__device__ __forceinline__ void il_pair_positions(const int32_t *__restrict__ src, int rem, int32_t (&p0)[M], int32_t (&p1)[M]) {
+    il_positions<M>(src, p0);
+#pragma unroll
+    for (int j = 0; j < M; j++) p1[j] = 0;
+    if (rem > M) il_positions<M>(src + M, p1);
 }
 
 // the LLRs of a symbol go to their codeword positions; those of pad bits (j >= rem) are not written

@@ -20,7 +20,7 @@ struct RmTab {
 };
 
 // E + kIlPad table entries are indexed with an int, so E may be no larger than this; the launchers, which work ONE item a lane, further
-// refuse batch * max(E, N) above kIlMaxItems
+// refuse batch * max(E, N) above kLaneMaxItems
 constexpr int kRmMaxE = 0x7fffffff - kIlPad;
 
 // pos [E] maps into 0 .. N - 1, 1 <= E <= kRmMaxE, N >= 1: LDPC_OK, or LDPC_EINVAL

@@ -5,13 +5,10 @@
 // normals of the pair (sim_noise.h box_muller4, the BPSK source's own): (z0, z1) -> I, Q of symbol 2g, (z2, z3) -> I, Q of 2g + 1.
 // The symbol rule and the LLR rule are the device functions of demap.h, the ones demap_kernel calls: the fused kernel equals
 // transmit + ldpc_demap_dev bit for bit, the sample never leaves its registers.
-#include "demap.h"
+#include "mod_dispatch.h"
 #include "sim_noise.h"
-#include <algorithm>
 
 namespace ldpc {
-
-static unsigned mod_grid(size_t total) { return (unsigned)std::min<size_t>((total + 255) / 256, (size_t)1 << 20); }
 
 // the two noisy symbols of pair g of frame f; a symbol from n_sym on (the second of the last pair when n_sym is odd) is not made
 template <int M>
@@ -66,68 +63,36 @@ __global__ __launch_bounds__(256) void mod_generate_kernel(ModTab tab, const uin
     }
 }
 
-template <int M>
-static void transmit_m(hipStream_t st, const ModTab &tab, int batch, int n_tx, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg, float *d_sym) {
-    const int n_sym = (n_tx + M - 1) / M, pairs = (n_sym + 1) / 2;
-    const size_t total = (size_t)batch * pairs;
-    const int vec4 = (n_sym % 2 == 0) && ((uintptr_t)d_sym % 16 == 0);
-    hipLaunchKernelGGL((mod_transmit_kernel<M>), dim3(mod_grid(total)), dim3(256), 0, st, tab, d_cw, PB, d_sym, n_sym, pairs, total, seed, first_frame, sg, vec4);
-}
-
-template <int M, typename OT>
-static void generate_as(hipStream_t st, const ModTab &tab, int batch, int n_tx, int N, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg, float inv,
-                        void *d_llr, float qs) {
-    const int n_sym = (n_tx + M - 1) / M, slots = (N + M - 1) / M, pslots = (slots + 1) / 2;
-    const size_t total = (size_t)batch * pslots;
-    const dim3 grid(mod_grid(total));
-    if constexpr (kDemapVec<M, OT>) {
-        if (N % M == 0 && (uintptr_t)d_llr % (M * sizeof(OT)) == 0) {
-            hipLaunchKernelGGL((mod_generate_kernel<M, OT, true>), grid, dim3(256), 0, st, tab, d_cw, PB, (OT *)d_llr, n_tx, N, n_sym, slots, pslots, total, seed, first_frame,
-                               sg, inv, qs);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((mod_generate_kernel<M, OT, false>), grid, dim3(256), 0, st, tab, d_cw, PB, (OT *)d_llr, n_tx, N, n_sym, slots, pslots, total, seed, first_frame, sg,
-                       inv, qs);
-}
-
-template <int M>
-static void generate_m(hipStream_t st, const ModTab &tab, int batch, int n_tx, int N, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg, float inv,
-                       void *d_llr, int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) generate_as<M, int8_t>(st, tab, batch, n_tx, N, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-    else if (fmt == MOD_LLR_F16) generate_as<M, __half>(st, tab, batch, n_tx, N, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-    else generate_as<M, float>(st, tab, batch, n_tx, N, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-}
-
-#define LDPC_MOD_SWITCH(m_, CALL)                                          \
-    switch (m_) {                                                          \
-        case 1: CALL(1); break;                                            \
-        case 2: CALL(2); break;                                            \
-        case 3: CALL(3); break;                                            \
-        case 4: CALL(4); break;                                            \
-        case 5: CALL(5); break;                                            \
-        case 6: CALL(6); break;                                            \
-        default: return set_error(LDPC_EINVAL, "modulation: %d bits per symbol", m_); \
-    }
-
 int mod_transmit_launch(hipStream_t st, const ModTab &tab, int m, int batch, int n_tx, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
                         float *d_sym) {
-#define LDPC_MOD_T(M_) transmit_m<M_>(st, tab, batch, n_tx, d_cw, PB, seed, first_frame, sg, d_sym)
-    LDPC_MOD_SWITCH(m, LDPC_MOD_T)
-#undef LDPC_MOD_T
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "ldpc_sim_transmit: %s", hipGetErrorString(e));
-    return LDPC_OK;
+    return launched("ldpc_sim_transmit", dispatch_bits("modulation", m, [&](auto k) {
+        constexpr int M = decltype(k)::value;
+        const int n_sym = mod_symbols(n_tx, M), pairs = mod_pairs(n_sym);
+        const size_t total = (size_t)batch * pairs;
+        hipLaunchKernelGGL((mod_transmit_kernel<M>), grid_stride(total), dim3(256), 0, st, tab, d_cw, PB, d_sym, n_sym, pairs, total, seed, first_frame, sg,
+                           grant_pair_store(n_sym, d_sym, 16));
+        return LDPC_OK;
+    }));
 }
 
 int mod_generate_launch(hipStream_t st, const ModTab &tab, int m, int batch, int n_tx, int N, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
                         float inv, void *d_llr, int fmt, float qscale) {
-#define LDPC_MOD_G(M_) generate_m<M_>(st, tab, batch, n_tx, N, d_cw, PB, seed, first_frame, sg, inv, d_llr, fmt, qscale)
-    LDPC_MOD_SWITCH(m, LDPC_MOD_G)
-#undef LDPC_MOD_G
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "ldpc_sim_generate_mod: %s", hipGetErrorString(e));
-    return LDPC_OK;
+    return launched("ldpc_sim_generate_mod", dispatch_bits_fmt("modulation", m, fmt, [&](auto k, auto t) {
+        constexpr int M = decltype(k)::value;
+        typedef typename decltype(t)::type OT;
+        const int n_sym = mod_symbols(n_tx, M), slots = mod_symbols(N, M), pslots = mod_pairs(slots);
+        const size_t total = (size_t)batch * pslots;
+        if constexpr (kDemapVec<M, OT>) {
+            if (grant_slot_store(N, M, d_llr, M * sizeof(OT))) {
+                hipLaunchKernelGGL((mod_generate_kernel<M, OT, true>), grid_stride(total), dim3(256), 0, st, tab, d_cw, PB, (OT *)d_llr, n_tx, N, n_sym, slots, pslots, total, seed,
+                                   first_frame, sg, inv, qscale);
+                return LDPC_OK;
+            }
+        }
+        hipLaunchKernelGGL((mod_generate_kernel<M, OT, false>), grid_stride(total), dim3(256), 0, st, tab, d_cw, PB, (OT *)d_llr, n_tx, N, n_sym, slots, pslots, total, seed,
+                           first_frame, sg, inv, qscale);
+        return LDPC_OK;
+    }));
 }
 
 }  // namespace ldpc

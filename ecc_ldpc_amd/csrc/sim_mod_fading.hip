@@ -9,22 +9,11 @@
 // bit.  A non-null d_gain [batch][n_sym] receives the gains.  The rule is restated in tests/fading_spec.py.
 // The gains are drawn, turned into the four per-lane scales and stored FIRST, so the descriptor and the gain pointer are dead before
 // the distances are live.  ONE ITEM A LANE, no grid-stride loop (demap_product.hip says why).
-#include "demap_product.h"
 #include "fading.h"
+#include "mod_dispatch.h"
+#include "sim_mod_pair.h"
 
 namespace ldpc {
-
-static unsigned fade_grid(size_t total) { return (unsigned)((total + 255) / 256); }
-
-// pair g's place in the table, as sim_mod_il.hip il_pair_positions: src = pos + M 2g, rem = n_tx - M 2g (> 0); symbol 2g + 1 has
-// rem - M bits, <= 0 from n_sym on: no entries are loaded for it
-template <int M>
-__device__ __forceinline__ void fade_pair_positions(const int32_t *__restrict__ src, int rem, int32_t (&p0)[M], int32_t (&p1)[M]) {
-    il_positions<M>(src, p0);
-#pragma unroll
-    for (int j = 0; j < M; j++) p1[j] = 0;
-    if (rem > M) il_positions<M>(src + M, p1);
-}
 
 // the gains of pair g of frame f, stored where the caller wants them (vec2: n_sym even and an 8-byte aligned buffer), and the per-symbol
 // sigma of the channel.  `second`: symbol 2g + 1 exists
@@ -43,28 +32,6 @@ __device__ __forceinline__ void fade_pair(const FadeArg &fad, uint64_t seed, uin
     sg1 = fade_sigma(sg, a1);
 }
 
-// the two noisy symbols of pair g, as sim_mod_il.hip mod_pair_il with a sigma per symbol
-template <int M>
-__device__ __forceinline__ void fade_mod_pair(const ModTab &tab, const uint8_t *__restrict__ row, const int32_t (&p0)[M], const int32_t (&p1)[M], int g, int rem,
-                                              uint64_t seed, uint64_t frame, float sg0, float sg1, float (&y)[4]) {
-    uint32_t r[4];
-    float z[4];
-    Philox::gen(seed, frame, (uint32_t)g, 2u, r);
-    box_muller4(r, z);
-    mod_symbol<M>(tab, il_label<M>(row, p0, rem), z[0], z[1], sg0, y[0], y[1]);
-    y[2] = 0.f; y[3] = 0.f;
-    if (rem > M) mod_symbol<M>(tab, il_label<M>(row, p1, rem - M), z[2], z[3], sg1, y[2], y[3]);
-}
-
-__device__ __forceinline__ void fade_store_pair(float *__restrict__ dst, const float (&y)[4], bool second, int vec4) {
-    if (vec4) {
-        *reinterpret_cast<float4 *>(dst) = make_float4(y[0], y[1], y[2], y[3]);
-    } else {
-        *reinterpret_cast<float2 *>(dst) = make_float2(y[0], y[1]);
-        if (second) *reinterpret_cast<float2 *>(dst + 2) = make_float2(y[2], y[3]);
-    }
-}
-
 // vec4: n_sym even and a 16-byte aligned sample buffer; vec2: n_sym even and an 8-byte aligned gain buffer
 template <int M>
 __global__ __launch_bounds__(256) void fading_transmit_kernel(ModTab tab, IlTab il, FadeArg fad, const uint8_t *__restrict__ cw, int PB, float *__restrict__ sym,
@@ -79,9 +46,9 @@ __global__ __launch_bounds__(256) void fading_transmit_kernel(ModTab tab, IlTab 
         fade_pair(fad, seed, first_frame + f, g, rem > M, sg, gain ? gain + f * (size_t)n_sym : nullptr, vec2, a0, a1, sg0, sg1);
         int32_t p0[M], p1[M];
         float y[4];
-        fade_pair_positions<M>(il.pos + (size_t)(2 * M) * g, rem, p0, p1);
-        fade_mod_pair<M>(tab, cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, sg0, sg1, y);
-        fade_store_pair(sym + 2 * (f * (size_t)n_sym + 2 * (size_t)g), y, rem > M, vec4);
+        il_pair_positions<M>(il.pos + (size_t)(2 * M) * g, rem, p0, p1);
+        mod_pair_il<M>(tab, cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, sg0, sg1, y);
+        store_pair_il<M>(sym + 2 * (f * (size_t)n_sym + 2 * (size_t)g), y, rem, vec4);
     }
 }
 
@@ -101,8 +68,8 @@ __global__ __launch_bounds__(256) void fading_generate_kernel(ModTab tab, IlTab 
             fade_pair(fad, seed, first_frame + f, g, rem > M, sg, gain ? gain + f * (size_t)n_sym : nullptr, vec2, a0, a1, sg0, sg1);
             int32_t p0[M], p1[M];
             float y[4], v[M];
-            fade_pair_positions<M>(il.pos + (size_t)(2 * M) * g, rem, p0, p1);
-            fade_mod_pair<M>(tab, cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, sg0, sg1, y);
+            il_pair_positions<M>(il.pos + (size_t)(2 * M) * g, rem, p0, p1);
+            mod_pair_il<M>(tab, cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, sg0, sg1, y);
             demap_llrs<M>(tab, y[0], y[1], fade_inv(inv, a0), v);
             il_store<M, OT>(row, p0, rem, v, qs);
             if (rem > M) {
@@ -118,16 +85,6 @@ __global__ __launch_bounds__(256) void fading_generate_kernel(ModTab tab, IlTab 
 // ---- product constellations: sim_mod_il.hip's product kernels, AXIS-MAJOR in a loop of two turns that is NOT unrolled, with the
 // per-symbol sigma and LLR scale in four per-lane registers
 template <int B>
-__device__ __forceinline__ void fade_product_draw(const uint8_t *__restrict__ row, const int32_t (&p0)[2 * B], const int32_t (&p1)[2 * B], int g, int rem, uint64_t seed,
-                                                  uint64_t frame, uint32_t (&label)[2], float (&z)[4]) {
-    uint32_t r[4];
-    Philox::gen(seed, frame, (uint32_t)g, 2u, r);
-    box_muller4(r, z);
-    label[0] = il_label<2 * B>(row, p0, rem);
-    label[1] = il_label<2 * B>(row, p1, rem - 2 * B);        // 0 for a symbol from n_sym on; what is computed for it is never stored
-}
-
-template <int B>
 __global__ __launch_bounds__(256) void fading_product_transmit_kernel(AxisTab tab, IlTab il, FadeArg fad, const uint8_t *__restrict__ cw, int PB, float *__restrict__ sym,
                                                                       float *__restrict__ gain, int n_sym, int pairs, size_t total, uint64_t seed, uint64_t first_frame,
                                                                       float sg, int vec4, int vec2) {
@@ -142,8 +99,8 @@ __global__ __launch_bounds__(256) void fading_product_transmit_kernel(AxisTab ta
         int32_t p0[M], p1[M];
         uint32_t label[2];
         float z[4], y[4];
-        fade_pair_positions<M>(il.pos + (size_t)(2 * M) * g, rem, p0, p1);
-        fade_product_draw<B>(cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, label, z);
+        il_pair_positions<M>(il.pos + (size_t)(2 * M) * g, rem, p0, p1);
+        product_pair_draw_il<B>(cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, label, z);
 #pragma unroll 1
         for (int a = 0; a < 2; a++) {
             const float (&lev)[kAxisMaxLevels] = tab.lev[a];
@@ -151,7 +108,7 @@ __global__ __launch_bounds__(256) void fading_product_transmit_kernel(AxisTab ta
             const float y1 = axis_symbol<B>(lev, axis_index<B>(label[1], a), a ? z[3] : z[2], sg1);
             if (a) { y[1] = y0; y[3] = y1; } else { y[0] = y0; y[2] = y1; }
         }
-        fade_store_pair(sym + 2 * (f * (size_t)n_sym + 2 * (size_t)g), y, rem > M, vec4);
+        store_pair_il<M>(sym + 2 * (f * (size_t)n_sym + 2 * (size_t)g), y, rem, vec4);
     }
 }
 
@@ -174,8 +131,8 @@ __global__ __launch_bounds__(256) void fading_product_generate_kernel(AxisTab ta
             int32_t p0[M], p1[M];
             uint32_t label[2];
             float z[4], v0[M], v1[M];
-            fade_pair_positions<M>(src, rem, p0, p1);
-            fade_product_draw<B>(cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, label, z);
+            il_pair_positions<M>(src, rem, p0, p1);
+            product_pair_draw_il<B>(cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, label, z);
             // the 2 M entries are loaded again for the stores below and not kept in registers across the axis loop, as
             // product_generate_il_kernel: the compiler barrier keeps the two loads apart
             __asm__ volatile("" ::: "memory");
@@ -193,7 +150,7 @@ __global__ __launch_bounds__(256) void fading_product_generate_kernel(AxisTab ta
             const int32_t *src2 = src;
             int rem2 = rem;
             __asm__ volatile("" : "+v"(src2), "+v"(rem2) : : "memory");
-            fade_pair_positions<M>(src2, rem2, p0, p1);
+            il_pair_positions<M>(src2, rem2, p0, p1);
             il_store<M, OT>(row, p0, rem2, v0, qs);
             il_store<M, OT>(row, p1, rem2 - M, v1, qs);      // (nothing for a symbol from n_sym on: rem - M <= 0)
         } else {
@@ -202,125 +159,68 @@ __global__ __launch_bounds__(256) void fading_product_generate_kernel(AxisTab ta
     }
 }
 
-// ---- launchers
-struct FadeGeom {
-    int n_sym, pairs, vec4, vec2;
-};
-
-static FadeGeom fade_geom(int n_tx, int M, const float *d_sym, const float *d_gain) {
-    FadeGeom q;
-    q.n_sym = (n_tx + M - 1) / M;
-    q.pairs = (q.n_sym + 1) / 2;
-    q.vec4 = (q.n_sym % 2 == 0) && ((uintptr_t)d_sym % 16 == 0);
-    q.vec2 = (q.n_sym % 2 == 0) && ((uintptr_t)d_gain % 8 == 0);
-    return q;
-}
-
-template <int M>
-static int fading_transmit_m(hipStream_t st, const ModTab &tab, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
-                             float sg, float *d_sym, float *d_gain) {
-    const FadeGeom q = fade_geom(il.n_tx, M, d_sym, d_gain);
-    const size_t total = (size_t)batch * q.pairs;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il_fading: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((fading_transmit_kernel<M>), dim3(fade_grid(total)), dim3(256), 0, st, tab, il, fad, d_cw, PB, d_sym, d_gain, q.n_sym, q.pairs, total, seed, first_frame,
-                       sg, q.vec4, q.vec2);
-    return LDPC_OK;
-}
-
-template <int B>
-static int fading_transmit_b(hipStream_t st, const AxisTab &tab, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
-                             float sg, float *d_sym, float *d_gain) {
-    const FadeGeom q = fade_geom(il.n_tx, 2 * B, d_sym, d_gain);
-    const size_t total = (size_t)batch * q.pairs;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il_fading: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((fading_product_transmit_kernel<B>), dim3(fade_grid(total)), dim3(256), 0, st, tab, il, fad, d_cw, PB, d_sym, d_gain, q.n_sym, q.pairs, total, seed,
-                       first_frame, sg, q.vec4, q.vec2);
-    return LDPC_OK;
-}
-
-template <int M, typename OT>
-static int fading_generate_as(hipStream_t st, const ModTab &tab, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
-                              float sg, float inv, void *d_llr, float qs, float *d_gain) {
-    const FadeGeom q = fade_geom(il.n_tx, M, nullptr, d_gain);
-    const int lanes = q.pairs + (il.n_holes + 2 * M - 1) / (2 * M);
-    const size_t total = (size_t)batch * lanes;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il_fading: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((fading_generate_kernel<M, OT>), dim3(fade_grid(total)), dim3(256), 0, st, tab, il, fad, d_cw, PB, (OT *)d_llr, d_gain, q.n_sym, q.pairs, lanes, total,
-                       seed, first_frame, sg, inv, qs, q.vec2);
-    return LDPC_OK;
-}
-
-template <int B, typename OT>
-static int fading_generate_product_as(hipStream_t st, const AxisTab &tab, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed,
-                                      uint64_t first_frame, float sg, float inv, void *d_llr, float qs, float *d_gain) {
-    constexpr int M = 2 * B;
-    const FadeGeom q = fade_geom(il.n_tx, M, nullptr, d_gain);
-    const int lanes = q.pairs + (il.n_holes + 2 * M - 1) / (2 * M);
-    const size_t total = (size_t)batch * lanes;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il_fading: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((fading_product_generate_kernel<B, OT>), dim3(fade_grid(total)), dim3(256), 0, st, tab, il, fad, d_cw, PB, (OT *)d_llr, d_gain, q.n_sym, q.pairs, lanes,
-                       total, seed, first_frame, sg, inv, qs, q.vec2);
-    return LDPC_OK;
-}
-
-template <int M>
-static int fading_generate_m(hipStream_t st, const ModTab &tab, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
-                             float sg, float inv, void *d_llr, int fmt, float qs, float *d_gain) {
-    if (fmt == MOD_LLR_I8) return fading_generate_as<M, int8_t>(st, tab, il, fad, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs, d_gain);
-    if (fmt == MOD_LLR_F16) return fading_generate_as<M, __half>(st, tab, il, fad, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs, d_gain);
-    return fading_generate_as<M, float>(st, tab, il, fad, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs, d_gain);
-}
-
-template <int B>
-static int fading_generate_b(hipStream_t st, const AxisTab &tab, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
-                             float sg, float inv, void *d_llr, int fmt, float qs, float *d_gain) {
-    if (fmt == MOD_LLR_I8) return fading_generate_product_as<B, int8_t>(st, tab, il, fad, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs, d_gain);
-    if (fmt == MOD_LLR_F16) return fading_generate_product_as<B, __half>(st, tab, il, fad, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs, d_gain);
-    return fading_generate_product_as<B, float>(st, tab, il, fad, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs, d_gain);
-}
-
-#define LDPC_FADE_SWITCH(n_, what_, CALL)                                  \
-    int rc;                                                                \
-    switch (n_) {                                                          \
-        case 1: rc = CALL(1); break;                                       \
-        case 2: rc = CALL(2); break;                                       \
-        case 3: rc = CALL(3); break;                                       \
-        case 4: rc = CALL(4); break;                                       \
-        case 5: rc = CALL(5); break;                                       \
-        case 6: rc = CALL(6); break;                                       \
-        default: return set_error(LDPC_EINVAL, "%s: %d bits per symbol or axis", what_, n_); \
-    }                                                                      \
-    if (rc != LDPC_OK) return rc;                                          \
-    hipError_t e = hipGetLastError();                                      \
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "%s: %s", what_, hipGetErrorString(e)); \
-    return LDPC_OK;
-
+// ---- launchers.  transmit: pairs lanes per frame; generate: pairs + ceil(n_holes / 2M).  vec4: n_sym even and a 16-byte aligned sample
+// buffer; vec2: n_sym even and an 8-byte aligned gain buffer (a null one is)
 int fading_transmit_launch(hipStream_t st, const ModTab &tab, int m, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed,
                            uint64_t first_frame, float sg, float *d_sym, float *d_gain) {
-#define LDPC_FADE_T(M_) fading_transmit_m<M_>(st, tab, il, fad, batch, d_cw, PB, seed, first_frame, sg, d_sym, d_gain)
-    LDPC_FADE_SWITCH(m, "ldpc_sim_transmit_il_fading", LDPC_FADE_T)
-#undef LDPC_FADE_T
-}
-
-int fading_generate_launch(hipStream_t st, const ModTab &tab, int m, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed,
-                           uint64_t first_frame, float sg, float inv, void *d_llr, int fmt, float qscale, float *d_gain) {
-#define LDPC_FADE_G(M_) fading_generate_m<M_>(st, tab, il, fad, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, fmt, qscale, d_gain)
-    LDPC_FADE_SWITCH(m, "ldpc_sim_generate_mod_il_fading", LDPC_FADE_G)
-#undef LDPC_FADE_G
+    const char *what = "ldpc_sim_transmit_il_fading";
+    return launched(what, dispatch_bits(what, m, [&](auto k) {
+        constexpr int M = decltype(k)::value;
+        const int n_sym = mod_symbols(il.n_tx, M), pairs = mod_pairs(n_sym);
+        const size_t total = (size_t)batch * pairs;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((fading_transmit_kernel<M>), grid_lanes(total), dim3(256), 0, st, tab, il, fad, d_cw, PB, d_sym, d_gain, n_sym, pairs, total, seed, first_frame, sg,
+                               grant_pair_store(n_sym, d_sym, 16), grant_pair_store(n_sym, d_gain, 8));
+        return rc;
+    }));
 }
 
 int fading_product_transmit_launch(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed,
                                    uint64_t first_frame, float sg, float *d_sym, float *d_gain) {
-#define LDPC_FADE_T(B_) fading_transmit_b<B_>(st, tab, il, fad, batch, d_cw, PB, seed, first_frame, sg, d_sym, d_gain)
-    LDPC_FADE_SWITCH(b, "ldpc_sim_transmit_il_fading", LDPC_FADE_T)
-#undef LDPC_FADE_T
+    const char *what = "ldpc_sim_transmit_il_fading";
+    return launched(what, dispatch_bits(what, b, [&](auto k) {
+        constexpr int B = decltype(k)::value;
+        const int n_sym = mod_symbols(il.n_tx, 2 * B), pairs = mod_pairs(n_sym);
+        const size_t total = (size_t)batch * pairs;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((fading_product_transmit_kernel<B>), grid_lanes(total), dim3(256), 0, st, tab, il, fad, d_cw, PB, d_sym, d_gain, n_sym, pairs, total, seed,
+                               first_frame, sg, grant_pair_store(n_sym, d_sym, 16), grant_pair_store(n_sym, d_gain, 8));
+        return rc;
+    }));
+}
+
+int fading_generate_launch(hipStream_t st, const ModTab &tab, int m, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed,
+                           uint64_t first_frame, float sg, float inv, void *d_llr, int fmt, float qscale, float *d_gain) {
+    const char *what = "ldpc_sim_generate_mod_il_fading";
+    return launched(what, dispatch_bits_fmt(what, m, fmt, [&](auto k, auto t) {
+        constexpr int M = decltype(k)::value;
+        typedef typename decltype(t)::type OT;
+        const int n_sym = mod_symbols(il.n_tx, M), pairs = mod_pairs(n_sym), lanes = mod_lanes(pairs, il.n_holes, 2 * M);
+        const size_t total = (size_t)batch * lanes;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((fading_generate_kernel<M, OT>), grid_lanes(total), dim3(256), 0, st, tab, il, fad, d_cw, PB, (OT *)d_llr, d_gain, n_sym, pairs, lanes, total, seed,
+                               first_frame, sg, inv, qscale, grant_pair_store(n_sym, d_gain, 8));
+        return rc;
+    }));
 }
 
 int fading_product_generate_launch(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, const FadeArg &fad, int batch, const uint8_t *d_cw, int PB, uint64_t seed,
                                    uint64_t first_frame, float sg, float inv, void *d_llr, int fmt, float qscale, float *d_gain) {
-#define LDPC_FADE_G(B_) fading_generate_b<B_>(st, tab, il, fad, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, fmt, qscale, d_gain)
-    LDPC_FADE_SWITCH(b, "ldpc_sim_generate_mod_il_fading", LDPC_FADE_G)
-#undef LDPC_FADE_G
+    const char *what = "ldpc_sim_generate_mod_il_fading";
+    return launched(what, dispatch_bits_fmt(what, b, fmt, [&](auto k, auto t) {
+        constexpr int B = decltype(k)::value, M = 2 * B;
+        typedef typename decltype(t)::type OT;
+        const int n_sym = mod_symbols(il.n_tx, M), pairs = mod_pairs(n_sym), lanes = mod_lanes(pairs, il.n_holes, 2 * M);
+        const size_t total = (size_t)batch * lanes;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((fading_product_generate_kernel<B, OT>), grid_lanes(total), dim3(256), 0, st, tab, il, fad, d_cw, PB, (OT *)d_llr, d_gain, n_sym, pairs, lanes, total,
+                               seed, first_frame, sg, inv, qscale, grant_pair_store(n_sym, d_gain, 8));
+        return rc;
+    }));
 }
 
 }  // namespace ldpc

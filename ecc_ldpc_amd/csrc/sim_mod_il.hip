@@ -9,38 +9,11 @@
 // table kernels keep the entries for the LLR stores; the fused product kernel loads them a second time after its axis loop (a cache hit)
 // so that they are not live next to the 2^b distances.  In generate_mod_il the lanes from ceil(n_sym / 2) on take the hole list, 2 m
 // holes a lane.  ONE ITEM A LANE, no grid-stride loop (demap_product.hip says why).
-#include "demap_product.h"
-#include "interleaver.h"
-#include "sim_noise.h"
+#include "mod_dispatch.h"
+#include "sim_mod_pair.h"
 
 namespace ldpc {
 
-static unsigned il_grid1(size_t total) { return (unsigned)((total + 255) / 256); }
-
-// pair g's place in the table: src = pos + M 2g, rem = n_tx - M 2g (> 0).  Symbol 2g + 1 is at src + M with rem - M, which is <= 0 from
-// n_sym on (the second of the last pair when n_sym is odd): such a symbol has no entries, none are loaded and none looked at
-template <int M>
-__device__ __forceinline__ void il_pair_positions(const int32_t *__restrict__ src, int rem, int32_t (&p0)[M], int32_t (&p1)[M]) {
-    il_positions<M>(src, p0);
-#pragma unroll
-    for (int j = 0; j < M; j++) p1[j] = 0;
-    if (rem > M) il_positions<M>(src + M, p1);
-}
-
-// the two noisy symbols of pair g of frame f, as sim_mod.hip mod_pair with the labels gathered; a symbol from n_sym on is not made
-template <int M>
-__device__ __forceinline__ void mod_pair_il(const ModTab &tab, const uint8_t *__restrict__ row, const int32_t (&p0)[M], const int32_t (&p1)[M], int g, int rem,
-                                            uint64_t seed, uint64_t frame, float sg, float (&y)[4]) {
-    uint32_t r[4];
-    float z[4];
-    Philox::gen(seed, frame, (uint32_t)g, 2u, r);
-    box_muller4(r, z);
-    mod_symbol<M>(tab, il_label<M>(row, p0, rem), z[0], z[1], sg, y[0], y[1]);
-    y[2] = 0.f; y[3] = 0.f;
-    if (rem > M) mod_symbol<M>(tab, il_label<M>(row, p1, rem - M), z[2], z[3], sg, y[2], y[3]);
-}
-
-// vec4: n_sym even and a 16-byte aligned buffer -- every pair is whole and starts on a 16-byte boundary
 template <int M>
 __global__ __launch_bounds__(256) void mod_transmit_il_kernel(ModTab tab, IlTab il, const uint8_t *__restrict__ cw, int PB, float *__restrict__ sym, int n_sym, int pairs,
                                                               size_t total, uint64_t seed, uint64_t first_frame, float sg, int vec4) {
@@ -52,14 +25,8 @@ __global__ __launch_bounds__(256) void mod_transmit_il_kernel(ModTab tab, IlTab 
         int32_t p0[M], p1[M];
         float y[4];
         il_pair_positions<M>(il.pos + (size_t)(2 * M) * g, rem, p0, p1);
-        mod_pair_il<M>(tab, cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, sg, y);
-        float *dst = sym + 2 * (f * (size_t)n_sym + 2 * (size_t)g);
-        if (vec4) {
-            *reinterpret_cast<float4 *>(dst) = make_float4(y[0], y[1], y[2], y[3]);
-        } else {
-            *reinterpret_cast<float2 *>(dst) = make_float2(y[0], y[1]);
-            if (rem > M) *reinterpret_cast<float2 *>(dst + 2) = make_float2(y[2], y[3]);
-        }
+        mod_pair_il<M>(tab, cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, sg, sg, y);
+        store_pair_il<M>(sym + 2 * (f * (size_t)n_sym + 2 * (size_t)g), y, rem, vec4);
     }
 }
 
@@ -77,7 +44,7 @@ __global__ __launch_bounds__(256) void mod_generate_il_kernel(ModTab tab, IlTab 
             int32_t p0[M], p1[M];
             float y[4], v[M];
             il_pair_positions<M>(il.pos + (size_t)(2 * M) * g, rem, p0, p1);
-            mod_pair_il<M>(tab, cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, sg, y);
+            mod_pair_il<M>(tab, cw + f * (size_t)PB, p0, p1, g, rem, seed, first_frame + f, sg, sg, y);
             demap_llrs<M>(tab, y[0], y[1], inv, v);
             il_store<M, OT>(row, p0, rem, v, qs);
             if (rem > M) {
@@ -92,16 +59,6 @@ __global__ __launch_bounds__(256) void mod_generate_il_kernel(ModTab tab, IlTab 
 
 // ---- product constellations: sim_mod_product.hip's kernels, AXIS-MAJOR in a loop of two turns that is NOT unrolled (2^B levels in
 // scalar registers at a time), with the labels gathered and the LLRs stored through the table
-template <int B>
-__device__ __forceinline__ void product_pair_draw_il(const uint8_t *__restrict__ row, const int32_t (&p0)[2 * B], const int32_t (&p1)[2 * B], int g, int rem,
-                                                     uint64_t seed, uint64_t frame, uint32_t (&label)[2], float (&z)[4]) {
-    uint32_t r[4];
-    Philox::gen(seed, frame, (uint32_t)g, 2u, r);
-    box_muller4(r, z);
-    label[0] = il_label<2 * B>(row, p0, rem);
-    label[1] = il_label<2 * B>(row, p1, rem - 2 * B);        // 0 for a symbol from n_sym on; what is computed for it is never stored
-}
-
 template <int B>
 __global__ __launch_bounds__(256) void product_transmit_il_kernel(AxisTab tab, IlTab il, const uint8_t *__restrict__ cw, int PB, float *__restrict__ sym, int n_sym,
                                                                   int pairs, size_t total, uint64_t seed, uint64_t first_frame, float sg, int vec4) {
@@ -123,7 +80,7 @@ __global__ __launch_bounds__(256) void product_transmit_il_kernel(AxisTab tab, I
             const float y1 = axis_symbol<B>(lev, axis_index<B>(label[1], a), a ? z[3] : z[2], sg);
             if (a) { y[1] = y0; y[3] = y1; } else { y[0] = y0; y[2] = y1; }
         }
-        float *dst = sym + 2 * (f * (size_t)n_sym + 2 * (size_t)g);
+        float *dst = sym + 2 * (f * (size_t)n_sym + 2 * (size_t)g);      // (not store_pair_il: through it this kernel compiles to other code)
         if (vec4) {
             *reinterpret_cast<float4 *>(dst) = make_float4(y[0], y[1], y[2], y[3]);
         } else {
@@ -176,110 +133,67 @@ __global__ __launch_bounds__(256) void product_generate_il_kernel(AxisTab tab, I
     }
 }
 
-// ---- launchers
-template <int M>
-static int transmit_il_m(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg, float *d_sym) {
-    const int n_sym = (il.n_tx + M - 1) / M, pairs = (n_sym + 1) / 2;
-    const size_t total = (size_t)batch * pairs;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il: %zu items are more than one launch holds", total);
-    const int vec4 = (n_sym % 2 == 0) && ((uintptr_t)d_sym % 16 == 0);
-    hipLaunchKernelGGL((mod_transmit_il_kernel<M>), dim3(il_grid1(total)), dim3(256), 0, st, tab, il, d_cw, PB, d_sym, n_sym, pairs, total, seed, first_frame, sg, vec4);
-    return LDPC_OK;
-}
-
-template <int B>
-static int transmit_il_b(hipStream_t st, const AxisTab &tab, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
-                         float *d_sym) {
-    constexpr int M = 2 * B;
-    const int n_sym = (il.n_tx + M - 1) / M, pairs = (n_sym + 1) / 2;
-    const size_t total = (size_t)batch * pairs;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_transmit_il: %zu items are more than one launch holds", total);
-    const int vec4 = (n_sym % 2 == 0) && ((uintptr_t)d_sym % 16 == 0);
-    hipLaunchKernelGGL((product_transmit_il_kernel<B>), dim3(il_grid1(total)), dim3(256), 0, st, tab, il, d_cw, PB, d_sym, n_sym, pairs, total, seed, first_frame, sg, vec4);
-    return LDPC_OK;
-}
-
-template <int M, typename OT>
-static int generate_il_as(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg, float inv,
-                          void *d_llr, float qs) {
-    const int n_sym = (il.n_tx + M - 1) / M, pairs = (n_sym + 1) / 2, lanes = pairs + (il.n_holes + 2 * M - 1) / (2 * M);
-    const size_t total = (size_t)batch * lanes;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((mod_generate_il_kernel<M, OT>), dim3(il_grid1(total)), dim3(256), 0, st, tab, il, d_cw, PB, (OT *)d_llr, pairs, lanes, total, seed, first_frame, sg,
-                       inv, qs);
-    return LDPC_OK;
-}
-
-template <int B, typename OT>
-static int generate_il_product_as(hipStream_t st, const AxisTab &tab, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
-                                  float inv, void *d_llr, float qs) {
-    constexpr int M = 2 * B;
-    const int n_sym = (il.n_tx + M - 1) / M, pairs = (n_sym + 1) / 2, lanes = pairs + (il.n_holes + 2 * M - 1) / (2 * M);
-    const size_t total = (size_t)batch * lanes;
-    if (total > kIlMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod_il: %zu items are more than one launch holds", total);
-    hipLaunchKernelGGL((product_generate_il_kernel<B, OT>), dim3(il_grid1(total)), dim3(256), 0, st, tab, il, d_cw, PB, (OT *)d_llr, pairs, lanes, total, seed, first_frame, sg,
-                       inv, qs);
-    return LDPC_OK;
-}
-
-template <int M>
-static int generate_il_m(hipStream_t st, const ModTab &tab, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg, float inv,
-                         void *d_llr, int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) return generate_il_as<M, int8_t>(st, tab, il, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-    if (fmt == MOD_LLR_F16) return generate_il_as<M, __half>(st, tab, il, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-    return generate_il_as<M, float>(st, tab, il, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-}
-
-template <int B>
-static int generate_il_b(hipStream_t st, const AxisTab &tab, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg, float inv,
-                         void *d_llr, int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) return generate_il_product_as<B, int8_t>(st, tab, il, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-    if (fmt == MOD_LLR_F16) return generate_il_product_as<B, __half>(st, tab, il, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-    return generate_il_product_as<B, float>(st, tab, il, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-}
-
-#define LDPC_IL_SWITCH(n_, what_, CALL)                                    \
-    int rc;                                                                \
-    switch (n_) {                                                          \
-        case 1: rc = CALL(1); break;                                       \
-        case 2: rc = CALL(2); break;                                       \
-        case 3: rc = CALL(3); break;                                       \
-        case 4: rc = CALL(4); break;                                       \
-        case 5: rc = CALL(5); break;                                       \
-        case 6: rc = CALL(6); break;                                       \
-        default: return set_error(LDPC_EINVAL, "%s: %d bits per symbol or axis", what_, n_); \
-    }                                                                      \
-    if (rc != LDPC_OK) return rc;                                          \
-    hipError_t e = hipGetLastError();                                      \
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "%s: %s", what_, hipGetErrorString(e)); \
-    return LDPC_OK;
-
+// ---- launchers.  transmit: pairs lanes per frame; generate: pairs + ceil(n_holes / 2M)
 int mod_transmit_il_launch(hipStream_t st, const ModTab &tab, int m, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
                            float *d_sym) {
-#define LDPC_IL_T(M_) transmit_il_m<M_>(st, tab, il, batch, d_cw, PB, seed, first_frame, sg, d_sym)
-    LDPC_IL_SWITCH(m, "ldpc_sim_transmit_il", LDPC_IL_T)
-#undef LDPC_IL_T
-}
-
-int mod_generate_il_launch(hipStream_t st, const ModTab &tab, int m, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
-                           float inv, void *d_llr, int fmt, float qscale) {
-#define LDPC_IL_G(M_) generate_il_m<M_>(st, tab, il, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, fmt, qscale)
-    LDPC_IL_SWITCH(m, "ldpc_sim_generate_mod_il", LDPC_IL_G)
-#undef LDPC_IL_G
+    const char *what = "ldpc_sim_transmit_il";
+    return launched(what, dispatch_bits(what, m, [&](auto k) {
+        constexpr int M = decltype(k)::value;
+        const int n_sym = mod_symbols(il.n_tx, M), pairs = mod_pairs(n_sym);
+        const size_t total = (size_t)batch * pairs;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((mod_transmit_il_kernel<M>), grid_lanes(total), dim3(256), 0, st, tab, il, d_cw, PB, d_sym, n_sym, pairs, total, seed, first_frame, sg,
+                               grant_pair_store(n_sym, d_sym, 16));
+        return rc;
+    }));
 }
 
 int product_transmit_il_launch(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
                                float sg, float *d_sym) {
-#define LDPC_IL_T(B_) transmit_il_b<B_>(st, tab, il, batch, d_cw, PB, seed, first_frame, sg, d_sym)
-    LDPC_IL_SWITCH(b, "ldpc_sim_transmit_il", LDPC_IL_T)
-#undef LDPC_IL_T
+    const char *what = "ldpc_sim_transmit_il";
+    return launched(what, dispatch_bits(what, b, [&](auto k) {
+        constexpr int B = decltype(k)::value;
+        const int n_sym = mod_symbols(il.n_tx, 2 * B), pairs = mod_pairs(n_sym);
+        const size_t total = (size_t)batch * pairs;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((product_transmit_il_kernel<B>), grid_lanes(total), dim3(256), 0, st, tab, il, d_cw, PB, d_sym, n_sym, pairs, total, seed, first_frame, sg,
+                               grant_pair_store(n_sym, d_sym, 16));
+        return rc;
+    }));
+}
+
+int mod_generate_il_launch(hipStream_t st, const ModTab &tab, int m, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
+                           float inv, void *d_llr, int fmt, float qscale) {
+    const char *what = "ldpc_sim_generate_mod_il";
+    return launched(what, dispatch_bits_fmt(what, m, fmt, [&](auto k, auto t) {
+        constexpr int M = decltype(k)::value;
+        typedef typename decltype(t)::type OT;
+        const int pairs = mod_pairs(mod_symbols(il.n_tx, M)), lanes = mod_lanes(pairs, il.n_holes, 2 * M);
+        const size_t total = (size_t)batch * lanes;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((mod_generate_il_kernel<M, OT>), grid_lanes(total), dim3(256), 0, st, tab, il, d_cw, PB, (OT *)d_llr, pairs, lanes, total, seed, first_frame, sg, inv,
+                               qscale);
+        return rc;
+    }));
 }
 
 int product_generate_il_launch(hipStream_t st, const AxisTab &tab, int b, const IlTab &il, int batch, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
                                float sg, float inv, void *d_llr, int fmt, float qscale) {
-#define LDPC_IL_G(B_) generate_il_b<B_>(st, tab, il, batch, d_cw, PB, seed, first_frame, sg, inv, d_llr, fmt, qscale)
-    LDPC_IL_SWITCH(b, "ldpc_sim_generate_mod_il", LDPC_IL_G)
-#undef LDPC_IL_G
+    const char *what = "ldpc_sim_generate_mod_il";
+    return launched(what, dispatch_bits_fmt(what, b, fmt, [&](auto k, auto t) {
+        constexpr int B = decltype(k)::value, M = 2 * B;
+        typedef typename decltype(t)::type OT;
+        const int pairs = mod_pairs(mod_symbols(il.n_tx, M)), lanes = mod_lanes(pairs, il.n_holes, 2 * M);
+        const size_t total = (size_t)batch * lanes;
+        const int rc = check_items(what, total);
+        if (rc == LDPC_OK)
+            hipLaunchKernelGGL((product_generate_il_kernel<B, OT>), grid_lanes(total), dim3(256), 0, st, tab, il, d_cw, PB, (OT *)d_llr, pairs, lanes, total, seed, first_frame, sg,
+                               inv, qscale);
+        return rc;
+    }));
 }
 
 }  // namespace ldpc

@@ -4,11 +4,10 @@
 // four normals of symbols 2g and 2g + 1.  The symbol rule and the LLR rule are the device functions of demap_product.h, the ones
 // demap_product_kernel calls: the fused kernel equals transmit + ldpc_demap_dev bit for bit.
 #include "demap_product.h"
+#include "mod_dispatch.h"
 #include "sim_noise.h"
 
 namespace ldpc {
-
-static unsigned product_grid(size_t total) { return (unsigned)((total + 255) / 256); }   // one item a lane (demap_product.hip): no grid-stride loop
 
 // the labels and the four normals of pair g of frame f.  A symbol from n_sym on (the second of the last pair when n_sym is odd, the
 // punctured tail) reads no byte at or past PB and gets label bits 0; what is computed for it is never stored
@@ -88,72 +87,40 @@ __global__ __launch_bounds__(256) void product_generate_kernel(AxisTab tab, cons
     }
 }
 
-template <int B>
-static void transmit_b(hipStream_t st, const AxisTab &tab, int batch, int n_tx, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg, float *d_sym) {
-    constexpr int M = 2 * B;
-    const int n_sym = (n_tx + M - 1) / M, pairs = (n_sym + 1) / 2;
-    const size_t total = (size_t)batch * pairs;
-    const int vec4 = (n_sym % 2 == 0) && ((uintptr_t)d_sym % 16 == 0);
-    hipLaunchKernelGGL((product_transmit_kernel<B>), dim3(product_grid(total)), dim3(256), 0, st, tab, d_cw, PB, d_sym, n_sym, pairs, total, seed, first_frame, sg, vec4);
-}
-
-template <int B, typename OT>
-static void generate_as(hipStream_t st, const AxisTab &tab, int batch, int n_tx, int N, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg, float inv,
-                        void *d_llr, float qs) {
-    constexpr int M = 2 * B;
-    const int n_sym = (n_tx + M - 1) / M, slots = (N + M - 1) / M, pslots = (slots + 1) / 2;
-    const size_t total = (size_t)batch * pslots;
-    const dim3 grid(product_grid(total));
-    if constexpr (kSlotPiece<M, OT> != 0) {
-        if (N % M == 0 && (uintptr_t)d_llr % kSlotPiece<M, OT> == 0) {
-            hipLaunchKernelGGL((product_generate_kernel<B, OT, true>), grid, dim3(256), 0, st, tab, d_cw, PB, (OT *)d_llr, n_tx, N, n_sym, slots, pslots, total, seed,
-                               first_frame, sg, inv, qs);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((product_generate_kernel<B, OT, false>), grid, dim3(256), 0, st, tab, d_cw, PB, (OT *)d_llr, n_tx, N, n_sym, slots, pslots, total, seed, first_frame,
-                       sg, inv, qs);
-}
-
-template <int B>
-static void generate_b(hipStream_t st, const AxisTab &tab, int batch, int n_tx, int N, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg, float inv,
-                       void *d_llr, int fmt, float qs) {
-    if (fmt == MOD_LLR_I8) generate_as<B, int8_t>(st, tab, batch, n_tx, N, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-    else if (fmt == MOD_LLR_F16) generate_as<B, __half>(st, tab, batch, n_tx, N, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-    else generate_as<B, float>(st, tab, batch, n_tx, N, d_cw, PB, seed, first_frame, sg, inv, d_llr, qs);
-}
-
-#define LDPC_AXIS_SWITCH(b_, CALL)                                         \
-    switch (b_) {                                                          \
-        case 1: CALL(1); break;                                            \
-        case 2: CALL(2); break;                                            \
-        case 3: CALL(3); break;                                            \
-        case 4: CALL(4); break;                                            \
-        case 5: CALL(5); break;                                            \
-        case 6: CALL(6); break;                                            \
-        default: return set_error(LDPC_EINVAL, "modulation: %d bits per axis", b_); \
-    }
-
 int product_transmit_launch(hipStream_t st, const AxisTab &tab, int b, int batch, int n_tx, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame, float sg,
                             float *d_sym) {
-    if ((size_t)batch * (size_t)n_tx > kProductMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_transmit: batch * n_tx = %zu is more than one launch holds", (size_t)batch * (size_t)n_tx);
-#define LDPC_AXIS_T(B_) transmit_b<B_>(st, tab, batch, n_tx, d_cw, PB, seed, first_frame, sg, d_sym)
-    LDPC_AXIS_SWITCH(b, LDPC_AXIS_T)
-#undef LDPC_AXIS_T
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "ldpc_sim_transmit: %s", hipGetErrorString(e));
-    return LDPC_OK;
+    const int rc = check_items("ldpc_sim_transmit", (size_t)batch * (size_t)n_tx, "batch * n_tx");
+    if (rc != LDPC_OK) return rc;
+    return launched("ldpc_sim_transmit", dispatch_bits("modulation", b, [&](auto k) {
+        constexpr int B = decltype(k)::value;
+        const int n_sym = mod_symbols(n_tx, 2 * B), pairs = mod_pairs(n_sym);
+        const size_t total = (size_t)batch * pairs;
+        hipLaunchKernelGGL((product_transmit_kernel<B>), grid_lanes(total), dim3(256), 0, st, tab, d_cw, PB, d_sym, n_sym, pairs, total, seed, first_frame, sg,
+                           grant_pair_store(n_sym, d_sym, 16));
+        return LDPC_OK;
+    }));
 }
 
 int product_generate_launch(hipStream_t st, const AxisTab &tab, int b, int batch, int n_tx, int N, const uint8_t *d_cw, int PB, uint64_t seed, uint64_t first_frame,
                             float sg, float inv, void *d_llr, int fmt, float qscale) {
-    if ((size_t)batch * (size_t)N > kProductMaxItems) return set_error(LDPC_EINVAL, "ldpc_sim_generate_mod: batch * N = %zu is more than one launch holds", (size_t)batch * (size_t)N);
-#define LDPC_AXIS_G(B_) generate_b<B_>(st, tab, batch, n_tx, N, d_cw, PB, seed, first_frame, sg, inv, d_llr, fmt, qscale)
-    LDPC_AXIS_SWITCH(b, LDPC_AXIS_G)
-#undef LDPC_AXIS_G
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "ldpc_sim_generate_mod: %s", hipGetErrorString(e));
-    return LDPC_OK;
+    const int rc = check_items("ldpc_sim_generate_mod", (size_t)batch * (size_t)N, "batch * N");
+    if (rc != LDPC_OK) return rc;
+    return launched("ldpc_sim_generate_mod", dispatch_bits_fmt("modulation", b, fmt, [&](auto k, auto t) {
+        constexpr int B = decltype(k)::value, M = 2 * B;
+        typedef typename decltype(t)::type OT;
+        const int n_sym = mod_symbols(n_tx, M), slots = mod_symbols(N, M), pslots = mod_pairs(slots);
+        const size_t total = (size_t)batch * pslots;
+        if constexpr (kSlotPiece<M, OT> != 0) {
+            if (grant_slot_store(N, M, d_llr, kSlotPiece<M, OT>)) {
+                hipLaunchKernelGGL((product_generate_kernel<B, OT, true>), grid_lanes(total), dim3(256), 0, st, tab, d_cw, PB, (OT *)d_llr, n_tx, N, n_sym, slots, pslots, total, seed,
+                                   first_frame, sg, inv, qscale);
+                return LDPC_OK;
+            }
+        }
+        hipLaunchKernelGGL((product_generate_kernel<B, OT, false>), grid_lanes(total), dim3(256), 0, st, tab, d_cw, PB, (OT *)d_llr, n_tx, N, n_sym, slots, pslots, total, seed,
+                           first_frame, sg, inv, qscale);
+        return LDPC_OK;
+    }));
 }
 
 }  // namespace ldpc

@@ -231,6 +231,27 @@ def test_fused_il_equals_two_step(hip, case):
             _same(d.get(same, B, FILL[fmt]), d.get(plain, B, FILL[fmt]), (case, name, fmt, "identity"))
             assert np.array_equal(d.get(mg, B, 9), d.get(mg2, B, 9))
         il.close(); ident.close(); mod.close()
+    # the instances of the fused kernels the two objects above leave out (every m and b = 1..6, in every format): the two steps, bit for bit
+    pts_of = {m: TABLES[TABLE_OF_M[m]]() for m in range(1, 7)}
+    objects = [(f"m={m}", m, lambda m=m: hip.Modulation(pts_of[m])) for m in range(1, 7)]
+    objects += [(f"b={b}", 2 * b, lambda b=b: hip.Modulation.product(_uneven(b, 60 + b), _uneven(b, 70 + b))) for b in range(1, 7)]
+    for name, m, make in objects:
+        mod = make()
+        assert mod.bits == m
+        ns = mod.symbols(src.n_tx)
+        pos = _source_table(src, m)
+        il = hip.Interleaver(pos, src.N)
+        for fmt, qs in (("f16", 0.0),) if name in ("m=3", "b=4") else (("f32", 0.0), ("f16", 0.0), ("i8", 4.0)):
+            sym, two, one = d.full(B, 2 * ns, 777.0, "f32"), d.full(B, src.N, FILL[fmt], fmt), d.full(B, src.N, FILL[fmt], fmt)
+            d.sync()
+            src.sim.transmit_il(mod, il, SEED, FIRST, B, 9.0, sym.data_ptr(), None, "bytes", None, None)
+            hip.demap_il(mod, il, B, sym.data_ptr(), src.sim.noise_var(mod, 9.0), two.data_ptr(), fmt, qs, None)
+            src.sim.generate_mod_il(mod, il, SEED, FIRST, B, 9.0, one.data_ptr(), fmt, qs, None, "bytes", None, None)
+            a, f = d.get(two, B, FILL[fmt]), d.get(one, B, FILL[fmt])
+            d.get(sym, B, 777.0)
+            _same(f, a, (case, name, fmt, "every instance"))
+            assert (f[:, ils.holes(pos, src.N)] == 0).all()
+        il.close(); mod.close()
     src.close()
 
 

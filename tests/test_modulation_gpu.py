@@ -272,6 +272,14 @@ def test_fused_equals_two_step(hip, case):
         _, l40, _ = _two_step_and_fused(hip, d, src, mod, B, 40.0, "f32", 0.0)
         assert np.array_equal((l40[:, :src.n_tx] > 0).astype(np.uint8), cw), (case, name, "40 dB")
         mod.close()
+    # the instances of the fused kernel the tables above leave out (m = 1, 4, 6), in every format: the two steps, bit for bit
+    for name in ("bpsk", "16qam", "grid64") if B < 1000 else ():
+        mod = hip.Modulation(TABLES[name]())
+        for fmt, qs in (("f32", 0.0), ("f16", 0.0), ("i8", 4.0)):
+            two, one, _ = _two_step_and_fused(hip, d, src, mod, B, 3.0, fmt, qs)
+            _same(one, two, (case, name, fmt))
+            assert (one[:, src.n_tx:] == 0).all()
+        mod.close()
     src.close()
 
 
@@ -402,3 +410,74 @@ def test_refusals(hip):
     assert (got[B] == 777.0).all() and (got[:B].reshape(B, ns, 2) == mod.points[0]).all()
     assert (gl[B] == 777.0).all() and (gl[:B, :n_tx] < 0).all() and (gl[:B, n_tx:] == 0).all()
     plain.close(); sim.close(); mod.close(); code.close()
+
+
+def test_which_error_wins(hip):
+    """A call with TWO mistakes is refused with the error of the check that comes first.  The entry points of the demappers and of the
+    modulated path share their argument checks (api.cc demap_args, sim_mod_check, sim_mod_run); this table pins the order those run
+    in, entry point by entry point: each row is a call, and a piece of the text ldpc_last_error() must hold"""
+    import torch
+    c = load("moon.7.13")
+    code = hip.Code.from_csr(c.graph.row_ptr, c.graph.col_idx, c.N)
+    dev = torch.device("cuda", 0)
+    B, N, n_tx = 4, c.N, 13
+    mod = hip.Modulation("qpsk")
+    logmap = mod.with_rule("logmap")
+    ns = mod.symbols(n_tx)
+    sym = torch.full((B + 1, 2 * ns + 2), 777.0, dtype=torch.float32, device=dev)
+    gain = torch.full((B + 1, ns + 2), 1.0, dtype=torch.float32, device=dev)
+    llr = torch.full((B + 1, N + 2), 777.0, dtype=torch.float32, device=dev)
+    la = torch.zeros((B + 1, N + 2), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    s, g, l, a = sym.data_ptr(), gain.data_ptr(), llr.data_ptr(), la.data_ptr()
+    il = hip.Interleaver(np.arange(n_tx, dtype=np.int32), N)
+    rm = hip.Ratematch(np.arange(n_tx, dtype=np.int32), N)
+    sim = hip.Sim(code, 7, n_tx, G=c.G, max_batch=B)
+    tiny = 1e-40                                            # a noise variance whose 1 / (2 noise_var) is no float32
+    rows = [
+        ("bad dimensions", hip.demap, (mod, 0, n_tx, N, s, 0.0, l)),
+        ("noise_var must be finite", hip.demap, (mod, B, n_tx, N, s, 0.0, l, 3)),
+        ("unknown LLR format", hip.demap, (mod, B, n_tx, N, s + 4, 0.1, l, 3)),
+        ("qscale must be finite", hip.demap, (mod, B, n_tx, N, s + 4, 0.1, l, "i8", -1.0)),
+        ("8-byte aligned", hip.demap, (mod, B, n_tx, N, s + 4, tiny, l)),
+        ("does not fit a float32", hip.demap, (mod, B, n_tx, N, s, tiny, l)),
+        ("bad dimensions", hip.demap_il, (mod, il, 0, s, 0.0, l)),
+        ("noise_var must be finite", hip.demap_il, (mod, il, B, s, 0.0, l, 3)),
+        ("unknown LLR format", hip.demap_il, (mod, il, B, s + 4, 0.1, l, 3)),
+        ("8-byte aligned", hip.demap_il, (mod, il, B, s + 4, tiny, l)),
+        ("bad dimensions", hip.demap_il_csi, (mod, il, 0, s, g, 0.0, l)),
+        ("unknown LLR format", hip.demap_il_csi, (mod, il, B, s, g + 2, 0.1, l, 3)),
+        ("gains 4-byte aligned", hip.demap_il_csi, (mod, il, B, s, g + 2, tiny, l)),
+        ("bad dimensions", hip.demap_il_apriori, (mod, il, 0, s, None, 0.0, l, l)),
+        ("noise_var must be finite", hip.demap_il_apriori, (mod, il, B, s, None, 0.0, l, l)),
+        ("unknown LLR format", hip.demap_il_apriori, (mod, il, B, s + 4, None, 0.1, l, l, 3)),
+        ("a-priori values 4-byte aligned", hip.demap_il_apriori, (mod, il, B, s + 4, None, tiny, l, l)),
+        ("overlaps d_llr", hip.demap_il_apriori, (mod, il, B, s, None, tiny, l, l)),
+        ("does not fit a float32", hip.demap_il_apriori, (mod, il, B, s, None, tiny, a, l)),
+        ("bad dimensions", hip.demap_rm, (mod, rm, 0, s, None, 0.1, l, "f32", 0.0, 2)),
+        ("accumulate must be 0 or 1", hip.demap_rm, (mod, rm, B, s, None, 0.0, l, "f32", 0.0, 2)),
+        ("noise_var must be finite", hip.demap_rm, (mod, rm, B, s, None, 0.0, l, 3)),
+        ("gains 4-byte aligned", hip.demap_rm, (mod, rm, B, s, g + 2, tiny, l)),
+        ("outside 1..", sim.transmit, (mod, 1, 0, 0, float("nan"), s + 4)),
+        ("8-byte aligned", sim.transmit, (mod, 1, 0, B, float("nan"), s + 4)),
+        ("no finite noise variance", sim.transmit, (mod, 1, 0, B, float("nan"), s)),
+        ("outside 1..", sim.generate_mod, (logmap, 1, 0, 0, 2.0, l, 3)),
+        ("no fused kernel for the log-MAP rule", sim.generate_mod, (logmap, 1, 0, B, 2.0, l, 3)),
+        ("unknown LLR format", sim.generate_mod, (mod, 1, 0, B, 2.0, l + 2, 3)),
+        ("aligned to their element", sim.generate_mod, (mod, 1, 0, B, float("nan"), l + 2)),
+        ("no finite noise variance > 0", sim.generate_mod, (mod, 1, 0, B, float("nan"), l)),
+        ("does not fit a float32", sim.generate_mod, (mod, 1, 0, B, 400.0, l)),
+        ("no fused kernel for the log-MAP rule", sim.generate_mod_il, (logmap, None, 1, 0, B, 2.0, l)),
+        ("null interleaver", sim.generate_mod_il, (mod, None, 1, 0, B, 2.0, l, 3)),
+        ("unknown LLR format", sim.generate_mod_il, (mod, il, 1, 0, B, 2.0, l + 2, 3)),
+        ("aligned to their element", sim.generate_mod_il, (mod, il, 1, 0, B, float("nan"), l + 2)),
+        ("null interleaver", sim.transmit_il, (mod, None, 1, 0, B, float("nan"), s + 4)),
+        ("8-byte aligned", sim.transmit_il, (mod, il, 1, 0, B, float("nan"), s + 4)),
+    ]
+    for text, fn, args in rows:
+        with pytest.raises(hip.LdpcError) as e:
+            fn(*args)
+        assert e.value.code == (-5 if "log-MAP" in text else -1) and text in str(e.value), (fn.__name__, text, str(e.value))
+    torch.cuda.synchronize()
+    assert (sym.cpu().numpy() == 777.0).all() and (llr.cpu().numpy() == 777.0).all()          # a refused call writes nothing
+    sim.close(); rm.close(); il.close(); logmap.close(); mod.close(); code.close()

@@ -200,6 +200,21 @@ def test_fused_equals_two_step(hip, case):
                 if db == 50.0:                           # far below half the minimum distance: the signs are the codeword
                     assert np.array_equal((f[:, :src.n_tx] > 0).astype(np.uint8), cw), (case, b, fmt, "50 dB")
         mod.close()
+    # the instances of the fused kernel the loop above leaves out (b = 1, 2, 3, 5 in every format, fp16 of b = 4, 6): the two steps, bit for bit
+    for b in range(1, 7):
+        mod = hip.Modulation.product(_uneven(b, 80 + b), _uneven(b, 90 + b))
+        ns = mod.symbols(src.n_tx)
+        for fmt, qs in (("f16", 0.0),) if b in (4, 6) else (("f32", 0.0), ("f16", 0.0), ("i8", 4.0)):
+            sym, two, one = d.full(B, 2 * ns, 777.0, "f32"), d.full(B, src.N, FILL[fmt], fmt), d.full(B, src.N, FILL[fmt], fmt)
+            d.sync()
+            src.sim.transmit(mod, SEED, FIRST, B, 12.0, sym.data_ptr(), None, "bytes", None, None)
+            hip.demap(mod, B, src.n_tx, src.N, sym.data_ptr(), src.sim.noise_var(mod, 12.0), two.data_ptr(), fmt, qs, None)
+            src.sim.generate_mod(mod, SEED, FIRST, B, 12.0, one.data_ptr(), fmt, qs, None, "bytes", None, None)
+            a, f = d.get(two, B, FILL[fmt]), d.get(one, B, FILL[fmt])
+            d.get(sym, B, 777.0)
+            _same(f, a, (case, b, fmt, "every instance"))
+            assert (f[:, src.n_tx:] == 0).all()
+        mod.close()
     src.close()
 
 
