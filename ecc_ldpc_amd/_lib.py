@@ -63,6 +63,8 @@ ABI_SYMBOLS = [
     "ldpc_demap_dev_rm", "ldpc_ratematch_llr_dev", "ldpc_ratematch_bits_dev", "ldpc_sim_noise_var_rm", "ldpc_sim_transmit_rm",
     "ldpc_crc_builtin", "ldpc_crc_bits_host", "ldpc_crc_table", "ldpc_crc_create_on", "ldpc_crc_destroy", "ldpc_crc_params",
     "ldpc_crc_attach_dev", "ldpc_crc_check_dev", "ldpc_sim_crc_check", "ldpc_sim_tally_crc",
+    "ldpc_bch_create_on", "ldpc_bch_destroy", "ldpc_bch_builtin", "ldpc_bch_params", "ldpc_bch_generator", "ldpc_bch_encode_host", "ldpc_bch_decode_host",
+    "ldpc_bch_encode_dev", "ldpc_bch_decode_dev", "ldpc_sim_bch_decode",
     "ldpc_matrix_load", "ldpc_matrix_load_mackay", "ldpc_matrix_destroy", "ldpc_matrix_info", "ldpc_matrix_dense",
     "ldpc_matrix_qc_offsets", "ldpc_code_from_matrix",
     "ldpc_ecc_create", "ldpc_ecc_destroy", "ldpc_ecc_name", "ldpc_ecc_message_length", "ldpc_ecc_codeword_length",
@@ -327,6 +329,18 @@ def lib():
     L.ldpc_crc_check_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
     L.ldpc_sim_crc_check.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp]
     L.ldpc_sim_tally_crc.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.ldpc_bch_create_on.restype = vp
+    L.ldpc_bch_create_on.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int]
+    L.ldpc_bch_destroy.restype = None
+    L.ldpc_bch_destroy.argtypes = [vp]
+    L.ldpc_bch_builtin.argtypes = [C.c_int, ip, u32p, ip]
+    L.ldpc_bch_params.argtypes = [vp, ip, u32p, ip, ip, ip]
+    L.ldpc_bch_generator.argtypes = [vp, u8p]
+    L.ldpc_bch_encode_host.argtypes = [vp, u8p]
+    L.ldpc_bch_decode_host.argtypes = [vp, u8p, ip]
+    L.ldpc_bch_encode_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    L.ldpc_bch_decode_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
+    L.ldpc_sim_bch_decode.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp]
     L.ldpc_matrix_qc_words.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.ldpc_matrix_rank.argtypes = [vp]
     L.ldpc_matrix_load.restype = vp
@@ -1323,6 +1337,96 @@ class Crc:
             pass
 
 
+BCH_KINDS = {"m16t8": 0, "m16t10": 1, "m16t12": 2, "m14t12": 3}   # LDPC_BCH_*
+
+
+class Bch:
+    """A binary, narrow-sense, primitive BCH code (ldpc_bch) over GF(2^m) from prim_poly (the x^m term included), correcting t errors,
+    shortened to n bits: k = n - p message bits, then the p bits of the remainder of m(x) x^p mod g, MSB first.  The parameters are
+    checked before the device is touched; the tables then live on `device` (None: the calling thread's; -1: a host-only object that
+    serves encode_host / decode_host alone).  Bch.builtin("m16t12", n) takes a built-in parameter set."""
+
+    def __init__(self, m, prim_poly, t, n, device=None):
+        for name, v in (("m", m), ("t", t), ("n", n)):
+            if not -2 ** 31 <= int(v) < 2 ** 31:
+                raise LdpcError(EINVAL, f"Bch: {name} does not fit an int")
+        if not 0 <= int(prim_poly) < 2 ** 32:
+            raise LdpcError(EINVAL, "Bch: prim_poly must be in 0 .. 2^32 - 1")
+        dev = int(device) if device is not None else lib().ldpc_current_device()
+        h = lib().ldpc_bch_create_on(dev, int(m), int(prim_poly), int(t), int(n))
+        if not h:
+            raise LdpcError(lib().ldpc_last_error_code(), last_error())
+        self._h = h
+        self.m, self.prim_poly, self.t, self.n, self.k = self.params()
+        self.p = self.n - self.k
+        _register(self)
+
+    @staticmethod
+    def builtin_params(kind):
+        """ldpc_bch_builtin (host only) -> (m, prim_poly, t); kind: a name of BCH_KINDS or the integer of LDPC_BCH_*"""
+        m, p, t = C.c_int(), C.c_uint32(), C.c_int()
+        check(lib().ldpc_bch_builtin(BCH_KINDS[kind] if isinstance(kind, str) else int(kind), C.byref(m), C.byref(p), C.byref(t)))
+        return m.value, p.value, t.value
+
+    @classmethod
+    def builtin(cls, kind, n, device=None):
+        m, p, t = cls.builtin_params(kind)
+        return cls(m, p, t, n, device=device)
+
+    def params(self):
+        """ldpc_bch_params -> (m, prim_poly, t, n, k)"""
+        m, p, t, n, k = C.c_int(), C.c_uint32(), C.c_int(), C.c_int(), C.c_int()
+        check(lib().ldpc_bch_params(self._h, C.byref(m), C.byref(p), C.byref(t), C.byref(n), C.byref(k)))
+        return m.value, p.value, t.value, n.value, k.value
+
+    def generator(self):
+        """ldpc_bch_generator -> g [p + 1] uint8, g[j] = the coefficient of x^j"""
+        g = np.zeros(self.p + 1, np.uint8)
+        got = lib().ldpc_bch_generator(self._h, ptr(g, C.c_uint8))
+        if got != self.p:
+            raise LdpcError(got, last_error())
+        return g
+
+    def _row(self, row):
+        r = np.array(row, np.uint8, copy=True).reshape(-1)
+        if r.shape[0] != self.n:
+            raise LdpcError(EINVAL, f"Bch: a row has n = {self.n} bytes, got {r.shape[0]}")
+        return r
+
+    def encode_host(self, row):
+        """ldpc_bch_encode_host: the serial rule on one row [n] bytes (bit 0 of each read) -> the row with its p parity bytes written"""
+        r = self._row(row)
+        check(lib().ldpc_bch_encode_host(self._h, ptr(r, C.c_uint8)))
+        return r
+
+    def decode_host(self, row):
+        """ldpc_bch_decode_host: -> (the row with bit 0 of the corrected bytes flipped, or as it was; nerr, -1 if not decodable)"""
+        r, e = self._row(row), C.c_int(-2)
+        check(lib().ldpc_bch_decode_host(self._h, ptr(r, C.c_uint8), C.byref(e)))
+        return r, e.value
+
+    def encode(self, batch, d_rows_ptr, fmt="bytes", stream=None):
+        """ldpc_bch_encode_dev, in place: rows [batch][n] bytes, or "packed" rows of 4 * ceil(n / 32) bytes; bits k .. n - 1 are written"""
+        check(lib().ldpc_bch_encode_dev(self._h, int(batch), d_rows_ptr, Sim._bits_fmt(fmt), stream))
+
+    def decode(self, batch, d_rows_ptr, d_nerr_ptr, fmt="bytes", stream=None):
+        """ldpc_bch_decode_dev, in place: d_nerr [batch] int32 <- the bits corrected in each row, or -1 for a row left as it was"""
+        check(lib().ldpc_bch_decode_dev(self._h, int(batch), d_rows_ptr, Sim._bits_fmt(fmt), d_nerr_ptr, stream))
+
+    def close(self):
+        if self._h:
+            lib().ldpc_bch_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        if _finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Sim:
     """Device-side frame source + error tally (ldpc_sim)."""
 
@@ -1461,6 +1565,11 @@ class Sim:
         """ldpc_sim_crc_check: Crc.check() straight on decoded codewords ([batch][N] bytes, or "packed" rows of ceil(N / 8) bytes): the flags
         of extract_messages() followed by crc.check(), with no message buffer in between"""
         check(lib().ldpc_sim_crc_check(self._h, _h(crc), int(batch), d_bits_ptr, self._bits_fmt(bits_fmt), d_ok_ptr, stream))
+
+    def bch_decode(self, bch: "Bch", batch, d_bits_ptr, d_nerr_ptr, bits_fmt="bytes", stream=None):
+        """ldpc_sim_bch_decode: Bch.decode() straight on decoded codewords ([batch][N] bytes, or "packed" rows of ceil(N / 8) bytes): BCH row
+        bit i is decoded bit msg_pos[i], corrected where it lies; d_nerr [batch] int32"""
+        check(lib().ldpc_sim_bch_decode(self._h, _h(bch), int(batch), d_bits_ptr, self._bits_fmt(bits_fmt), d_nerr_ptr, stream))
 
     def tally_crc(self, batch, d_bits_ptr, d_ok_ptr, d_tally_ptr, stream=None):
         """ldpc_sim_tally_crc: d_tally [4] uint64 += {frames, CRC passes, frames with a message-bit error, passes with an error (undetected)}"""

@@ -16,6 +16,7 @@
 #include "interleaver.h"
 #include "fading.h"
 #include "ratematch.h"
+#include "bch.h"
 #include "crc.h"
 #include "jit.h"
 #include "sim.h"
@@ -1997,6 +1998,96 @@ int ldpc_sim_tally_crc(ldpc_sim *sim, int batch, const uint8_t *d_bits, const ui
     HIPCHK(hipSetDevice(sim->device));
     return ldpc::crc_tally_launch((hipStream_t)stream, sim->systematic ? sim->sy.msg_pos : nullptr, sim->dev.N, sim->dev.k, sim->dev.kwords, sim->d_msgw, batch,
                                   d_bits, d_ok, (unsigned long long *)d_tally);
+}
+
+// ---- the BCH outer code (csrc/bch.h): the object, encode and decode on rows, the decode on decoded codewords
+ldpc_bch *ldpc_bch_create_on(int device, int m, uint32_t prim_poly, int t, int n) {
+    ldpc_bch *bch = new (std::nothrow) ldpc_bch();
+    if (!bch) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    std::vector<uint32_t> planes;
+    try {
+        std::string err;
+        if (bch->code.init("ldpc_bch_create_on", m, prim_poly, t, n, err) != 0) {   // before the device is touched
+            delete bch;
+            set_error(LDPC_EINVAL, "%s", err.c_str());
+            return nullptr;
+        }
+        const int words = (bch->code.p + 31) / 32;
+        bch->W = words <= 2 ? words : words <= 4 ? 4 : words <= 6 ? 6 : 8;
+        if (device >= 0) bch->code.table(bch->W, planes);
+    } catch (const std::bad_alloc &) { delete bch; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    if (device < 0) return bch;                                                     // a host-only object: the two _host functions serve it
+    if (check_device(device) != LDPC_OK) { delete bch; return nullptr; }
+    bch->device = device;
+    const ldpc::BchCode &c = bch->code;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void **)&bch->d_T, planes.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(bch->d_T, planes.data(), planes.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&bch->d_alog, c.alog.size() * 2);
+    if (e == hipSuccess) e = hipMemcpy(bch->d_alog, c.alog.data(), c.alog.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&bch->d_log, c.log.size() * 2);
+    if (e == hipSuccess) e = hipMemcpy(bch->d_log, c.log.data(), c.log.size() * 2, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_error(LDPC_EHIP, "ldpc_bch_create_on: %s", hipGetErrorString(e)); ldpc_bch_destroy(bch); return nullptr; }
+    bch->tab.T = bch->d_T; bch->tab.alog = bch->d_alog; bch->tab.log = bch->d_log;
+    bch->tab.n = c.n; bch->tab.k = c.k; bch->tab.p = c.p; bch->tab.n4 = (c.n + 3) / 4 * 4; bch->tab.m = c.m; bch->tab.t = c.t; bch->tab.N0 = c.N0;
+    bch->tab.prim_poly = c.prim_poly;
+    return bch;
+}
+
+void ldpc_bch_destroy(ldpc_bch *bch) {
+    if (!bch) return;
+    if (bch->device >= 0) {
+        (void)hipSetDevice(bch->device);
+        if (bch->d_T) hipFree(bch->d_T);
+        if (bch->d_alog) hipFree(bch->d_alog);
+        if (bch->d_log) hipFree(bch->d_log);
+    }
+    delete bch;
+}
+
+// what the two entry points on rows share; on LDPC_OK the calling thread's device, which is the object's, is current
+static int bch_call_check(const char *what, const ldpc_bch *bch, int batch, const void *d_rows, int fmt) {
+    if (!bch || !d_rows) return set_error(LDPC_EINVAL, "%s: null %s", what, bch ? "d_rows" : "bch");
+    if (batch <= 0 || (size_t)batch * (size_t)bch->code.n > ldpc::kBchMaxItems)
+        return set_error(LDPC_EINVAL, "%s: batch = %d: must be >= 1 with batch * n at most 2^32 - 256 (n = %d)", what, batch, bch->code.n);
+    if (fmt != LDPC_BITS_BYTES && fmt != LDPC_BITS_PACKED) return set_error(LDPC_EINVAL, "%s: fmt = %d: unknown bit format (LDPC_BITS_BYTES = 0, LDPC_BITS_PACKED = 1)", what, fmt);
+    if (fmt == LDPC_BITS_PACKED && (uintptr_t)d_rows % 4 != 0) return set_error(LDPC_EINVAL, "%s: d_rows: packed rows must be 4-byte aligned", what);
+    if (bch->device < 0) return set_error(LDPC_EINVAL, "%s: bch is a host-only object (created with device = -1)", what);
+    const int device = current_device();
+    if (device < 0) return set_error(LDPC_ENODEVICE, "ldpc_init() has not succeeded");
+    if (bch->device != device) return set_error(LDPC_EINVAL, "%s: bch lives on device %d, the calling thread's device is %d", what, bch->device, device);
+    HIPCHK(hipSetDevice(device));
+    return LDPC_OK;
+}
+
+int ldpc_bch_encode_dev(const ldpc_bch *bch, int batch, void *d_rows, int fmt, void *stream) {
+    const int rc = bch_call_check("ldpc_bch_encode_dev", bch, batch, d_rows, fmt);
+    if (rc != LDPC_OK) return rc;
+    return ldpc::bch_encode_launch((hipStream_t)stream, bch->tab, bch->W, batch, d_rows, fmt == LDPC_BITS_PACKED);
+}
+
+int ldpc_bch_decode_dev(const ldpc_bch *bch, int batch, void *d_rows, int fmt, int32_t *d_nerr, void *stream) {
+    if (!d_nerr) return set_error(LDPC_EINVAL, "ldpc_bch_decode_dev: null d_nerr");
+    const int rc = bch_call_check("ldpc_bch_decode_dev", bch, batch, d_rows, fmt);
+    if (rc != LDPC_OK) return rc;
+    const bool packed = fmt == LDPC_BITS_PACKED;
+    return ldpc::bch_decode_launch((hipStream_t)stream, bch->tab, bch->W, batch, (uint8_t *)d_rows, packed ? (size_t)4 * ((bch->code.n + 31) / 32) : (size_t)bch->code.n, packed,
+                                   nullptr, d_nerr);
+}
+
+int ldpc_sim_bch_decode(const ldpc_sim *sim, const ldpc_bch *bch, int batch, void *d_bits, int bits_fmt, int32_t *d_nerr, void *stream) {
+    if (!sim || !bch || !d_bits || !d_nerr) return set_error(LDPC_EINVAL, "ldpc_sim_bch_decode: null %s", !sim ? "sim" : !bch ? "bch" : !d_bits ? "d_bits" : "d_nerr");
+    if (bits_fmt != LDPC_BITS_BYTES && bits_fmt != LDPC_BITS_PACKED)
+        return set_error(LDPC_EINVAL, "ldpc_sim_bch_decode: bits_fmt = %d: unknown bit format (LDPC_BITS_BYTES = 0, LDPC_BITS_PACKED = 1)", bits_fmt);
+    if (bch->code.n != sim->dev.k)
+        return set_error(LDPC_EINVAL, "ldpc_sim_bch_decode: bch is for rows of n = %d bits, the frame source's messages have %d", bch->code.n, sim->dev.k);
+    if (bch->device != sim->device) return set_error(LDPC_EINVAL, "ldpc_sim_bch_decode: bch lives on device %d, the frame source on device %d", bch->device, sim->device);
+    if (batch <= 0 || (size_t)batch * (size_t)sim->dev.k > ldpc::kBchMaxItems)
+        return set_error(LDPC_EINVAL, "ldpc_sim_bch_decode: batch = %d: must be >= 1 with batch * n at most 2^32 - 256 (n = %d)", batch, sim->dev.k);
+    HIPCHK(hipSetDevice(sim->device));
+    const bool packed = bits_fmt == LDPC_BITS_PACKED;
+    return ldpc::bch_decode_launch((hipStream_t)stream, bch->tab, bch->W, batch, (uint8_t *)d_bits, packed ? (size_t)(sim->dev.N + 7) / 8 : (size_t)sim->dev.N, packed,
+                                   sim->systematic ? sim->sy.msg_pos : nullptr, d_nerr);
 }
 
 int ldpc_sim_extract_messages(const ldpc_sim *sim, int batch, const uint8_t *d_bits, void *d_msg, int msg_fmt, void *stream) {

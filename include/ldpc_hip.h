@@ -913,6 +913,48 @@ int ldpc_sim_crc_check(const ldpc_sim *sim, const ldpc_crc *crc, int batch, cons
  * the source last drew, or the caller's after ldpc_sim_generate_from, ldpc_sim_encode_messages or a transmit with d_msg_in.
  * 1 <= batch <= max_batch. */
 int ldpc_sim_tally_crc(ldpc_sim *sim, int batch, const uint8_t *d_bits, const uint8_t *d_ok /* [batch] */, uint64_t *d_tally /* [4] */, void *stream);
+/* ---- BCH outer code: a binary, narrow-sense, primitive BCH code that REPAIRS the few bit errors a decode leaves where the CRC above
+ * can only detect them.  The rule is integer arithmetic, restated in tests/bch_spec.py; the kernels reproduce it exactly.
+ * FIELD: GF(2^m), m = 3 .. 16, from prim_poly (the x^m term included, e.g. 0x1002D), alpha = x, N0 = 2^m - 1; a prim_poly under which x
+ * does not have order N0 is refused.  GENERATOR: g = the product of the distinct minimal polynomials of alpha^1 .. alpha^(2t), t = 1 .. 16,
+ * 2t < N0; p = deg g <= m t <= 256.  The code is shortened to n bits, p < n <= N0; k = n - p.
+ * ROW: bit i, i = 0 .. n - 1, is the coefficient of x^(n - 1 - i): bits 0 .. k - 1 the message, bits k .. n - 1 the remainder of
+ * m(x) x^p mod g, MSB first (the CRC's order).  LDPC_BITS_BYTES rows are n bytes; LDPC_BITS_PACKED rows are 4 * ceil(n / 32) bytes, 4-byte
+ * aligned, bit i in byte i / 8 at bit i % 8.
+ * DECODE: if a codeword lies within Hamming distance e <= t of the row (it is unique) the row becomes it and nerr = e; otherwise the row
+ * stays exactly as it was and nerr = -1.
+ * The built-in parameter sets are defined by formula, with NO claim that they are any standard's (m, prim_poly, t):
+ *   LDPC_BCH_M16_T8 (16, 0x1002D, 8)  LDPC_BCH_M16_T10 (16, 0x1002D, 10)  LDPC_BCH_M16_T12 (16, 0x1002D, 12)  LDPC_BCH_M14_T12 (14, 0x402B, 12). */
+enum { LDPC_BCH_M16_T8 = 0, LDPC_BCH_M16_T10 = 1, LDPC_BCH_M16_T12 = 2, LDPC_BCH_M14_T12 = 3 };
+/* The object holds the field's tables and g on the host and, for device >= 0, the kernels' tables in device memory: 4 W n bytes of the
+ * remainder's linear form (W = ceil(p / 32) rounded up to 1, 2, 4, 6 or 8) and 6 N0 bytes of antilog (doubled) and log.  device = -1
+ * makes a host-only object that serves the _host functions alone.  The arguments are checked before the device is touched: LDPC_EINVAL
+ * and NULL, the message naming the argument, for m, t or n out of range, a prim_poly that is not primitive, 2t >= N0, n <= p. */
+typedef struct ldpc_bch ldpc_bch;
+ldpc_bch *ldpc_bch_create_on(int device, int m, uint32_t prim_poly, int t, int n);
+void ldpc_bch_destroy(ldpc_bch *bch);
+int ldpc_bch_builtin(int kind, int *m, uint32_t *prim_poly, int *t);                                  /* any pointer may be NULL */
+int ldpc_bch_params(const ldpc_bch *bch, int *m, uint32_t *prim_poly, int *t, int *n, int *k);   /* any pointer may be NULL */
+int ldpc_bch_generator(const ldpc_bch *bch, uint8_t *g /* [p + 1], g[j] = coeff of x^j; may be NULL */);   /* returns p */
+/* The serial rule on one row of n bytes, in place, no device touched: bit 0 of a byte is read, encode writes the p parity bytes as 0 / 1,
+ * decode flips bit 0 of the bytes it corrects (*nerr as above). */
+int ldpc_bch_encode_host(const ldpc_bch *bch, uint8_t *row /* [n] bytes, in place */);
+int ldpc_bch_decode_host(const ldpc_bch *bch, uint8_t *row /* [n] bytes, in place */, int *nerr);
+/* Device pointers, the calling thread's device = the object's, enqueued on `stream`, not synchronised.  batch >= 1 and batch * n <=
+ * 2^32 - 256 (LDPC_EINVAL otherwise, and for a null pointer, an unknown format or a host-only object).  One wave per frame; no atomics.
+ * ldpc_bch_encode_dev, IN PLACE: reads bits 0 .. k - 1 and writes bits k .. n - 1.
+ *   LDPC_BITS_BYTES   only bit 0 of a message byte is read and no message byte is written; the parity bytes are 0 or 1.
+ *   LDPC_BITS_PACKED  message bits are kept, bits >= n of the last word are written 0.
+ * ldpc_bch_decode_dev, IN PLACE: d_nerr[f] is written exactly once; a corrected bit is row[i] ^= 1 (bytes: bits 1 .. 7 survive) or that
+ * one bit of a packed row; a row with d_nerr[f] <= 0 is not written. */
+int ldpc_bch_encode_dev(const ldpc_bch *bch, int batch, void *d_rows, int fmt, void *stream);
+int ldpc_bch_decode_dev(const ldpc_bch *bch, int batch, void *d_rows, int fmt, int32_t *d_nerr /* [batch] */, void *stream);
+/* The same decode straight on decoded codewords, to the BCH decoder what ldpc_sim_crc_check is to the CRC: BCH row bit i = decoded bit
+ * msg_pos[i] of d_bits, [batch][N] bytes (LDPC_BITS_BYTES) or packed rows of ceil(N / 8) bytes (LDPC_BITS_PACKED), corrected where they
+ * lie; no other bit is written.  LDPC_EINVAL also when n is not the source's message length, or the object lives on another device
+ * than the source.  ldpc_sim_tally, ldpc_sim_extract_messages and ldpc_sim_tally_crc (with ok = nerr >= 0) then work as they are. */
+int ldpc_sim_bch_decode(const ldpc_sim *sim, const ldpc_bch *bch, int batch, void *d_bits /* decoded codewords [batch][N] */, int bits_fmt, int32_t *d_nerr /* [batch] */,
+                        void *stream);
 
 /* ---- matrix ingest --------------------------------------------------------------------------------
  * replaces loadMatrix (src/Data/BitMatrix/Loader.hs:58-81): `name` is "<matrix>/H" or "<matrix>/G";
