@@ -26,11 +26,13 @@ DEMAP_MAXLOG, DEMAP_LOGMAP = 0, 1   # ldpc_demap_rule
 LLR_F32, LLR_F16, LLR_I8 = 0, 1, 2   # LDPC_LLR_*: the output formats of the demapper
 SOFT_POSTERIOR, SOFT_EXTRINSIC = 0, 1   # LDPC_SOFT_*: the kinds of ldpc_decode_batch_dev_soft
 _SOFT_KINDS = {"posterior": SOFT_POSTERIOR, "extrinsic": SOFT_EXTRINSIC}
+CN_MINSUM, CN_AMINSTAR = 0, 1   # ldpc_cn_rule
+_CN_RULES = {None: CN_MINSUM, "minsum": CN_MINSUM, "aminstar": CN_AMINSTAR, CN_MINSUM: CN_MINSUM, CN_AMINSTAR: CN_AMINSTAR}
 
 
 class CtxConfig(C.Structure):   # ldpc_ctx_config
     _fields_ = [("struct_size", C.c_size_t), ("device", C.c_int), ("variant", C.c_int), ("dtype", C.c_int), ("max_batch", C.c_int),
-                ("path", C.c_int), ("schedule", C.c_int), ("sum_order", C.c_int), ("llr_qscale", C.c_float), ("cn_scale", C.c_float), ("cn_offset", C.c_float)]
+                ("path", C.c_int), ("schedule", C.c_int), ("sum_order", C.c_int), ("llr_qscale", C.c_float), ("cn_scale", C.c_float), ("cn_offset", C.c_float), ("cn_rule", C.c_int)]
 
 class FadingStruct(C.Structure):   # ldpc_fading
     _fields_ = [("struct_size", C.c_size_t), ("block", C.c_int), ("k_factor", C.c_float)]
@@ -44,7 +46,7 @@ ABI_SYMBOLS = [
     "ldpc_code_create_qc", "ldpc_code_create_csr", "ldpc_code_destroy", "ldpc_code_dims", "ldpc_code_csr",
     "ldpc_ctx_create", "ldpc_ctx_create_ex", "ldpc_ctx_destroy", "ldpc_ctx_path", "ldpc_ctx_synchronize",
     "ldpc_decode_one", "ldpc_decode_batch", "ldpc_decode_batch_f64", "ldpc_decode_batch_dev",
-    "ldpc_decode_batch_i8", "ldpc_decode_batch_dev_i8", "ldpc_ctx_llr_qscale", "ldpc_ctx_cn_scale", "ldpc_ctx_cn_offset",
+    "ldpc_decode_batch_i8", "ldpc_decode_batch_dev_i8", "ldpc_ctx_llr_qscale", "ldpc_ctx_cn_scale", "ldpc_ctx_cn_offset", "ldpc_ctx_cn_rule",
     "ldpc_decode_batch_f16", "ldpc_decode_batch_dev_f16", "ldpc_sim_generate_f16", "ldpc_decode_batch_dev_packed", "ldpc_decode_batch_packed",
     "ldpc_debug_step", "ldpc_decode_trace",
     "ldpc_host_alloc", "ldpc_host_free",
@@ -221,6 +223,8 @@ def lib():
     L.ldpc_ctx_cn_scale.argtypes = [vp]
     L.ldpc_ctx_cn_offset.restype = C.c_float
     L.ldpc_ctx_cn_offset.argtypes = [vp]
+    L.ldpc_ctx_cn_rule.restype = C.c_int
+    L.ldpc_ctx_cn_rule.argtypes = [vp]
     L.ldpc_decode_batch_dev_packed.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.ldpc_decode_batch_packed.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, u8p, i32p, u8p]
     L.ldpc_debug_step.argtypes = [vp, C.c_int, f64p, f64p, f64p, f64p, f64p, u8p]
@@ -602,22 +606,23 @@ class Decoder:
     """One decoder replica (ldpc_ctx): the object behind the reference's per-frame closure."""
 
     def __init__(self, code: Code, variant="min", dtype="f32", max_batch=64, path="auto", _handle=None, device=None, schedule="flooding",
-                 sum_order="reference", qscale=None, cn_scale=None, cn_offset=None):
+                 sum_order="reference", qscale=None, cn_scale=None, cn_offset=None, cn_rule=None):
         """sum_order: "reference" | "arraylet" | "sparse" -- the column-sum order of that family of the reference's decoders
         (ldpc_sum_order: parity modes, flood path); qscale: the quantiser's scale of dtype "i8" (None: the library's default, 4);
         cn_scale, cn_offset: the check-node rule |msg'| = max(cn_scale * min - cn_offset, 0) of layered min-sum with dtype "f16", "f32"
-        or "i8" on the on-chip kernel for any H (None: the 3/4 of every other kernel, and no offset)"""
+        or "i8" on the on-chip kernel for any H (None: the 3/4 of every other kernel, and no offset); cn_rule: None or "minsum" for that,
+        "aminstar" for the A-min* check-node rule of the same kernel (dtype "f16" or "f32"; it has no scale and no offset)"""
         self.code = code
         self.max_batch = int(max_batch)
         self._owned = _handle is None
         if _handle is not None:
             self._h = _handle
-        elif device is None and _SCHEDULES[schedule] == SCHED_FLOODING and _SUM_ORDERS[sum_order] == SUM_REFERENCE and qscale is None and cn_scale is None and cn_offset is None:
+        elif device is None and _SCHEDULES[schedule] == SCHED_FLOODING and _SUM_ORDERS[sum_order] == SUM_REFERENCE and qscale is None and cn_scale is None and cn_offset is None and _CN_RULES[cn_rule] == CN_MINSUM:
             self._h = lib().ldpc_ctx_create_ex(code._h, _VARIANTS[variant], _DTYPES[dtype], int(max_batch), _PATHS[path])
         else:   # explicit device (replicas of one code on several GPUs of this process) and/or the layered schedule
             cfg = CtxConfig(C.sizeof(CtxConfig), -1 if device is None else int(device), _VARIANTS[variant], _DTYPES[dtype], int(max_batch),
                             _PATHS[path], _SCHEDULES[schedule], _SUM_ORDERS[sum_order], 0.0 if qscale is None else float(qscale),
-                            0.0 if cn_scale is None else float(cn_scale), 0.0 if cn_offset is None else float(cn_offset))
+                            0.0 if cn_scale is None else float(cn_scale), 0.0 if cn_offset is None else float(cn_offset), _CN_RULES[cn_rule])
             self._h = lib().ldpc_ctx_create_cfg(code._h, C.byref(cfg))
         if not self._h:
             raise LdpcError(lib().ldpc_last_error_code(), last_error())
@@ -630,6 +635,11 @@ class Decoder:
     def cn_scale(self):
         """the scale of the min-sum check-node rule this context computes with (an "i8" context: a / 16); 0.0 on a tanh context"""
         return float(lib().ldpc_ctx_cn_scale(self._h))
+
+    @property
+    def cn_rule(self):
+        """"aminstar" on a context of the A-min* check-node rule, "minsum" on every other"""
+        return {CN_MINSUM: "minsum", CN_AMINSTAR: "aminstar"}[lib().ldpc_ctx_cn_rule(self._h)]
 
     @property
     def cn_offset(self):

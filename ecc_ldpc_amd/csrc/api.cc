@@ -57,6 +57,7 @@ struct ldpc_ctx {
     const ldpc_code *code = nullptr;
     int max_batch = 0, device = 0, schedule = LDPC_SCHED_FLOODING, dtype = LDPC_F32;
     float llr_qscale = 0.f;             // LDPC_I8: the quantiser's scale (0 for every other dtype)
+    int cn_rule = LDPC_CN_MINSUM;           // LDPC_CN_AMINSTAR: the A-min* row of csrc/layered_csr.hip (then cn_scale = cn_offset = 0)
     float cn_scale = 0.f, cn_offset = 0.f;  // the min-sum check-node rule the kernel computes with (0.75, 0 unless configured; 0, 0: tanh)
     hipStream_t stream = nullptr;
     ldpc::Backend *backend = nullptr;   // the context's decoder (select.cc make_backend)
@@ -511,6 +512,7 @@ int ldpc_ctx_schedule(const ldpc_ctx *ctx) { return ctx ? ctx->schedule : set_er
 float ldpc_ctx_llr_qscale(const ldpc_ctx *ctx) { return ctx ? ctx->llr_qscale : 0.f; }
 float ldpc_ctx_cn_scale(const ldpc_ctx *ctx) { return ctx ? ctx->cn_scale : 0.f; }
 float ldpc_ctx_cn_offset(const ldpc_ctx *ctx) { return ctx ? ctx->cn_offset : 0.f; }
+int ldpc_ctx_cn_rule(const ldpc_ctx *ctx) { return ctx ? ctx->cn_rule : set_error(LDPC_EINVAL, "null ctx"); }
 
 ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cfg) {
     if (!cfg || cfg->struct_size < offsetof(ldpc_ctx_config, schedule)) { set_error(LDPC_EINVAL, "ldpc_ctx_create_cfg: bad config"); return nullptr; }
@@ -535,16 +537,25 @@ ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cf
     float cn_offset = cfg->struct_size >= offsetof(ldpc_ctx_config, cn_offset) + sizeof(float) ? cfg->cn_offset : 0.f;
     if (!(cn_scale >= 0.f && cn_scale <= 1.f)) { set_error(LDPC_EINVAL, "cn_scale %g: the check-node rule's scale must be finite and in (0, 1] (0: the default, 3/4)", (double)cn_scale); return nullptr; }
     if (!(cn_offset >= 0.f) || cn_offset > 3.4028234e38f) { set_error(LDPC_EINVAL, "cn_offset %g: the check-node rule's offset must be finite and >= 0", (double)cn_offset); return nullptr; }
+    // cn_rule: LDPC_CN_AMINSTAR is the A-min* row (csrc/layered_csr.hip layered_csr_kernel<D, MinStar<LT>>), which has no scale and no offset
+    const int cn_rule = cfg->struct_size >= offsetof(ldpc_ctx_config, cn_rule) + sizeof(int) ? cfg->cn_rule : LDPC_CN_MINSUM;
+    if (cn_rule != LDPC_CN_MINSUM && cn_rule != LDPC_CN_AMINSTAR) { set_error(LDPC_EINVAL, "unknown cn_rule %d (LDPC_CN_MINSUM or LDPC_CN_AMINSTAR)", cn_rule); return nullptr; }
+    const bool aminstar = cn_rule == LDPC_CN_AMINSTAR;
+    if (aminstar && (cn_scale != 0.f || cn_offset != 0.f)) {
+        set_error(LDPC_EINVAL, "cn_rule LDPC_CN_AMINSTAR has no scale and no offset: cn_scale %g and cn_offset %g must be 0", (double)cn_scale, (double)cn_offset);
+        return nullptr;
+    }
     if (cn_scale == 0.f) cn_scale = 0.75f;
     ldpc::CnRule rule{cn_scale, cn_offset, 12, 0};
-    if (dtype == LDPC_I8) {
+    rule.kind = cn_rule;
+    if (dtype == LDPC_I8 && !aminstar) {
         const float a = rintf(cn_scale * 16.f), b = rintf(cn_offset * llr_qscale);       // (ties to even; 16 alpha is exact)
         if (a < 1.f) { set_error(LDPC_EINVAL, "cn_scale %g: LDPC_I8 computes with rint(16 cn_scale) sixteenths, which is 0", (double)cn_scale); return nullptr; }
         if (!(b <= 127.f)) { set_error(LDPC_EINVAL, "cn_offset %g: LDPC_I8 computes with rint(cn_offset * llr_qscale) = %g quantiser steps, above 127", (double)cn_offset, (double)b); return nullptr; }
         rule.a = (int)a; rule.b = (int)b;
         rule.scale = (float)rule.a / 16.f; rule.offset = (float)rule.b / llr_qscale;
     }
-    const bool has_rule = dtype == LDPC_I8 ? (rule.a != 12 || rule.b != 0) : (cn_scale != 0.75f || cn_offset != 0.f);
+    const bool has_rule = aminstar ? true : dtype == LDPC_I8 ? (rule.a != 12 || rule.b != 0) : (cn_scale != 0.75f || cn_offset != 0.f);
     // (a context with a rule of its own is refused by make_backend, whose message names the rule, not by the parity-mode checks below)
     if (!has_rule && sum_order != LDPC_SUM_REFERENCE && (schedule != LDPC_SCHED_FLOODING || path == LDPC_PATH_FUSED || cfg->dtype == LDPC_F16 || cfg->dtype == LDPC_F16PK)) {
         set_error(LDPC_EUNSUPPORTED, "LDPC_SUM_ARRAYLET / LDPC_SUM_SPARSE are parity modes: flooding schedule, flood path, f32 or f64");
@@ -584,7 +595,7 @@ ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code_c, const ldpc_ctx_config *cf
     ctx->code = code; ctx->max_batch = max_batch; ctx->device = device; ctx->schedule = schedule; ctx->backend = backend;
     ctx->dtype = dtype; ctx->llr_qscale = dtype == LDPC_I8 ? llr_qscale : 0.f;
     const bool minsum = variant == LDPC_MINSUM;
-    ctx->cn_scale = minsum ? rule.scale : 0.f; ctx->cn_offset = minsum ? rule.offset : 0.f;
+    ctx->cn_scale = minsum && !aminstar ? rule.scale : 0.f; ctx->cn_offset = minsum && !aminstar ? rule.offset : 0.f; ctx->cn_rule = cn_rule;
     backend->timer = &ctx->timer;
     {
         std::lock_guard<std::mutex> lk(g_ctx_mu);

@@ -54,7 +54,9 @@ struct Backend {
 // A min-sum check-node rule other than the library's 3/4 (ldpc_ctx_config cn_scale / cn_offset, validated by api.cc):
 // |msg'| = max(scale * min - offset, 0) in float cells; a / 16 and b quantiser steps in the integers of an LDPC_I8 context
 // (a = clip(rint(16 scale), 1, 16), b = rint(offset * llr_qscale)).  Served by csrc/layered_csr.hip alone.
-struct CnRule { float scale, offset; int a, b; };
+// kind LDPC_CN_AMINSTAR (ldpc_ctx_config cn_rule): the A-min* row of layered_csr_kernel<D, MinStar<LT>> instead -- float cells only, the
+// other members are not read.
+struct CnRule { float scale, offset; int a, b; int kind = LDPC_CN_MINSUM; };
 
 // The decoder for a validated context configuration (api.cc ldpc_ctx_create_cfg), on the calling thread's current device, whose
 // graph tables are `tabs`.  nullptr + set_error when no kernel serves the configuration or creating it failed.  llr_qscale: the

@@ -467,8 +467,10 @@ ldpc_ecc *ldpc_ecc_create_replicas(const char *codes_dir, const char *code_name,
         int dtype = LDPC_F32;
         auto ends = [&](const char *suf) { size_t n = strlen(suf); return dec.size() > n && dec.compare(dec.size() - n, n, suf) == 0; };
         // the check-node rule of hip-minsum-layered, after the dtype suffix: [-s<decimal>][-o<decimal>] (cn_scale, cn_offset of ldpc_ctx_config)
+        // ... or -amin, the A-min* rule (cn_rule = LDPC_CN_AMINSTAR), in the same place: it has no scale and no offset, so neither suffix goes with it
         float cn_scale = 0.f, cn_offset = 0.f;
-        bool has_rule = false;
+        bool has_rule = false, amin = false;
+        if (ends("-amin")) { amin = true; dec.resize(dec.size() - 5); }
         for (const char tag : {'o', 's'}) {
             const size_t d = dec.rfind('-');
             if (d == std::string::npos || d + 2 >= dec.size() || dec[d + 1] != tag) continue;
@@ -480,6 +482,11 @@ ldpc_ecc *ldpc_ecc_create_replicas(const char *codes_dir, const char *code_name,
             has_rule = true;
             dec.resize(d);
         }
+        if (!amin && has_rule && ends("-amin")) { amin = true; dec.resize(dec.size() - 5); }
+        if (amin && has_rule) {
+            set_error(LDPC_ENOTFOUND, "decoder '%s' is not provided by libldpc_hip (-amin, the A-min* rule, has no scale and no offset: no -s<scale> / -o<offset> with it)", xs[1].c_str());
+            return nullptr;
+        }
         if (ends("-f16pk")) { dtype = LDPC_F16PK; dec.resize(dec.size() - 6); }   // packed fp16 arithmetic, two frames per lane (min-sum)
         else if (ends("-f64")) { dtype = LDPC_F64; dec.resize(dec.size() - 4); }
         else if (ends("-f16")) { dtype = LDPC_F16; dec.resize(dec.size() - 4); }
@@ -489,6 +496,10 @@ ldpc_ecc *ldpc_ecc_create_replicas(const char *codes_dir, const char *code_name,
         bool as_bool = false;   // "-bool": take H as a plain Boolean matrix (the Haskell binding's `Matrix Bool` flavour, haskell/.../HIP.hs)
         if (ends("-bool")) { as_bool = true; dec.resize(dec.size() - 5); }
         if (ends("-layered")) { schedule = LDPC_SCHED_LAYERED; dec.resize(dec.size() - 8); }   // extension: row-layered schedule
+        if (amin && !(dec == "hip-minsum" && schedule == LDPC_SCHED_LAYERED)) {
+            set_error(LDPC_ENOTFOUND, "decoder '%s' is not provided by libldpc_hip (the rule suffix -amin belongs to hip-minsum-layered[-bool][-f32|-f16])", xs[1].c_str());
+            return nullptr;
+        }
         if (has_rule && !(dec == "hip-minsum" && schedule == LDPC_SCHED_LAYERED)) {
             set_error(LDPC_ENOTFOUND, "decoder '%s' is not provided by libldpc_hip (the rule suffix -s<scale> / -o<offset> belongs to hip-minsum-layered[-bool][-f32|-f16|-i8])", xs[1].c_str());
             return nullptr;
@@ -609,7 +620,7 @@ ldpc_ecc *ldpc_ecc_create_replicas(const char *codes_dir, const char *code_name,
                 ldpc_ctx_config cfg{};
                 cfg.struct_size = sizeof(cfg); cfg.device = devices ? devices[i] : -1; cfg.variant = variant; cfg.dtype = dtype; cfg.max_batch = max_batch;
                 cfg.path = (sum_order != LDPC_SUM_REFERENCE) ? LDPC_PATH_FLOOD : path; cfg.schedule = schedule; cfg.sum_order = sum_order;
-                cfg.cn_scale = cn_scale; cfg.cn_offset = cn_offset;
+                cfg.cn_scale = cn_scale; cfg.cn_offset = cn_offset; cfg.cn_rule = amin ? LDPC_CN_AMINSTAR : LDPC_CN_MINSUM;
                 r->ctx = ldpc_ctx_create_cfg(e->code, &cfg);
                 ldpc_ecc_replica *rp = r.get();
                 e->reps.push_back(std::move(r));      // owned by the record from here on (ldpc_ecc_destroy frees it)

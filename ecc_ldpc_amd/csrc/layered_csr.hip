@@ -36,6 +36,17 @@
 //   int8 cells:  n = min(max(((a m + 8) >> 4) - b, 0), 511), a = clip(rint(16 alpha), 1, 16), b = rint(beta qscale): integers only.
 // Nothing per edge: a subtract and a select (int8: a max and a min) per minimum, two minima per row.  The nine layered_csr_kernel
 // plain instances are instruction for instruction what they were before the rule existed (profiles/r10_layered_rule_default_ab.txt).
+// THE A-MIN* RULE (ldpc_ctx_config cn_rule = LDPC_CN_AMINSTAR; Jones, Valles, Smith, Villasenor 2003; specification
+// tests/layered_aminstar_spec.py, reproduced bit for bit).  layered_csr_kernel<D, MinStar<LT>>, LT = _Float16 or float: the same kernel
+// compiled with RULE = kRuleAMinStar.  A-min* sends two magnitudes per row, like min-sum -- Delta, the box-plus of every |t| but the least,
+// to the arg-min edge, and n1 = Delta [+] m1 to every other edge -- so the row record {c1 = n1, c2 = Delta, signs | arg-min} is what it was
+// and nothing of the soft output, the decode state or the HBM traffic changes.  What changes in a row: the first pass keeps the arg-min BY
+// INDEX (the first edge with the least |t|: a strict compare and two selects per edge in place of med3 + min), a serial fold of
+// a [+] b = max(min(a, b) + c(a + b) - c(|a - b|), 0), c(x) = max(0.625 - x / 4, 0), over the other edges (a min, three adds / subtracts,
+// two multiplies, two subtracts from a constant and three compare-selects per edge, each rounded on its own: no transcendental, no table),
+// and the write loop picks the magnitude by index -- an edge that ties with m1 takes n1, which here differs from Delta.  A row of weight 2
+// is exact.  The 54 instances without it are instruction for instruction what they were (tools/same_kernels.py against a build of the
+// parent commit; profiles/r23_aminstar.txt).
 // THE SOFT OUTPUT (ldpc_decode_batch_dev_soft; specification tests/soft_output_spec.py, reproduced bit for bit).  In a layered schedule the
 // lam cells in LDS ARE the posterior, so the output is an epilogue of the frame: lam as it stands when the frame stops -- converged, out of
 // sweeps or vetoed alike --, or that less the channel LLR as the cell took it in, read from memory again; f32, fp16 or int8 out.  It lives in
@@ -85,8 +96,12 @@ struct CsrRule { float scale, offset; int a, b; };
 // the kernel's second template argument: the lam cell's type -- _Float16, float, int8_t: the 3/4 --, or Ruled<that type>: the same
 // kernel with the context's rule in place of the 3/4 (a compile-time flag: the plain instances hold no trace of it)
 template <typename LT> struct Ruled {};
-template <typename X> struct CellOf { typedef X type; static constexpr bool rule = false; };
-template <typename X> struct CellOf<Ruled<X>> { typedef X type; static constexpr bool rule = true; };
+// ... or MinStar<_Float16 / float>: the same kernel with the A-min* row (see THE A-MIN* RULE above) in place of the two minima
+template <typename LT> struct MinStar {};
+enum { kRule34 = 0, kRuleScaled = 1, kRuleAMinStar = 2 };
+template <typename X> struct CellOf { typedef X type; static constexpr int rule = kRule34; };
+template <typename X> struct CellOf<Ruled<X>> { typedef X type; static constexpr int rule = kRuleScaled; };
+template <typename X> struct CellOf<MinStar<X>> { typedef X type; static constexpr int rule = kRuleAMinStar; };
 
 struct CsrLayArgs {
     const void *llr; int llr_fmt;   // [batch][N]
@@ -177,6 +192,7 @@ template <typename LT> __device__ __forceinline__ __attribute__((address_space(3
 // ---- int8 lam (LDPC_I8): the quantiser of tests/layered_i8_spec.py, the frame's way in and out, the row in integers
 template <> struct Cell<int8_t> { typedef uint2 vec8; typedef CsrRecI8 Rec; };      // (eight cells: the bytes of two words)
 template <typename LT> struct Cell<Ruled<LT>> : Cell<LT> {};                         // (the rule changes no cell and no record)
+template <typename LT> struct Cell<MinStar<LT>> : Cell<LT> {};
 
 __device__ __forceinline__ int quant_i8(float v, float qs) {
     const float r = __builtin_rintf(v * qs);           // ONE float multiply (no contraction), ties to even
@@ -255,8 +271,24 @@ __device__ __forceinline__ float rule_mag(float m, float alpha, float beta) {
     return n < 0.f ? 0.f : n;
 }
 
+// the A-min* rule's correction c(x) = max(0.625 - x / 4, 0), the two-segment fit of log(1 + exp(-x)), and a [+] b = max(min(a, b) + c(a + b)
+// - c(|a - b|), 0) for two magnitudes: every operation rounded on its own (no fused multiply-add), compare-selects so that a NaN stays one.
+// c is non-increasing and a + b >= |a - b|, so a [+] b <= min(a, b); the operands commute bit for bit
+__device__ __forceinline__ float amin_corr(float x) {
+#pragma clang fp contract(off)
+    const float p = 0.25f * x;
+    const float n = 0.625f - p;
+    return n < 0.f ? 0.f : n;
+}
+__device__ __forceinline__ float boxplus(float a, float b) {
+#pragma clang fp contract(off)
+    const float s = fminf(a, b) + amin_corr(a + b);
+    const float n = s - amin_corr(fabsf(a - b));
+    return n < 0.f ? 0.f : n;
+}
+
 // one check row in 32-bit integers (tests/layered_i8_spec.py row_update); same table walk, same meta word as csr_row below
-template <typename LT, int D, bool EXACT, bool FIRST, bool RULE>
+template <typename LT, int D, bool EXACT, bool FIRST, int RULE>
 __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint32_t lam0, const CsrRecI8 &in, CsrRecI8 &out, bool &odd, bool &flip, CsrRule rule) {
     uint32_t ad[D];
     int t[D];
@@ -291,7 +323,7 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
     }
     odd |= (__builtin_popcount(hl) & 1) != 0;
     int n1, n2;
-    if constexpr (RULE) {   // a / 16 rounded half up, less b, in 0..511 (the cap: at a = 16 no induction keeps a magnitude below 2^9)
+    if constexpr (RULE == kRuleScaled) {   // a / 16 rounded half up, less b, in 0..511 (the cap: at a = 16 no induction keeps a magnitude below 2^9)
         n1 = min(max(((rule.a * m1 + 8) >> 4) - rule.b, 0), 511); n2 = min(max(((rule.a * m2 + 8) >> 4) - rule.b, 0), 511);
     } else {
         n1 = (3 * m1 + 2) >> 2; n2 = (3 * m2 + 2) >> 2;             // 3/4, rounded half up
@@ -318,7 +350,7 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
 
 // one check row: layered_lds.hip lds_row with the row's weight per LANE (deg <= D; EXACT: every lane's row has weight D).  cp: this
 // lane's entry of edge 0 in the column table, edge k at cp[k T]; wd: the heaviest row of the wave (entries past it are not read).
-template <typename LT, int D, bool EXACT, bool FIRST, bool RULE>
+template <typename LT, int D, bool EXACT, bool FIRST, int RULE>
 __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint32_t lam0, const CsrRec &in, CsrRec &out, bool &odd, bool &flip, CsrRule rule) {
     uint32_t ad[D];
     float l[D], t[D];
@@ -334,7 +366,9 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
     for (int k = 0; k < D; k++) l[k] = (float)*lds_cell<LT>(ad[k]);
     bool par = false;
     uint32_t X = 0;
-    float m1 = INFINITY, m2 = INFINITY;
+    float m1 = INFINITY;
+    [[maybe_unused]] float m2 = INFINITY;
+    [[maybe_unused]] uint32_t imin = 0;                 // (A-min*) the arg-min edge
     const uint32_t oidx = in.meta >> 27;
 #pragma unroll
     for (int k = 0; k < D; k++) {
@@ -348,13 +382,33 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
             t[k] = l[k] - old;
             X ^= __float_as_uint(t[k]);
             const float a = fabsf(t[k]);
-            m2 = __builtin_amdgcn_fmed3f(m1, m2, a);
-            m1 = fminf(m1, a);
+            if constexpr (RULE == kRuleAMinStar) {          // the arg-min by index: the FIRST edge with the least |t|
+                const bool lt = a < m1;
+                imin = lt ? (uint32_t)k : imin;
+                m1 = lt ? a : m1;
+            } else {
+                m2 = __builtin_amdgcn_fmed3f(m1, m2, a);
+                m1 = fminf(m1, a);
+            }
         } else t[k] = INFINITY;
     }
     odd |= par;
     float n1, n2;
-    if constexpr (RULE) {
+    if constexpr (RULE == kRuleAMinStar) {
+        // n2 = Delta, the [+] of every |t_k| but the arg-min's, folded in ascending k from the first such edge (edge 0, or edge 1 when
+        // the arg-min is edge 0); n1 = Delta [+] m1.  A row of weight 2 is exact: Delta is the other edge's |t|, n1 = m1
+        float dl = fabsf(imin == 0 ? t[1] : t[0]);
+#pragma unroll
+        for (int k = 1; k < D; k++) {
+            if (EXACT || k < deg) {
+                const float nd = boxplus(dl, fabsf(t[k]));
+                dl = ((uint32_t)k == imin || (k == 1 && imin == 0)) ? dl : nd;
+            }
+        }
+        n2 = dl;
+        if constexpr (EXACT && D == 2) n1 = m1;
+        else n1 = deg <= 2 ? m1 : boxplus(dl, m1);
+    } else if constexpr (RULE == kRuleScaled) {
         n1 = rule_mag(m1, rule.scale, rule.offset); n2 = rule_mag(m2, rule.scale, rule.offset);
     } else {
         n1 = 0.75f * m1; n2 = 0.75f * m2;               // |(-3/4) * acc|: the one rounding of Min.hs:78
@@ -366,7 +420,9 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
 #pragma unroll
     for (int k = 0; k < D; k++) {
         if (EXACT || k < deg) {
-            const bool ismin = fabsf(t[k]) == m1;           // ties: n2 == n1, either answer gives the same message
+            bool ismin;
+            if constexpr (RULE == kRuleAMinStar) ismin = (uint32_t)k == imin;   // by index: a tie with m1 elsewhere takes n1, which is not n2 here
+            else ismin = fabsf(t[k]) == m1;                 // ties: n2 == n1, either answer gives the same message
             const uint32_t nmb = __builtin_amdgcn_bitop3_b32(ismin ? c2 : c1, __float_as_uint(t[k]), 0x80000000u, 0x78);   // a ^ (b & c)
             nidx = ismin ? (uint32_t)k : nidx;
             tsig = __builtin_amdgcn_alignbit(tsig, __float_as_uint(t[k]), 31);
@@ -380,7 +436,7 @@ __device__ __forceinline__ void csr_row(const uint16_t *cp, int T, int wd, uint3
 }
 
 // the instance for a wave: wd = its heaviest row, uni = all its rows have that weight
-template <typename LT, int DCLASS, bool FIRST, bool RULE>
+template <typename LT, int DCLASS, bool FIRST, int RULE>
 __device__ __forceinline__ void csr_row_at(const uint16_t *cp, int T, int wd, bool uni, uint32_t lam0, const typename Cell<LT>::Rec &in,
                                            typename Cell<LT>::Rec &out, bool &odd, bool &flip, CsrRule rule) {
     if (uni) {
@@ -478,11 +534,15 @@ template <typename LT> using csr_kernel_t = void (*)(CsrLayDev, typename Cell<LT
 template <typename LT> csr_kernel_t<LT> kernel_for(int dclass) {
     return dclass == 8 ? layered_csr_kernel<8, LT> : dclass == 20 ? layered_csr_kernel<20, LT> : layered_csr_kernel<32, LT>;
 }
-const void *pick_kernel(int dclass, int dtype, bool rule) {
+const void *pick_kernel(int dclass, int dtype, int rule) {
+    if (rule == kRuleAMinStar) return dtype == LDPC_F32 ? (const void *)kernel_for<MinStar<float>>(dclass) : (const void *)kernel_for<MinStar<_Float16>>(dclass);
     if (rule) return dtype == LDPC_F32 ? (const void *)kernel_for<Ruled<float>>(dclass) : dtype == LDPC_I8 ? (const void *)kernel_for<Ruled<int8_t>>(dclass) : (const void *)kernel_for<Ruled<_Float16>>(dclass);
     return dtype == LDPC_F32 ? (const void *)kernel_for<float>(dclass) : dtype == LDPC_I8 ? (const void *)kernel_for<int8_t>(dclass) : (const void *)kernel_for<_Float16>(dclass);
 }
-template <typename LT> void launch(int dclass, bool rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, void *rec, const CsrLayArgs &a) {
+template <typename LT> void launch(int dclass, int rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, void *rec, const CsrLayArgs &a) {
+    if constexpr (!std::is_same<LT, int8_t>::value) {
+        if (rule == kRuleAMinStar) { hipLaunchKernelGGL(kernel_for<MinStar<LT>>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a); return; }
+    }
     if (rule) hipLaunchKernelGGL(kernel_for<Ruled<LT>>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a);
     else hipLaunchKernelGGL(kernel_for<LT>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a);
 }
@@ -491,11 +551,15 @@ template <typename LT> using csr_soft_kernel_t = void (*)(CsrLayDev, typename Ce
 template <typename LT> csr_soft_kernel_t<LT> soft_kernel_for(int dclass) {
     return dclass == 8 ? layered_csr_soft_kernel<8, LT> : dclass == 20 ? layered_csr_soft_kernel<20, LT> : layered_csr_soft_kernel<32, LT>;
 }
-const void *pick_soft_kernel(int dclass, int dtype, bool rule) {
+const void *pick_soft_kernel(int dclass, int dtype, int rule) {
+    if (rule == kRuleAMinStar) return dtype == LDPC_F32 ? (const void *)soft_kernel_for<MinStar<float>>(dclass) : (const void *)soft_kernel_for<MinStar<_Float16>>(dclass);
     if (rule) return dtype == LDPC_F32 ? (const void *)soft_kernel_for<Ruled<float>>(dclass) : dtype == LDPC_I8 ? (const void *)soft_kernel_for<Ruled<int8_t>>(dclass) : (const void *)soft_kernel_for<Ruled<_Float16>>(dclass);
     return dtype == LDPC_F32 ? (const void *)soft_kernel_for<float>(dclass) : dtype == LDPC_I8 ? (const void *)soft_kernel_for<int8_t>(dclass) : (const void *)soft_kernel_for<_Float16>(dclass);
 }
-template <typename LT> void launch_soft(int dclass, bool rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, void *rec, const CsrLayArgs &a, const CsrSoftArgs &so) {
+template <typename LT> void launch_soft(int dclass, int rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, void *rec, const CsrLayArgs &a, const CsrSoftArgs &so) {
+    if constexpr (!std::is_same<LT, int8_t>::value) {
+        if (rule == kRuleAMinStar) { hipLaunchKernelGGL(soft_kernel_for<MinStar<LT>>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a, so); return; }
+    }
     if (rule) hipLaunchKernelGGL(soft_kernel_for<Ruled<LT>>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a, so);
     else hipLaunchKernelGGL(soft_kernel_for<LT>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a, so);
 }
@@ -504,11 +568,15 @@ template <typename LT> using csr_cont_kernel_t = void (*)(CsrLayDev, CsrLayArgs,
 template <typename LT> csr_cont_kernel_t<LT> cont_kernel_for(int dclass) {
     return dclass == 8 ? layered_csr_cont_kernel<8, LT> : dclass == 20 ? layered_csr_cont_kernel<20, LT> : layered_csr_cont_kernel<32, LT>;
 }
-const void *pick_cont_kernel(int dclass, int dtype, bool rule) {
+const void *pick_cont_kernel(int dclass, int dtype, int rule) {
+    if (rule == kRuleAMinStar) return dtype == LDPC_F32 ? (const void *)cont_kernel_for<MinStar<float>>(dclass) : (const void *)cont_kernel_for<MinStar<_Float16>>(dclass);
     if (rule) return dtype == LDPC_F32 ? (const void *)cont_kernel_for<Ruled<float>>(dclass) : dtype == LDPC_I8 ? (const void *)cont_kernel_for<Ruled<int8_t>>(dclass) : (const void *)cont_kernel_for<Ruled<_Float16>>(dclass);
     return dtype == LDPC_F32 ? (const void *)cont_kernel_for<float>(dclass) : dtype == LDPC_I8 ? (const void *)cont_kernel_for<int8_t>(dclass) : (const void *)cont_kernel_for<_Float16>(dclass);
 }
-template <typename LT> void launch_cont(int dclass, bool rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, const CsrLayArgs &a, const CsrSoftArgs &so, const CsrContArgs &k) {
+template <typename LT> void launch_cont(int dclass, int rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, const CsrLayArgs &a, const CsrSoftArgs &so, const CsrContArgs &k) {
+    if constexpr (!std::is_same<LT, int8_t>::value) {
+        if (rule == kRuleAMinStar) { hipLaunchKernelGGL(cont_kernel_for<MinStar<LT>>(dclass), grid, block, lds, st, g, a, so, k); return; }
+    }
     if (rule) hipLaunchKernelGGL(cont_kernel_for<Ruled<LT>>(dclass), grid, block, lds, st, g, a, so, k);
     else hipLaunchKernelGGL(cont_kernel_for<LT>(dclass), grid, block, lds, st, g, a, so, k);
 }
@@ -518,7 +586,7 @@ struct LayeredCsrState : Backend {
     int max_batch = 0, dclass = 8, grid = 0, nslab = 0;
     int dtype = LDPC_F16;       // the lam cell: fp16 (LDPC_F16), float (LDPC_F32) or int8 (LDPC_I8)
     float qscale = 0.f;         // (LDPC_I8) the quantiser's scale
-    bool has_rule = false;      // a check-node rule other than the 3/4: the Ruled instances with `rule`
+    int has_rule = kRule34;     // a check-node rule other than the 3/4: kRuleScaled, the Ruled instances with `rule`; kRuleAMinStar, the MinStar instances
     CsrRule rule{};
     size_t lds = 0;
     CsrLayDev g{};
@@ -545,6 +613,7 @@ struct LayeredCsrState : Backend {
     int decode_soft(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                     uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) override;
     int step(hipStream_t, int, const double *, const double *, const double *, double *, double *, uint8_t *) override {
+        if (has_rule == kRuleAMinStar) return set_error(LDPC_EUNSUPPORTED, "no teacher-forced step with a check-node rule (cn_rule = LDPC_CN_AMINSTAR: the record kernels keep no per-edge messages)");
         if (has_rule) return set_error(LDPC_EUNSUPPORTED, "no teacher-forced step with a check-node rule (cn_scale / cn_offset: the record kernels keep no per-edge messages)");
         return set_error(LDPC_EUNSUPPORTED, dtype == LDPC_I8 ? "no teacher-forced step with LDPC_I8 (fixed-point state; the record kernels keep no per-edge messages)"
                                             : dtype == LDPC_F32 ? "no teacher-forced step on the on-chip layered kernel for any H (the record kernels keep no per-edge messages)"
@@ -573,7 +642,8 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
         // lam stays on-chip for the whole decode in one launch (only the row records travel to HBM): reported as the on-chip path
         s->path = LDPC_PATH_FUSED;
         s->max_batch = max_batch; s->dclass = dclass_of(c.max_row_deg); s->dtype = dtype; s->qscale = qscale;
-        if (cn) { s->has_rule = true; s->rule.scale = cn->scale; s->rule.offset = cn->offset; s->rule.a = cn->a; s->rule.b = cn->b; }
+        if (cn && cn->kind == LDPC_CN_AMINSTAR) s->has_rule = kRuleAMinStar;
+        else if (cn) { s->has_rule = kRuleScaled; s->rule.scale = cn->scale; s->rule.offset = cn->offset; s->rule.a = cn->a; s->rule.b = cn->b; }
         // barrier steps: maximal runs of consecutive layers that share no column
         std::vector<std::vector<int>> steps;
         {
@@ -667,7 +737,8 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
             return nullptr;
         }
         s->g.cols = s->d_cols; s->g.slab = s->d_slab; s->g.wdeg = s->d_wdeg; s->g.step_ptr = s->d_step;
-        if (s->has_rule) snprintf(s->info.name, sizeof(s->info.name), "ldpc::layered_csr_kernel<%d, ldpc::Ruled<%s>>", s->dclass, dtype == LDPC_I8 ? "signed char" : dtype == LDPC_F32 ? "float" : "_Float16");
+        if (s->has_rule == kRuleAMinStar) snprintf(s->info.name, sizeof(s->info.name), "ldpc::layered_csr_kernel<%d, ldpc::MinStar<%s>>", s->dclass, dtype == LDPC_F32 ? "float" : "_Float16");
+        else if (s->has_rule) snprintf(s->info.name, sizeof(s->info.name), "ldpc::layered_csr_kernel<%d, ldpc::Ruled<%s>>", s->dclass, dtype == LDPC_I8 ? "signed char" : dtype == LDPC_F32 ? "float" : "_Float16");
         else snprintf(s->info.name, sizeof(s->info.name), dtype == LDPC_I8 ? "ldpc::layered_csr_kernel<%d, signed char>" : dtype == LDPC_F32 ? "ldpc::layered_csr_kernel<%d, float>" : "ldpc::layered_csr_kernel<%d>", s->dclass);
         snprintf(s->name_plain, sizeof(s->name_plain), "%s", s->info.name);
         {   // "ldpc::layered_csr_kernel<...>" -> "ldpc::layered_csr_soft_kernel<...>"
@@ -682,7 +753,7 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
 
 int LayeredCsrState::decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
                             uint8_t *d_conv, double *d_final, double *d_trace) {
-    if (d_trace) return set_error(LDPC_EUNSUPPORTED, has_rule ? "layered_csr: no per-sweep trace with a check-node rule (cn_scale / cn_offset; decode without one)" : "layered_csr: no per-sweep trace (decode without one)");
+    if (d_trace) return set_error(LDPC_EUNSUPPORTED, has_rule == kRuleAMinStar ? "layered_csr: no per-sweep trace with a check-node rule (cn_rule = LDPC_CN_AMINSTAR; decode without one)" : has_rule ? "layered_csr: no per-sweep trace with a check-node rule (cn_scale / cn_offset; decode without one)" : "layered_csr: no per-sweep trace (decode without one)");
     CsrLayArgs a{};
     if (llr_fmt == LLR_I8 && dtype != LDPC_I8) return set_error(LDPC_EUNSUPPORTED, "int8 LLRs are taken by LDPC_I8 contexts only");
     a.llr = d_llr; a.llr_fmt = llr_fmt; a.qscale = qscale; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final;

@@ -8,9 +8,9 @@
 // LLRs, every sweep reads its records, the epilogue writes the new sum for every frame and the soft output only when S.out is not null.
 // The other two inclusions define LAYERED_CSR_CONT as 0: their preprocessed text is what it was.  In scope there: K, and no rec_all.
     typedef typename CellOf<CELL>::type LT;
-    constexpr bool RULE = CellOf<CELL>::rule;
+    constexpr int RULE = CellOf<CELL>::rule;          // the 3/4, the rule of A.rule, or the A-min* row (which reads no argument)
     CsrRule rule{};
-    if constexpr (RULE) rule = A.rule;
+    if constexpr (RULE == kRuleScaled) rule = A.rule;
     typedef typename Cell<LT>::vec8 cell8;
     typedef typename Cell<LT>::Rec Rec;               // the row record follows the lam cell: 12 bytes (fp16, f32), 8 bytes (int8)
     constexpr bool kInt8 = std::is_same<LT, int8_t>::value;

@@ -14,7 +14,7 @@ Backend *layered_lds_create(const ldpc_code &c, int max_batch);
 // layered_csr.hip: the same for ANY H (column table in device memory, the code's layers merged into barrier steps) -- min-sum with
 // lam stored as fp16 (LDPC_F16, 2 N bytes of LDS) or as f32 (LDPC_F32, 4 N bytes: N <= 40 952; with the non-finite veto), or the
 // int8 fixed-point decoder (LDPC_I8, N bytes; llr_qscale: its quantiser's scale); lam never leaves the chip, so the context reports
-// LDPC_PATH_FUSED.  rule: a check-node rule other than the 3/4 (backend.h CnRule; layered_csr_kernel<D, Ruled<LT>>), null for the 3/4
+// LDPC_PATH_FUSED.  rule: a check-node rule other than the 3/4 (backend.h CnRule; layered_csr_kernel<D, Ruled<LT>>, or <D, MinStar<LT>> for kind LDPC_CN_AMINSTAR), null for the 3/4
 const char *layered_csr_why_not(const ldpc_code &c, int variant, int dtype);
 Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float llr_qscale = 0.f, const CnRule *rule = nullptr);
 }  // namespace ldpc

@@ -180,6 +180,16 @@ static Backend *frame_per_workgroup(const ldpc_code &c, int variant, int dtype, 
 
 Backend *make_backend(const ldpc_code &c, const ldpc_code_dev &tabs, int variant, int dtype, int schedule, int sum_order, int path,
                       int max_batch, float llr_qscale, const CnRule *rule) {
+    if (rule && rule->kind == LDPC_CN_AMINSTAR) {     // the A-min* row: the same family's MinStar instances, float cells only
+        const char *why = dtype == LDPC_I8 ? "LDPC_I8 (an integer A-min* does not exist: LDPC_F16 or LDPC_F32 only)"
+                          : schedule != LDPC_SCHED_LAYERED ? "the flooding schedule (LDPC_SCHED_LAYERED only)"
+                          : variant != LDPC_MINSUM || sum_order != LDPC_SUM_REFERENCE ? "any variant but LDPC_MINSUM (the tanh rule and the parity modes have a check-node rule of their own)"
+                          : dtype != LDPC_F16 && dtype != LDPC_F32 ? "this dtype (LDPC_F16 or LDPC_F32 only)"
+                          : path == LDPC_PATH_FLOOD ? "LDPC_PATH_FLOOD (lam is kept on-chip: LDPC_PATH_AUTO or LDPC_PATH_FUSED)"
+                          : layered_csr_why_not(c, variant, dtype);
+        if (why) { set_error(LDPC_EUNSUPPORTED, "cn_rule = LDPC_CN_AMINSTAR (the A-min* check-node rule) does not serve this request: %s", why); return nullptr; }
+        return layered_csr_create(c, dtype, max_batch, 0.f, rule);
+    }
     if (rule) {     // a check-node rule other than the 3/4: layered min-sum in csrc/layered_csr.hip (layered_csr_kernel<D, Ruled<LT>>), nothing else
         const char *why = schedule != LDPC_SCHED_LAYERED ? "the flooding schedule (its kernels compute 3/4 min, always; LDPC_SCHED_LAYERED only)"
                           : variant != LDPC_MINSUM || sum_order != LDPC_SUM_REFERENCE ? "any rule but min-sum (the tanh rule and the parity modes have no scale or offset)"

@@ -231,7 +231,26 @@ ldpc_ctx *ldpc_ctx_create_on(const ldpc_code *code, int device, int variant, int
  * LDPC_PATH_AUTO or LDPC_PATH_FUSED and LDPC_F16, LDPC_F32 or LDPC_I8, on any code within that kernel's limits (rows of weight
  * 2..27, N <= 65 535, f32 lam N <= 40 952; a quasi-cyclic code is taken as its CSR form with its layers), reports LDPC_PATH_FUSED and
  * ldpc::layered_csr_kernel<D, ldpc::Ruled<LT>>; the flooding schedule, tanh and the parity modes, LDPC_F64, LDPC_F16PK, LDPC_PATH_FLOOD,
- * ldpc_debug_step and ldpc_decode_trace are LDPC_EUNSUPPORTED with a message that names the rule. */
+ * ldpc_debug_step and ldpc_decode_trace are LDPC_EUNSUPPORTED with a message that names the rule.
+ * THE A-MIN* CHECK-NODE RULE (cn_rule = LDPC_CN_AMINSTAR; extension, no reference counterpart; Jones, Valles, Smith, Villasenor 2003).
+ * The same kernel family also exists with a row that approximates the sum-product rule and still sends only TWO magnitudes, so that the
+ * row record, the soft output and the decode state are what they are.  In float32, every operation rounded on its own:
+ *   c(x)  = n = 0.625f - fl(0.25f * x), then n < 0 ? 0 : n                                  (a compare-select: a NaN stays a NaN)
+ *   a [+] b = s = fl(min(a, b) + c(fl(a + b))), n = fl(s - c(|fl(a - b)|)), then n < 0 ? 0 : n
+ * For a row with differences t_k = lam[c_k] - old msg_k, edges in CSR order: i* = the FIRST k with the least |t_k|, m1 = |t_i*|;
+ * Delta = the left fold of [+] over |t_k|, k != i*, in ascending k from the first such edge; n1 = Delta [+] m1.  The message magnitude
+ * is Delta on edge i* and n1 on every other edge (an edge that ties with m1 included); a row of weight 2 is exact (the arg-min edge gets
+ * the other's |t|, the other gets m1, no [+]).  a [+] b <= min(a, b), so magnitudes are bounded as for cn_scale = 1.  Signs, the parity /
+ * flip / stop rule, lam writes (LDPC_F16 saturates and rounds, LDPC_F32 keeps the float and vetoes what is not finite), final_lam, the
+ * soft output and the decode state are unchanged.  Specification: tests/layered_aminstar_spec.py, reproduced bit for bit.
+ * cn_rule = LDPC_CN_MINSUM (0, or absent) is everything said above.  With LDPC_CN_AMINSTAR cn_scale and cn_offset must be 0 or absent
+ * (LDPC_EINVAL otherwise; an unknown cn_rule is LDPC_EINVAL too).  It is accepted exactly where another (cn_scale, cn_offset) is, less
+ * LDPC_I8 -- LDPC_MINSUM, LDPC_SCHED_LAYERED, LDPC_PATH_AUTO or LDPC_PATH_FUSED, LDPC_F16 or LDPC_F32, any code within the kernel's
+ * limits --, reports LDPC_PATH_FUSED and ldpc::layered_csr_kernel<D, ldpc::MinStar<LT>>; LDPC_I8, the flooding schedule, tanh and the
+ * parity modes, LDPC_F64, LDPC_F16PK, LDPC_PATH_FLOOD, ldpc_debug_step and ldpc_decode_trace are LDPC_EUNSUPPORTED with a message that
+ * names cn_rule.  ldpc_decode_batch_dev_soft, ldpc_decode_state_* and ldpc_decode_batch_dev_continue serve such a context like any other
+ * of the family; the state's layout is unchanged. */
+enum ldpc_cn_rule { LDPC_CN_MINSUM = 0, LDPC_CN_AMINSTAR = 1 };
 typedef struct {
     size_t struct_size;
     int device, variant, dtype, max_batch, path, schedule;
@@ -242,14 +261,18 @@ typedef struct {
                          LDPC_I8: rint(16 alpha) must not be 0 (LDPC_EINVAL) */
     float cn_offset;  /* beta, in LLR units; read when struct_size covers it; 0 or absent: none; anything else must be finite and >= 0
                          (LDPC_EINVAL); LDPC_I8: rint(beta * llr_qscale) must not exceed 127 (LDPC_EINVAL) */
+    int cn_rule;      /* ldpc_cn_rule; read when struct_size covers it, else LDPC_CN_MINSUM; LDPC_CN_AMINSTAR wants cn_scale = cn_offset = 0 */
 } ldpc_ctx_config;
 ldpc_ctx *ldpc_ctx_create_cfg(const ldpc_code *code, const ldpc_ctx_config *cfg);
 int ldpc_ctx_schedule(const ldpc_ctx *ctx);
 float ldpc_ctx_llr_qscale(const ldpc_ctx *ctx);   /* the quantiser's scale of an LDPC_I8 context, 0 for every other dtype */
 /* the min-sum check-node rule the context really computes with: 0.75 and 0 unless configured; the float32 values of the fields for
- * LDPC_F16 / LDPC_F32; the quantised ones, a / 16 and b / llr_qscale, for LDPC_I8; 0 and 0 on a context of the tanh rule */
+ * LDPC_F16 / LDPC_F32; the quantised ones, a / 16 and b / llr_qscale, for LDPC_I8; 0 and 0 on a context of the tanh rule and on an
+ * A-min* context (neither has a scale or an offset) */
 float ldpc_ctx_cn_scale(const ldpc_ctx *ctx);
 float ldpc_ctx_cn_offset(const ldpc_ctx *ctx);
+/* LDPC_CN_AMINSTAR on an A-min* context, LDPC_CN_MINSUM on every other */
+int ldpc_ctx_cn_rule(const ldpc_ctx *ctx);
 const ldpc_code *ldpc_ctx_code(const ldpc_ctx *ctx);
 int ldpc_ctx_max_batch(const ldpc_ctx *ctx);
 int ldpc_ctx_device(const ldpc_ctx *ctx);
@@ -990,7 +1013,9 @@ ldpc_code *ldpc_code_from_matrix(const ldpc_matrix *m);
  * with <decoder> in {hip-tanh, hip-minsum}[-layered][-bool][-f32|-f64|-f16|-i8] (-i8: hip-minsum-layered only) or hip-tanh-cm-f64 (-bool: H taken as a plain
  * Boolean matrix, the `Matrix Bool` decoders' input).  hip-minsum-layered takes the check-node rule after the dtype suffix:
  * [-s<decimal>][-o<decimal>] = cn_scale, cn_offset of ldpc_ctx_config, e.g. ldpc/hip-minsum-layered-i8-s1-o0.5/<matrix>/<rounds>
- * (<decimal>: digits with at most one point; on any other decoder name the suffix makes the name unknown: LDPC_ENOTFOUND).  The reference's own decoder names are accepted as aliases, so a
+ * (<decimal>: digits with at most one point; on any other decoder name the suffix makes the name unknown: LDPC_ENOTFOUND), or, in the same
+ * place and instead of them, -amin = cn_rule LDPC_CN_AMINSTAR, e.g. ldpc/hip-minsum-layered-f16-amin/<matrix>/<rounds> (-amin together
+ * with -s / -o, or on another decoder name: LDPC_ENOTFOUND; with -i8: the context's LDPC_EUNSUPPORTED).  The reference's own decoder names are accepted as aliases, so a
  * command line written for it runs unchanged: reference, sparse -> hip-tanh-bool; min, sparsemin -> hip-minsum-bool;
  * arraylet, cuda-arraylet1, cuda-arraylet2, two-arrays, cuda-arraylet-cm -> hip-tanh; arraylet-min -> hip-minsum;
  * arraylet-cm -> hip-tanh-cm-f64 (a dtype suffix may follow: ldpc/reference-f64/...).  The ECC keeps the name it was
