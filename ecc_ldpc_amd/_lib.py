@@ -40,7 +40,7 @@ class FadingStruct(C.Structure):   # ldpc_fading
 
 # every symbol include/ldpc_hip.h declares (tests/test_abi.py checks the library exports them all)
 ABI_SYMBOLS = [
-    "ldpc_init", "ldpc_decode_batch_dev_soft", "ldpc_decode_state_create", "ldpc_decode_state_destroy", "ldpc_decode_state_frames", "ldpc_decode_state_bytes", "ldpc_decode_state_reset", "ldpc_decode_batch_dev_continue", "ldpc_demap_dev_il_apriori", "ldpc_shutdown", "ldpc_current_device", "ldpc_ctx_create_on", "ldpc_sim_create_on", "ldpc_ctx_create_cfg", "ldpc_ctx_schedule", "ldpc_ctx_code", "ldpc_ctx_max_batch", "ldpc_ctx_device",
+    "ldpc_init", "ldpc_decode_batch_dev_soft", "ldpc_decode_state_create", "ldpc_decode_state_destroy", "ldpc_decode_state_frames", "ldpc_decode_state_bytes", "ldpc_decode_state_reset", "ldpc_decode_batch_dev_continue", "ldpc_cascade_create", "ldpc_cascade_destroy", "ldpc_cascade_capacity", "ldpc_cascade_bytes", "ldpc_cascade_decode_dev", "ldpc_demap_dev_il_apriori", "ldpc_shutdown", "ldpc_current_device", "ldpc_ctx_create_on", "ldpc_sim_create_on", "ldpc_ctx_create_cfg", "ldpc_ctx_schedule", "ldpc_ctx_code", "ldpc_ctx_max_batch", "ldpc_ctx_device",
     "ldpc_batcher_create", "ldpc_batcher_destroy", "ldpc_batcher_decode_one", "ldpc_batcher_stats",
     "ldpc_ecc_create_replicas", "ldpc_ecc_replicas", "ldpc_ecc_ctx_at", "ldpc_ecc_sim_at", "ldpc_ecc_decode_on", "ldpc_ecc_set_coalescing", "ldpc_ecc_coalescing_stats", "ldpc_code_set_layers", "ldpc_code_layers", "ldpc_qc_layer_order", "ldpc_csr_layer_order", "ldpc_last_error", "ldpc_last_error_code", "ldpc_abi_version", "ldpc_device_count",
     "ldpc_code_create_qc", "ldpc_code_create_csr", "ldpc_code_destroy", "ldpc_code_dims", "ldpc_code_csr",
@@ -89,7 +89,7 @@ _lib = None
 # the interpreter is finalising, __del__ does nothing: no hipFree / hipStreamDestroy ever runs from a finaliser during
 # shutdown, when the order against the HIP runtime's own exit handlers is not defined.
 _live = weakref.WeakSet()
-_CLOSE_ORDER = {"ECC": 0, "Batcher": 1, "DecodeState": 1, "Decoder": 2, "Sim": 3, "Code": 4, "Matrix": 5, "PinnedArray": 6, "Modulation": 7, "Interleaver": 8}
+_CLOSE_ORDER = {"ECC": 0, "Batcher": 1, "DecodeState": 1, "Cascade": 1, "Decoder": 2, "Sim": 3, "Code": 4, "Matrix": 5, "PinnedArray": 6, "Modulation": 7, "Interleaver": 8}
 _closed_all = False
 
 
@@ -216,6 +216,14 @@ def lib():
     L.ldpc_decode_state_bytes.restype = C.c_size_t
     L.ldpc_decode_state_bytes.argtypes = [vp]
     L.ldpc_decode_state_reset.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.ldpc_cascade_create.restype = vp
+    L.ldpc_cascade_create.argtypes = [vp, vp, C.c_int]
+    L.ldpc_cascade_destroy.restype = None
+    L.ldpc_cascade_destroy.argtypes = [vp]
+    L.ldpc_cascade_capacity.argtypes = [vp]
+    L.ldpc_cascade_bytes.restype = C.c_size_t
+    L.ldpc_cascade_bytes.argtypes = [vp]
+    L.ldpc_cascade_decode_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.ldpc_decode_batch_dev_continue.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp]
     L.ldpc_ctx_llr_qscale.restype = C.c_float
     L.ldpc_ctx_llr_qscale.argtypes = [vp]
@@ -844,6 +852,71 @@ class DecodeState:
     def close(self):
         if self._h:
             lib().ldpc_decode_state_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        if _finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Cascade:
+    """ldpc_cascade: two Decoders in a row -- dec1 decodes the batch, the frames it does not converge on (the first `capacity` in frame
+    order) are decoded again from the channel LLRs by dec2 and take its result.  capacity None: dec2's max_batch.  Close it before its
+    decoders (close_all does)"""
+
+    def __init__(self, dec1, dec2, capacity=None):
+        cap = dec2.max_batch if capacity is None else capacity
+        self._h = lib().ldpc_cascade_create(dec1._h if dec1 is not None else None, dec2._h if dec2 is not None else None, int(cap))
+        if not self._h:
+            raise LdpcError(lib().ldpc_last_error_code(), last_error())
+        self.dec1, self.dec2 = dec1, dec2
+        _register(self)
+
+    @property
+    def capacity(self):
+        return int(lib().ldpc_cascade_capacity(self._h))
+
+    @property
+    def nbytes(self):
+        """the device bytes the cascade holds"""
+        return int(lib().ldpc_cascade_bytes(self._h))
+
+    def decode_batch_dev(self, d_llr_ptr, d_bits_ptr, batch, max_iters1, max_iters2, d_iters_ptr=None, d_conv_ptr=None, d_stage_ptr=None, d_stats_ptr=None, stream=None,
+                         llr_fmt="f32"):
+        """ldpc_cascade_decode_dev: device pointers; d_llr [batch][N] of llr_fmt "f32" / "f16" / "i8"; d_stage [batch] bytes (1 or 2) and
+        d_stats [3] uint32 (failed stage 1, sent to stage 2, sent and failed again) may be None like d_iters and d_conv.  Enqueued on
+        `stream` (None: dec1's own), not synchronised"""
+        check(lib().ldpc_cascade_decode_dev(self._h, int(max_iters1), int(max_iters2), int(batch), d_llr_ptr, _llr_fmt(llr_fmt), d_bits_ptr, d_iters_ptr, d_conv_ptr,
+                                            d_stage_ptr, d_stats_ptr, stream))
+
+    def decode_batch(self, llr, max_iters1, max_iters2):
+        """llr [F][N] float32, float16 or (two "i8" decoders) int8, host -> bits [F][N], iters [F], converged [F], stage [F], stats [3]
+        (through torch tensors on the decoders' device)"""
+        import torch
+        llr = np.ascontiguousarray(llr)
+        fmt = {np.dtype(np.float32): "f32", np.dtype(np.float16): "f16", np.dtype(np.int8): "i8"}[llr.dtype]
+        F, N = llr.shape[0], self.dec1.code.N
+        assert llr.shape == (F, N)
+        dev = torch.device("cuda", lib().ldpc_ctx_device(self.dec1._h))
+        d_llr = torch.from_numpy(llr).to(dev)
+        d_bits = torch.zeros((F, N), dtype=torch.uint8, device=dev)
+        d_iters = torch.zeros(F, dtype=torch.int32, device=dev)
+        d_conv = torch.zeros(F, dtype=torch.uint8, device=dev)
+        d_stage = torch.zeros(F, dtype=torch.uint8, device=dev)
+        d_stats = torch.zeros(3, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.decode_batch_dev(d_llr.data_ptr(), d_bits.data_ptr(), F, max_iters1, max_iters2, d_iters.data_ptr(), d_conv.data_ptr(), d_stage.data_ptr(), d_stats.data_ptr(),
+                              None, fmt)
+        self.dec1.synchronize()
+        return d_bits.cpu().numpy(), d_iters.cpu().numpy(), d_conv.cpu().numpy(), d_stage.cpu().numpy(), d_stats.cpu().numpy().view(np.uint32)
+
+    def close(self):
+        if self._h:
+            lib().ldpc_cascade_destroy(self._h)
         self._h = None
 
     def __del__(self):

@@ -17,6 +17,7 @@
 #include "fading.h"
 #include "ratematch.h"
 #include "bch.h"
+#include "cascade.h"
 #include "crc.h"
 #include "jit.h"
 #include "sim.h"
@@ -1011,6 +1012,91 @@ int ldpc_decode_batch_dev_continue(ldpc_ctx *ctx, ldpc_decode_state *state, int 
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     return ctx->backend->decode_continue(st, state->rec, state->sum, first, max_iters, batch, d_llr, fmt, d_bits, d_iters, d_converged, d_soft, soft_fmt,
                                          soft_qscale == 0.f ? 4.0f : soft_qscale, soft_kind);
+}
+
+// ---- a cascade: two contexts in a row, the frames the first does not converge on decoded again by the second (csrc/cascade.h)
+struct ldpc_cascade {
+    ldpc_ctx *ctx1 = nullptr, *ctx2 = nullptr;
+    uint64_t serial1 = 0, serial2 = 0;   // the contexts' serials: a destroyed context is refused, not touched
+    int capacity = 0, device = 0, N = 0;
+    size_t bytes = 0;
+    char *block = nullptr;               // one device allocation, cut into:
+    void *llr2 = nullptr;                // [capacity][N] of up to 4-byte elements: the compact channel LLRs stage 2 decodes
+    uint8_t *bits2 = nullptr;            // [capacity][N]
+    int32_t *iters2 = nullptr;           // [capacity]
+    uint8_t *conv2 = nullptr;            // [capacity]
+    int32_t *idx = nullptr;              // [capacity]
+    uint32_t *stats = nullptr;           // [3], when the caller passes none
+    int32_t *iters1 = nullptr;           // [ctx1's max_batch], when the caller passes no d_iters
+    uint8_t *conv1 = nullptr;            // [ctx1's max_batch], when the caller passes no d_converged
+};
+
+ldpc_cascade *ldpc_cascade_create(ldpc_ctx *ctx1, ldpc_ctx *ctx2, int capacity) {
+    if (!ctx1 || !ctx2) { set_error(LDPC_EINVAL, "null %s", !ctx1 ? "ctx1" : "ctx2"); return nullptr; }
+    if (ctx1->code->N != ctx2->code->N) { set_error(LDPC_EINVAL, "ctx1 decodes frames of N = %d, ctx2 of N = %d: not one code", ctx1->code->N, ctx2->code->N); return nullptr; }
+    if (ctx1->device != ctx2->device) { set_error(LDPC_EINVAL, "ctx1 is on device %d, ctx2 on device %d", ctx1->device, ctx2->device); return nullptr; }
+    if (capacity < 1 || capacity > ctx2->max_batch) { set_error(LDPC_EINVAL, "capacity %d outside [1,%d] (ctx2's max_batch)", capacity, ctx2->max_batch); return nullptr; }
+    HIPCHK_NULL(hipSetDevice(ctx1->device));
+    ldpc_cascade *c = new (std::nothrow) ldpc_cascade();
+    if (!c) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
+    c->ctx1 = ctx1; c->ctx2 = ctx2; c->serial1 = ctx1->serial; c->serial2 = ctx2->serial;
+    c->capacity = capacity; c->device = ctx1->device; c->N = ctx1->code->N;
+    const size_t cap = (size_t)capacity, N = (size_t)c->N, mb = (size_t)ctx1->max_batch;
+    const size_t part[8] = {cap * N * 4, cap * N, cap * 4, cap, cap * 4, 3 * sizeof(uint32_t), mb * 4, mb};
+    size_t off[8], total = 0;
+    for (int i = 0; i < 8; i++) { off[i] = total; total += (part[i] + 255) & ~(size_t)255; }
+    hipError_t e = hipMalloc((void **)&c->block, total);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error(e == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "ldpc_cascade_create: %zu bytes of device memory for capacity %d (N = %d, ctx1's max_batch %d): %s", total,
+                  capacity, c->N, ctx1->max_batch, hipGetErrorString(e));
+        delete c;
+        return nullptr;
+    }
+    c->bytes = total;
+    c->llr2 = c->block + off[0]; c->bits2 = (uint8_t *)(c->block + off[1]); c->iters2 = (int32_t *)(c->block + off[2]); c->conv2 = (uint8_t *)(c->block + off[3]);
+    c->idx = (int32_t *)(c->block + off[4]); c->stats = (uint32_t *)(c->block + off[5]); c->iters1 = (int32_t *)(c->block + off[6]); c->conv1 = (uint8_t *)(c->block + off[7]);
+    return c;
+}
+
+void ldpc_cascade_destroy(ldpc_cascade *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(c->block);
+    delete c;
+}
+
+int ldpc_cascade_capacity(const ldpc_cascade *c) { return c ? c->capacity : set_error(LDPC_EINVAL, "null cascade"); }
+size_t ldpc_cascade_bytes(const ldpc_cascade *c) { return c ? c->bytes : 0; }
+
+int ldpc_cascade_decode_dev(ldpc_cascade *c, int max_iters1, int max_iters2, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                            uint8_t *d_converged, uint8_t *d_stage, uint32_t *d_stats, void *stream) {
+    if (!c) return set_error(LDPC_EINVAL, "null cascade");
+    if (!ctx_alive(c->serial1) || !ctx_alive(c->serial2)) return set_error(LDPC_EINVAL, "%s of the cascade was destroyed", !ctx_alive(c->serial1) ? "ctx1" : "ctx2");
+    ldpc_ctx *ctx1 = c->ctx1, *ctx2 = c->ctx2;
+    if (max_iters1 < 0 || max_iters2 < 0) return set_error(LDPC_EINVAL, "%s %d < 0", max_iters1 < 0 ? "max_iters1" : "max_iters2", max_iters1 < 0 ? max_iters1 : max_iters2);
+    if (batch < 0 || batch > ctx1->max_batch) return set_error(LDPC_EINVAL, "batch %d outside [0,%d] (ctx1's max_batch)", batch, ctx1->max_batch);
+    if (llr_fmt != LDPC_LLR_F32 && llr_fmt != LDPC_LLR_F16 && llr_fmt != LDPC_LLR_I8) return set_error(LDPC_EINVAL, "llr_fmt %d is not one of LDPC_LLR_F32, LDPC_LLR_F16, LDPC_LLR_I8", llr_fmt);
+    // both stages read the caller's format: refused here, so that no call stops between its stages
+    if (llr_fmt == LDPC_LLR_I8 && (ctx1->dtype != LDPC_I8 || ctx2->dtype != LDPC_I8))
+        return set_error(LDPC_EUNSUPPORTED, "llr_fmt LDPC_LLR_I8: int8 LLRs are accepted by LDPC_I8 contexts only (ctx1's dtype is %d, ctx2's is %d)", ctx1->dtype, ctx2->dtype);
+    if (batch == 0) return LDPC_OK;
+    if (!d_llr || !d_bits) return set_error(LDPC_EINVAL, "null %s", !d_llr ? "d_llr" : "d_bits");
+    const int fmt = packed_format(llr_fmt), es = (int)llr_bytes(fmt);
+    if ((uintptr_t)d_llr % (size_t)es) return set_error(LDPC_EINVAL, "d_llr is not aligned to its %d-byte elements", es);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ctx1->stream;
+    int32_t *iters = d_iters ? d_iters : c->iters1;
+    uint8_t *conv = d_converged ? d_converged : c->conv1;
+    uint32_t *stats = d_stats ? d_stats : c->stats;
+    int rc = decode_dev(ctx1, st, max_iters1, batch, d_llr, fmt, d_bits, iters, conv, nullptr, nullptr);
+    if (rc == LDPC_OK) rc = ldpc::cascade_select_launch(st, batch, c->capacity, conv, c->idx, d_stage, stats);
+    if (rc == LDPC_OK) rc = ldpc::cascade_gather_launch(st, c->N, es, c->capacity, d_llr, c->idx, stats, c->llr2);
+    // stage 2 always decodes `capacity` rows: how many of them are frames is known on the device only
+    if (rc == LDPC_OK) rc = decode_dev(ctx2, st, max_iters2, c->capacity, c->llr2, fmt, c->bits2, c->iters2, c->conv2, nullptr, nullptr);
+    if (rc == LDPC_OK) rc = ldpc::cascade_scatter_launch(st, c->N, c->capacity, c->idx, c->bits2, c->iters2, c->conv2, d_bits, iters, conv, d_stage, stats);
+    return rc;
 }
 
 int ldpc_decode_batch_dev_packed(ldpc_ctx *ctx, int max_iters, int batch, const void *d_llr, int llr_f16, uint8_t *d_packed, int32_t *d_iters,

@@ -430,6 +430,42 @@ int ldpc_decode_state_reset(ldpc_decode_state *st, int first, int count, void *s
 int ldpc_decode_batch_dev_continue(ldpc_ctx *ctx, ldpc_decode_state *st, int first, int max_iters, int batch, const void *d_llr, int llr_fmt,
                                    uint8_t *d_bits, int32_t *d_iters, uint8_t *d_converged, void *d_soft, int soft_fmt, float soft_qscale,
                                    int soft_kind, void *stream);
+/* TWO DECODERS IN A ROW: a batch is decoded by a fast context, and only the frames it did not converge on are decoded again, FROM THE
+ * CHANNEL LLRs, by a second one -- 3/4 min-sum on a quasi-cyclic on-chip kernel and then A-min* on the kernel for any H; int8 and then
+ * f32; min-sum and then tanh; few sweeps and then many.  The failed frames are found, gathered, decoded and put back on the device, on one
+ * stream, with no host round trip.  Specification: tests/cascade_spec.py.  No counterpart in the reference.
+ * A cascade binds ctx1 (stage 1) and ctx2 (stage 2) to a capacity in 1 .. ctx2's max_batch: both on one device, codes of one N.  That the
+ * two codes ARE one code -- a row-permuted, or quasi-cyclic against CSR, form of the same H -- is the caller's duty.  ctx1 == ctx2 is
+ * allowed (the two decodes are ordered on one stream).  The cascade owns the compact LLR buffer (capacity x N x 4 bytes), stage 2's bits,
+ * iters and flags, the index list and the buffers that stand in for NULL arguments; ldpc_cascade_bytes reports the total.  NULL +
+ * LDPC_ENOMEM with the byte count in the message when that allocation fails.  Destroy it BEFORE its contexts; a cascade whose context was
+ * destroyed refuses every call with LDPC_EINVAL.
+ * ONE CALL, ldpc_cascade_decode_dev, decodes batch <= ctx1's max_batch frames; every pointer is DEVICE memory:
+ *   1. stage 1: ctx1's ldpc_decode_batch_dev* of all the frames with max_iters1;
+ *   2. idx = the frames with converged == 0 in ascending frame order, cut to the first `capacity` (a stable compaction: no atomic decides
+ *      the order);
+ *   3. stage 2: ctx2's ldpc_decode_batch_dev* of exactly those frames' channel LLRs with max_iters2;
+ *   4. frames in idx take stage 2's bits, iters and flag ENTIRELY -- one that fails again returns what ctx2 returns for a failed frame --
+ *      and d_stage = 2; every other frame, failed frames beyond `capacity` included, keeps stage 1's result and d_stage = 1;
+ *   5. d_stats [3] = {frames that failed stage 1, frames sent to stage 2 = min(that, capacity), frames sent and still not converged}.
+ * The count stays on the device, so stage 2 always decodes `capacity` rows: the rows past the count are padding with the LLR -1 (f32,
+ * fp16 or int8), the all-zero word, on which every decoder stops before its first sweep.  capacity = batch never overflows; a smaller one
+ * costs less padding.  d_llr [batch][N] of llr_fmt (LDPC_LLR_F32, LDPC_LLR_F16, LDPC_LLR_I8), aligned to its element; d_bits [batch][N];
+ * d_iters, d_converged, d_stage [batch] and d_stats may each be NULL.  Enqueued on `stream` -- ctx2's decode too -- and NOT synchronised;
+ * NULL = ctx1's own stream; ordering as ldpc_decode_batch_dev, and a cascade decodes one batch at a time.
+ * LDPC_EINVAL -- before the device is touched -- for a null handle, N that differs between the contexts, contexts on different devices,
+ * capacity out of range (create); a null cascade, a negative max_iters1 / max_iters2, batch < 0 or above ctx1's max_batch, an unknown
+ * llr_fmt, a null d_llr / d_bits, a misaligned d_llr (the call); the message names the argument.  LDPC_LLR_I8 is LDPC_EUNSUPPORTED unless
+ * BOTH contexts are LDPC_I8 -- checked up front, no call stops between its stages.  batch = 0 succeeds and touches nothing.
+ * Not offered: soft output, packed bits and decode-state variants, more than two stages, and a stage 2 that continues from stage 1's
+ * messages (the two stages need not be one kernel family). */
+typedef struct ldpc_cascade ldpc_cascade;
+ldpc_cascade *ldpc_cascade_create(ldpc_ctx *ctx1, ldpc_ctx *ctx2, int capacity);
+void ldpc_cascade_destroy(ldpc_cascade *c);            /* before its contexts */
+int ldpc_cascade_capacity(const ldpc_cascade *c);
+size_t ldpc_cascade_bytes(const ldpc_cascade *c);
+int ldpc_cascade_decode_dev(ldpc_cascade *c, int max_iters1, int max_iters2, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
+                            uint8_t *d_converged, uint8_t *d_stage /* may be NULL */, uint32_t *d_stats /* [3], may be NULL */, void *stream);
 /* page-locked host memory for the host-pointer entry points.  With llr AND bits buffers from ldpc_host_alloc (or
  * registered with hipHostRegister) ldpc_decode_batch runs zero-copy: the decode kernel itself reads the LLRs and
  * writes the bits over PCIe (10-11 Gbit/s PCIe-inclusive on jpl.4096); pageable buffers go through a chunked
