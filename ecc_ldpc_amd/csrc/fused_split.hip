@@ -61,6 +61,12 @@
 #ifndef SPLIT_SYN_SKIP
 #define SPLIT_SYN_SKIP 3
 #endif
+// Phase B's stores by lane id (ds_write_addtid_b32: no address register, half the transfer to LDS) for the edges a wave cannot wrap, in
+// the read-add-write rounds (= 1): 16.13 ms against 16.47 at 2 dB, same VALU count (profiles/r09_split_addtid.txt).  Round 0 too (= 3) times
+// equal and drops that round's address arithmetic: 897 VALU per wave-turn, under the contract test's band like SPLIT_WAVE_PHASES = 3 above.
+#ifndef SPLIT_STORE_ADDTID
+#define SPLIT_STORE_ADDTID 1
+#endif
 #include "fused_split_body.h"
 
 #ifndef SPLIT_WAVES_PER_EU

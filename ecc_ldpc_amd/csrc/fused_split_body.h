@@ -3,7 +3,7 @@
 // generated_tables.h) and at run time by hiprtc for any other single-circulant quasi-cyclic H (jit.cc: plan and
 // rotation table generated as constexpr structs from the code's description) -- so it includes nothing host-side.
 // The ahead-of-time f32 min-sum instances with whole waves of one frame (sz = 128) are built in a tighter form behind
-// SPLIT_WAVE_SPEC, SPLIT_FLAGS_LDS, SPLIT_NEG_LAM and SPLIT_SYN_SKIP below; all default to off here, so a run-time compiled instance
+// SPLIT_WAVE_SPEC, SPLIT_FLAGS_LDS, SPLIT_NEG_LAM, SPLIT_SYN_SKIP and SPLIT_STORE_ADDTID below; all default to off here, so a run-time compiled instance
 // and the sz = 32 instances compile to what they were.
 // What is not about check rows or column rounds -- LDS layout, lane locator, per-frame workgroup OR, the stores of trace rows,
 // snapshots and results -- is shared with the packed-fp16 and the layered bodies: fused_frame.h.
@@ -49,6 +49,17 @@
 // because that OR is the parities' only use.  If not, the other rows run as before.  0 = off.
 #ifndef SPLIT_SYN_SKIP
 #define SPLIT_SYN_SKIP 0
+#endif
+// Phase B's stores of edges that cannot wrap in their wave as ds_write_addtid_b32 (same instances; needs SPLIT_WAVE_SPEC): the
+// cell of such an edge is lane * 4 + a constant, which that instruction addresses as M0[15:0] + 16-bit offset + 4 * lane with no
+// address VGPR -- the store's transfer to LDS is then one source dword instead of two.  The reads keep their form whatever
+// SPLIT_WAVE_PHASES says; only the store is decided by the wave's own rotations (fused_rows.h WaveRot).  The instruction sits in
+// inline assembly, which the compiler's wait-count pass does not see: split_body waits for lgkmcnt(0) itself before the barrier
+// of every round.  Bits: 1 = in the read-add-write rounds (q >= 1), 2 = in round 0 (lam = msg + channel LLR: no read, so the
+// edge's address arithmetic goes with the register), 0 = off.  4 = timing only, results WRONG: the wrapping edges too (each lands
+// in a cell of its block column that is not its own) -- the upper bound of what 3 can give, tools/build_ablation.sh.
+#ifndef SPLIT_STORE_ADDTID
+#define SPLIT_STORE_ADDTID 0
 #endif
 // wave priority while in phase A (check rows: long stretches of independent VALU work) and in phase B (column
 // rounds: short, LDS-bound, barrier-separated).  Measured on jpl.4096, 65 536 frames: A=0/B=0 20.72 ms,
@@ -187,11 +198,23 @@ struct SplitLds {
 // b4: the address base of the thread -- its byte offset inside a block column (WV < 0), or its LANE's, with the wave's rows
 // folded into the rotations (WV = the wave inside the group, WaveRot).  An edge that cannot wrap is base + immediate and
 // holds no address register; the fence keeps the wrapped addresses of the others from being hoisted out of the turn loop.
-template <typename CT, int VARIANT, int SZ, class Plan, class T, int P, int WV, int Q, int I0, int I1>
+// WVS >= 0 (SPLIT_STORE_ADDTID): the program's wave inside the group whatever WV says, for the stores alone -- an edge that
+// cannot wrap in that wave is stored by lane id (split_store_addtid), and its address register dies with the read.
+// M0_TOO: the chunk's first such store, which also sets M0 to the LDS address of the workgroup's array.  One wait state between the
+// scalar write of M0 and the DS instruction that reads it (without it the instruction takes the old M0): the compiler does not look
+// into inline assembly, so the s_nop is written here, and ecc_ldpc_amd/build.py checks that nothing else in the kernel writes M0.
+template <int OFF, bool M0_TOO>
+__device__ __forceinline__ void split_store_addtid(float v, uint32_t lds_base) {
+    static_assert(OFF >= 0 && OFF < 65536, "16-bit offset field");
+    if constexpr (M0_TOO) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tds_write_addtid_b32 %0 offset:%2" ::"v"(v), "s"(lds_base), "n"(OFF) : "memory");
+    else asm volatile("ds_write_addtid_b32 %0 offset:%1" ::"v"(v), "n"(OFF) : "memory");
+}
+template <typename CT, int VARIANT, int SZ, class Plan, class T, int P, int WV, int WVS, int Q, int I0, int I1>
 __device__ __forceinline__ void split_round_chunk(char *lds, const uint32_t b4, uint32_t vmask, const CT *msg, const CT *orig_rot, const float *gllr, uint32_t r0) {
     using S = Split<Plan, T>;
     using L = SplitLds<CT, VARIANT, Plan, SZ, T>;
     using R = WaveRot<SZ, WV>;
+    using RS = WaveRot<SZ, WVS>;
     constexpr uint32_t ES = sizeof(CT), V = QcGeom<SZ>::V;
     constexpr uint32_t WOFF = WV < 0 ? 0 : WV * 64 * ES;   // own position inside a block column = b4 + WOFF
     constexpr bool NEG = SPLIT_NEG_LAM && kSplitWholeWaves<CT, VARIANT, SZ>;   // LDS (lam and the round-0 copies) holds 0 - lam
@@ -205,6 +228,22 @@ __device__ __forceinline__ void split_round_chunk(char *lds, const uint32_t b4, 
         constexpr uint32_t rot = T::rot[decltype(ec)::value];
         if constexpr (R::nowrap(rot)) return b4 + R::rot(rot) * ES; else return qc_wrap(p4 + R::rot(rot) * ES, vmask);
     };
+    // the store of edge e: by lane id where the program's wave cannot wrap it, else to `at()` (= pos(e))
+    constexpr auto by_lane = [](int e) { return WVS >= 0 && ((SPLIT_STORE_ADDTID & (Q == 0 ? 2 : 1)) != 0) && ((SPLIT_STORE_ADDTID & 4) != 0 || RS::nowrap(T::rot[e])); };
+    constexpr int FIRST = [by_lane] {   // the chunk's first store by lane id
+        for (int i = I0; i < I1; i++) if (by_lane(S::nth(Q, P, i))) return i;
+        return -1;
+    }();
+    auto put = [&](auto ic, auto at, CT v) {
+        constexpr int i = decltype(ic)::value, e = S::nth(Q, P, i);
+        if constexpr (by_lane(e)) {
+            constexpr uint32_t s = RS::nowrap(T::rot[e]) ? RS::rot(T::rot[e]) : RS::rot(T::rot[e]) % 64;   // (% 64: the timing-only form, a cell of the same column)
+            static_assert(s + 63 < V && (T::bc[e] + 1) * V * ES <= (uint32_t)L::LAM_BYTES, "inside the block column, inside lam");
+            split_store_addtid<(int)(T::bc[e] * V * ES + s * ES), i == FIRST>(v, (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)lds);
+        } else {
+            lds_st<CT>(lds + T::bc[e] * V * ES, at(), v);
+        }
+    };
     if constexpr (Q == 0) {
         static_for<I0, I1>([&](auto ic) {
             // (constexpr VARIABLES: a constexpr function call in a subscript is not a constant expression and was
@@ -214,7 +253,7 @@ __device__ __forceinline__ void split_round_chunk(char *lds, const uint32_t b4, 
             CT o;
             if constexpr (SPLIT_ORIG_REGS && os < L::NOL) o = lds_ld<CT>(lds + L::orig_at(P, os) + WOFF, b4);
             else if constexpr (SPLIT_ORIG_REGS) o = orig_rot[os]; else o = (CT)gllr[T::bc[e] * SZ + ((r0 + T::rot[e]) % SZ)];
-            lds_st<CT>(lds + T::bc[e] * V * ES, pos(std::integral_constant<int, e>{}), NEG ? o - msg[ms] : msg[ms] + o);
+            put(ic, [&] { return pos(std::integral_constant<int, e>{}); }, NEG ? o - msg[ms] : msg[ms] + o);
         });
         return;
     }
@@ -230,16 +269,16 @@ __device__ __forceinline__ void split_round_chunk(char *lds, const uint32_t b4, 
         constexpr int i = decltype(ic)::value;
         constexpr int e = S::nth(Q, P, i);
         constexpr int ms = S::slot(e);
-        lds_st<CT>(lds + T::bc[e] * V * ES, adr[i - I0], NEG ? cur[i - I0] - msg[ms] : msg[ms] + cur[i - I0]);
+        put(ic, [&] { return adr[i - I0]; }, NEG ? cur[i - I0] - msg[ms] : msg[ms] + cur[i - I0]);
     });
     asm volatile("" ::: "memory");
 }
-template <typename CT, int VARIANT, int SZ, class Plan, class T, int P, int WV, int Q, int I0>
+template <typename CT, int VARIANT, int SZ, class Plan, class T, int P, int WV, int WVS, int Q, int I0>
 __device__ __forceinline__ void split_round(char *lds, uint32_t p4, uint32_t vmask, const CT *msg, const CT *orig_rot, const float *gllr, uint32_t r0) {
     constexpr int CNT = Split<Plan, T>::count(Q, P), CH = SZ < 64 ? SPLIT_CH_SMALL : SPLIT_CH;
     if constexpr (I0 < CNT) {
-        split_round_chunk<CT, VARIANT, SZ, Plan, T, P, WV, Q, I0, (I0 + CH < CNT ? I0 + CH : CNT)>(lds, p4, vmask, msg, orig_rot, gllr, r0);
-        split_round<CT, VARIANT, SZ, Plan, T, P, WV, Q, I0 + CH>(lds, p4, vmask, msg, orig_rot, gllr, r0);
+        split_round_chunk<CT, VARIANT, SZ, Plan, T, P, WV, WVS, Q, I0, (I0 + CH < CNT ? I0 + CH : CNT)>(lds, p4, vmask, msg, orig_rot, gllr, r0);
+        split_round<CT, VARIANT, SZ, Plan, T, P, WV, WVS, Q, I0 + CH>(lds, p4, vmask, msg, orig_rot, gllr, r0);
     }
 }
 
@@ -267,6 +306,7 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
     const uint32_t b4 = (tid % (WV < 0 ? VT : 64)) * ES;
     const uint32_t p4 = b4 + (WV < 0 ? 0 : WV * 64) * ES;
     constexpr int WVA = (SPLIT_WAVE_PHASES & 1) ? WV : -1, WVB = (SPLIT_WAVE_PHASES & 2) ? WV : -1;   // per phase: specialised or not
+    constexpr int WVS = (SPLIT_STORE_ADDTID && kSplitWholeWaves<CT, VARIANT, SZ>) ? WV : -1;   // phase B's stores by lane id where this wave cannot wrap
     auto fE_of = [](const Where &w) { return (size_t)(w.valid[0] ? w.frame0 : 0) * Plan::NEDGE * SZ; };   // the frame's messages (step mode)
     const Where w0(p4, A.batch);
     const uint32_t r0 = w0.r0;
@@ -431,7 +471,9 @@ __device__ __forceinline__ void split_body(const FusedArgs &A, char *lds, const 
         if (done != FULL) {
             __builtin_amdgcn_s_setprio(SPLIT_PRIO_B);
             static_for<0, Rounds<T>::num_rounds()>([&](auto qc) {
-                split_round<CT, VARIANT, SZ, Plan, T, P, WVB, decltype(qc)::value, 0>(lds, WVB < 0 ? p4 : b4, vmask, msg, orig, reinterpret_cast<const float *>(A.llr) + fN, r0);
+                split_round<CT, VARIANT, SZ, Plan, T, P, WVB, WVS, decltype(qc)::value, 0>(lds, WVB < 0 ? p4 : b4, vmask, msg, orig, reinterpret_cast<const float *>(A.llr) + fN, r0);
+                // stores by lane id are inline assembly, which the compiler's wait counts do not include: every one has landed before the barrier
+                if constexpr (WVS >= 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __syncthreads();  // the next round adds into the same columns
             });
             __builtin_amdgcn_s_setprio(SPLIT_PRIO_A);
