@@ -61,17 +61,23 @@
 // lam <- cell(C' + S) in the prologue (a reset slot adds +0), the syndrome before the first sweep is that lam's, every sweep reads its
 // records (a zero record is "no old message": t = l - (+0) is l bit for bit), the epilogue writes S <- lam - C' for every frame and the soft
 // output when asked.  The 36 other instances are what they were (profiles/r21_decode_continue.txt).
+// WHERE THINGS ARE.  Which of the 72 instances exist (3 families x 3 row classes x 8 cells), how a context's (dtype, rule, row class) picks
+// one and what each is called is ONE list, instance_of below the kernels; a new cell type or rule is a line there.  The three decodes share
+// one launch path, LayeredCsrState::run, and one residency query.  The graph work -- steps, slabs, the column table, the per-wave weights --
+// is host code of its own, layered_csr_layout.{h,cc}, with a stand-alone driver that runs it under a sanitizer
+// (tools/layered_csr_layout_main.cc, tests/test_layered_csr_layout.py).  Every kernel is the code it was (profiles/r25_layered_csr_host.txt).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <numeric>
-#include <vector>
+#include <string>
 
 #include "demap.h"
+#include "layered_csr_layout.h"
 #include "layered_qc.h"
 #include "ldpc_math.h"
+#include "mod_dispatch.h"
 
 namespace ldpc {
 
@@ -81,9 +87,7 @@ struct CsrRec { float c1, c2; uint32_t meta; };   // meta: bit (deg-1-k) = sign 
 // int8 lam: the two message magnitudes (3/4 min1 in bits 0..15, 3/4 min2 in bits 16..31; both < 2^9) and the same meta word
 struct __attribute__((aligned(8))) CsrRecI8 { uint32_t mags, meta; };
 
-constexpr uint16_t kNoEdge = 0xFFFF;
-
-struct CsrLayDev {
+struct CsrLayDev {             // (the four tables are built by layered_csr_layout.cc, which also defines kNoEdge)
     int N, T, nstep;
     const uint16_t *cols;       // per slab, [edge k < slab weight][thread]: column index, kNoEdge past the row's weight
     const int32_t *slab;        // [nslab][2]: {first entry in cols, slab weight (its heaviest row)}
@@ -530,55 +534,48 @@ int dclass_of(int max_row_deg) { return max_row_deg <= 8 ? 8 : (max_row_deg <= 2
 size_t cell_bytes(int dtype) { return dtype == LDPC_F32 ? 4 : dtype == LDPC_I8 ? 1 : 2; }
 size_t rec_bytes(int dtype) { return dtype == LDPC_I8 ? sizeof(CsrRecI8) : sizeof(CsrRec); }
 size_t lds_bytes_for(const ldpc_code &c, int dtype) { return (((size_t)c.N * cell_bytes(dtype) + 15) & ~(size_t)15) + 32; }
-template <typename LT> using csr_kernel_t = void (*)(CsrLayDev, typename Cell<LT>::Rec *, CsrLayArgs);
-template <typename LT> csr_kernel_t<LT> kernel_for(int dclass) {
-    return dclass == 8 ? layered_csr_kernel<8, LT> : dclass == 20 ? layered_csr_kernel<20, LT> : layered_csr_kernel<32, LT>;
+
+// ------------------------------------------------------------------ THE INSTANCES: 3 families x 3 row classes x 8 cells = 72 kernels.
+// Every one is named here and nowhere else; `word` is what the error texts call the family
+enum { kPlain = 0, kSoft = 1, kCont = 2 };
+const struct { const char *kernel, *word; } kFamily[3] = {{"layered_csr_kernel", ""}, {"layered_csr_soft_kernel", "soft "}, {"layered_csr_cont_kernel", "continuing "}};
+// a kernel, launched through hipLaunchKernel, and its name as the demangler writes it (LaunchInfo::name, ldpc_ctx_kernel_name)
+struct Instance { const void *kern = nullptr; char name[sizeof(LaunchInfo::name)] = ""; };
+
+template <int DCLASS, typename CELL> const void *kernel_of(int family) {    // family -> kernel template
+    return family == kSoft   ? (const void *)layered_csr_soft_kernel<DCLASS, CELL>
+           : family == kCont ? (const void *)layered_csr_cont_kernel<DCLASS, CELL> : (const void *)layered_csr_kernel<DCLASS, CELL>;
 }
-const void *pick_kernel(int dclass, int dtype, int rule) {
-    if (rule == kRuleAMinStar) return dtype == LDPC_F32 ? (const void *)kernel_for<MinStar<float>>(dclass) : (const void *)kernel_for<MinStar<_Float16>>(dclass);
-    if (rule) return dtype == LDPC_F32 ? (const void *)kernel_for<Ruled<float>>(dclass) : dtype == LDPC_I8 ? (const void *)kernel_for<Ruled<int8_t>>(dclass) : (const void *)kernel_for<Ruled<_Float16>>(dclass);
-    return dtype == LDPC_F32 ? (const void *)kernel_for<float>(dclass) : dtype == LDPC_I8 ? (const void *)kernel_for<int8_t>(dclass) : (const void *)kernel_for<_Float16>(dclass);
+// row class -> DCLASS.  cell: CELL as the demangler writes it, "" where it is the template's default and not written
+template <typename CELL> Instance instance(int family, int dclass, const std::string &cell) {
+    Instance r;
+    r.kern = dclass == 8 ? kernel_of<8, CELL>(family) : dclass == 20 ? kernel_of<20, CELL>(family) : kernel_of<32, CELL>(family);
+    snprintf(r.name, sizeof(r.name), "ldpc::%s<%d%s%s>", kFamily[family].kernel, dclass, cell.empty() ? "" : ", ", cell.c_str());
+    return r;
 }
-template <typename LT> void launch(int dclass, int rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, void *rec, const CsrLayArgs &a) {
-    if constexpr (!std::is_same<LT, int8_t>::value) {
-        if (rule == kRuleAMinStar) { hipLaunchKernelGGL(kernel_for<MinStar<LT>>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a); return; }
-    }
-    if (rule) hipLaunchKernelGGL(kernel_for<Ruled<LT>>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a);
-    else hipLaunchKernelGGL(kernel_for<LT>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a);
+// dtype -> LT; rule -> cell: the 3/4 LT, scaled Ruled<LT>, A-min* MinStar<LT> -- for float cells only: MinStar<int8_t> is never named, so
+// it is not instantiated (select.cc refuses the request; an Instance without a kernel fails its creation)
+Instance instance_of(int family, int dclass, int dtype, int rule) {
+    auto cell = [&](auto t, const std::string &lt) {
+        typedef typename decltype(t)::type LT;
+        if (rule == kRule34) return instance<LT>(family, dclass, std::is_same<LT, _Float16>::value ? "" : lt);
+        if (rule == kRuleScaled) return instance<Ruled<LT>>(family, dclass, "ldpc::Ruled<" + lt + ">");
+        if constexpr (!std::is_same<LT, int8_t>::value) return instance<MinStar<LT>>(family, dclass, "ldpc::MinStar<" + lt + ">");
+        else return Instance{};
+    };
+    return dtype == LDPC_F32 ? cell(Fmt<float>{}, "float") : dtype == LDPC_I8 ? cell(Fmt<int8_t>{}, "signed char") : cell(Fmt<_Float16>{}, "_Float16");
 }
 
-template <typename LT> using csr_soft_kernel_t = void (*)(CsrLayDev, typename Cell<LT>::Rec *, CsrLayArgs, CsrSoftArgs);
-template <typename LT> csr_soft_kernel_t<LT> soft_kernel_for(int dclass) {
-    return dclass == 8 ? layered_csr_soft_kernel<8, LT> : dclass == 20 ? layered_csr_soft_kernel<20, LT> : layered_csr_soft_kernel<32, LT>;
-}
-const void *pick_soft_kernel(int dclass, int dtype, int rule) {
-    if (rule == kRuleAMinStar) return dtype == LDPC_F32 ? (const void *)soft_kernel_for<MinStar<float>>(dclass) : (const void *)soft_kernel_for<MinStar<_Float16>>(dclass);
-    if (rule) return dtype == LDPC_F32 ? (const void *)soft_kernel_for<Ruled<float>>(dclass) : dtype == LDPC_I8 ? (const void *)soft_kernel_for<Ruled<int8_t>>(dclass) : (const void *)soft_kernel_for<Ruled<_Float16>>(dclass);
-    return dtype == LDPC_F32 ? (const void *)soft_kernel_for<float>(dclass) : dtype == LDPC_I8 ? (const void *)soft_kernel_for<int8_t>(dclass) : (const void *)soft_kernel_for<_Float16>(dclass);
-}
-template <typename LT> void launch_soft(int dclass, int rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, void *rec, const CsrLayArgs &a, const CsrSoftArgs &so) {
-    if constexpr (!std::is_same<LT, int8_t>::value) {
-        if (rule == kRuleAMinStar) { hipLaunchKernelGGL(soft_kernel_for<MinStar<LT>>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a, so); return; }
-    }
-    if (rule) hipLaunchKernelGGL(soft_kernel_for<Ruled<LT>>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a, so);
-    else hipLaunchKernelGGL(soft_kernel_for<LT>(dclass), grid, block, lds, st, g, (typename Cell<LT>::Rec *)rec, a, so);
-}
-
-template <typename LT> using csr_cont_kernel_t = void (*)(CsrLayDev, CsrLayArgs, CsrSoftArgs, CsrContArgs);
-template <typename LT> csr_cont_kernel_t<LT> cont_kernel_for(int dclass) {
-    return dclass == 8 ? layered_csr_cont_kernel<8, LT> : dclass == 20 ? layered_csr_cont_kernel<20, LT> : layered_csr_cont_kernel<32, LT>;
-}
-const void *pick_cont_kernel(int dclass, int dtype, int rule) {
-    if (rule == kRuleAMinStar) return dtype == LDPC_F32 ? (const void *)cont_kernel_for<MinStar<float>>(dclass) : (const void *)cont_kernel_for<MinStar<_Float16>>(dclass);
-    if (rule) return dtype == LDPC_F32 ? (const void *)cont_kernel_for<Ruled<float>>(dclass) : dtype == LDPC_I8 ? (const void *)cont_kernel_for<Ruled<int8_t>>(dclass) : (const void *)cont_kernel_for<Ruled<_Float16>>(dclass);
-    return dtype == LDPC_F32 ? (const void *)cont_kernel_for<float>(dclass) : dtype == LDPC_I8 ? (const void *)cont_kernel_for<int8_t>(dclass) : (const void *)cont_kernel_for<_Float16>(dclass);
-}
-template <typename LT> void launch_cont(int dclass, int rule, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsrLayDev &g, const CsrLayArgs &a, const CsrSoftArgs &so, const CsrContArgs &k) {
-    if constexpr (!std::is_same<LT, int8_t>::value) {
-        if (rule == kRuleAMinStar) { hipLaunchKernelGGL(cont_kernel_for<MinStar<LT>>(dclass), grid, block, lds, st, g, a, so, k); return; }
-    }
-    if (rule) hipLaunchKernelGGL(cont_kernel_for<Ruled<LT>>(dclass), grid, block, lds, st, g, a, so, k);
-    else hipLaunchKernelGGL(cont_kernel_for<LT>(dclass), grid, block, lds, st, g, a, so, k);
+// resident workgroups of an instance at T threads and lds bytes of LDS: the attribute that grants it that LDS, its occupancy, the CUs
+hipError_t resident_workgroups(const void *kern, int T, size_t lds, int *n) {
+    int per_cu = 0, dev = 0;
+    hipDeviceProp_t prop;
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, T, lds);
+    *n = e == hipSuccess ? per_cu * prop.multiProcessorCount : 0;
+    return e;
 }
 
 // ------------------------------------------------------------------ host side
@@ -594,24 +591,66 @@ struct LayeredCsrState : Backend {
     int32_t *d_slab = nullptr, *d_wdeg = nullptr, *d_step = nullptr;
     int *d_counter = nullptr;
     void *rec = nullptr;        // [grid][nslab][T] row records (CsrRec, or CsrRecI8 with int8 lam)
+    Instance inst[3];           // by family.  The plain one is set at creation, the others by their first call; info.name is that of the last launch
+    int resident[3] = {0, 0, 0};    // resident workgroups of each (0: not asked yet); `grid` is the plain one's, at most max_batch
 
     ~LayeredCsrState() override {
         (void)hipFree(d_cols); (void)hipFree(d_slab); (void)hipFree(d_wdeg); (void)hipFree(d_step); (void)hipFree(d_counter); (void)hipFree(rec);
     }
-    char name_plain[sizeof(LaunchInfo::name)] = "", name_soft[sizeof(LaunchInfo::name)] = "", name_cont[sizeof(LaunchInfo::name)] = "";   // info.name is that of the last launch
-    int soft_grid = 0;          // resident workgroups of the soft instance (0: not asked yet)
-    int cont_grid = 0;          // ... of the continuing instance, whose records are the state's: not bounded by `grid`
     int decode_state_bytes(size_t *rec_b, size_t *sum_b) override {
         *rec_b = rec_bytes(dtype) * (size_t)std::max(nslab, 1) * g.T;
         *sum_b = (dtype == LDPC_I8 ? sizeof(int16_t) : sizeof(float)) * (size_t)g.N;
         return LDPC_OK;
     }
-    int decode_continue(hipStream_t st, void *st_rec, void *st_sum, int first, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits,
-                        int32_t *d_iters, uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) override;
+    // What the three decodes share: one launch of the context's instance of `family`, with the same tables, counter and geometry.  so, k: the
+    // family's further arguments (null where it has none)
+    int run(int family, hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters, uint8_t *d_conv,
+            double *d_final, CsrSoftArgs *so, CsrContArgs *k) {
+        if (llr_fmt == LLR_I8 && dtype != LDPC_I8) return set_error(LDPC_EUNSUPPORTED, "int8 LLRs are taken by LDPC_I8 contexts only");
+        Instance &in = inst[family];
+        if (!resident[family]) {        // asked for once
+            in = instance_of(family, dclass, dtype, has_rule);
+            const hipError_t e = resident_workgroups(in.kern, g.T, lds, &resident[family]);
+            if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr %sinstance: %s", kFamily[family].word, hipGetErrorString(e));
+            if (resident[family] <= 0) return set_error(LDPC_EHIP, "layered_csr: no workgroup of %d threads and %zu B of LDS of the %sinstance is resident", g.T, lds, kFamily[family].word);
+        }
+        // the plain and the soft instance write the context's records, sized for `grid` workgroups; the continuing one writes the state's
+        const int bound = family == kPlain ? grid : family == kSoft ? std::min(grid, resident[kSoft]) : resident[kCont];
+        CsrLayArgs a{};
+        a.llr = d_llr; a.llr_fmt = llr_fmt; a.qscale = qscale; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final;
+        a.batch = batch; a.max_iters = max_iters; a.work_counter = d_counter; a.rule = rule;
+        hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(int), st);
+        if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
+        void *args[3][4] = {{&g, &rec, &a, nullptr}, {&g, &rec, &a, so}, {&g, &a, so, k}};     // the continuing kernel takes no `rec`
+        memcpy(info.name, in.name, sizeof(info.name));
+        if (timer) timer->begin(st);
+        (void)hipLaunchKernel(in.kern, dim3(std::min(batch, bound)), dim3(g.T), args[family], lds, st);
+        if (timer) timer->end(st);
+        e = hipGetLastError();
+        if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr %slaunch: %s", kFamily[family].word, hipGetErrorString(e));
+        return LDPC_OK;
+    }
     int decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
-               uint8_t *d_conv, double *d_final, double *d_trace) override;
+               uint8_t *d_conv, double *d_final, double *d_trace) override {
+        if (d_trace) return set_error(LDPC_EUNSUPPORTED, has_rule == kRuleAMinStar ? "layered_csr: no per-sweep trace with a check-node rule (cn_rule = LDPC_CN_AMINSTAR; decode without one)" : has_rule ? "layered_csr: no per-sweep trace with a check-node rule (cn_scale / cn_offset; decode without one)" : "layered_csr: no per-sweep trace (decode without one)");
+        return run(kPlain, st, max_iters, batch, d_llr, llr_fmt, d_bits, d_iters, d_conv, d_final, nullptr, nullptr);
+    }
+    // The soft instance of the context's kernel: same tables, records, counter and geometry.  It holds more registers than the plain one in
+    // its epilogue only; its grid is bounded by the records the context owns (sized for the plain instance's resident workgroups) and by its
+    // own residency.
     int decode_soft(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
-                    uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) override;
+                    uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) override {
+        CsrSoftArgs so{d_soft, soft_fmt, soft_kind, soft_qscale};
+        return run(kSoft, st, max_iters, batch, d_llr, llr_fmt, d_bits, d_iters, d_conv, nullptr, &so, nullptr);
+    }
+    // The continuing instance of the context's kernel: same tables, counter and geometry; its records and sums are the state's slots
+    // first .. first + batch - 1 (st_rec, st_sum: slot 0), so its grid is bounded by its own residency alone.
+    int decode_continue(hipStream_t st, void *st_rec, void *st_sum, int first, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits,
+                        int32_t *d_iters, uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) override {
+        CsrSoftArgs so{d_soft, soft_fmt, soft_kind, soft_qscale};
+        CsrContArgs k{st_rec, st_sum, first};
+        return run(kCont, st, max_iters, batch, d_llr, llr_fmt, d_bits, d_iters, d_conv, nullptr, &so, &k);
+    }
     int step(hipStream_t, int, const double *, const double *, const double *, double *, double *, uint8_t *) override {
         if (has_rule == kRuleAMinStar) return set_error(LDPC_EUNSUPPORTED, "no teacher-forced step with a check-node rule (cn_rule = LDPC_CN_AMINSTAR: the record kernels keep no per-edge messages)");
         if (has_rule) return set_error(LDPC_EUNSUPPORTED, "no teacher-forced step with a check-node rule (cn_scale / cn_offset: the record kernels keep no per-edge messages)");
@@ -635,6 +674,8 @@ const char *layered_csr_why_not(const ldpc_code &c, int variant, int dtype) {
     return nullptr;
 }
 
+// The graph work -- steps, slabs, the column table -- is csrc/layered_csr_layout.cc; here are the decisions that need the device: T, the
+// allocations and uploads, the resident workgroups
 Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float qscale, const CnRule *cn) {
     LayeredCsrState *s = new (std::nothrow) LayeredCsrState();
     if (!s) { set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
@@ -644,31 +685,11 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
         s->max_batch = max_batch; s->dclass = dclass_of(c.max_row_deg); s->dtype = dtype; s->qscale = qscale;
         if (cn && cn->kind == LDPC_CN_AMINSTAR) s->has_rule = kRuleAMinStar;
         else if (cn) { s->has_rule = kRuleScaled; s->rule.scale = cn->scale; s->rule.offset = cn->offset; s->rule.a = cn->a; s->rule.b = cn->b; }
-        // barrier steps: maximal runs of consecutive layers that share no column
-        std::vector<std::vector<int>> steps;
-        {
-            std::vector<int32_t> stamp((size_t)c.N, -1);
-            const int nl = (int)c.layer_ptr.size() - 1;
-            for (int l = 0; l < nl; l++) {
-                bool clash = steps.empty();
-                for (int m = c.layer_ptr[l]; m < c.layer_ptr[l + 1] && !clash; m++)
-                    for (int q = c.row_ptr[m]; q < c.row_ptr[m + 1] && !clash; q++) clash = stamp[c.col_idx[q]] == (int)steps.size() - 1;
-                if (clash) steps.emplace_back();
-                for (int m = c.layer_ptr[l]; m < c.layer_ptr[l + 1]; m++) {
-                    steps.back().push_back(m);
-                    for (int q = c.row_ptr[m]; q < c.row_ptr[m + 1]; q++) stamp[c.col_idx[q]] = (int)steps.size() - 1;
-                }
-            }
-        }
-        auto deg = [&](int m) { return c.row_ptr[m + 1] - c.row_ptr[m]; };
-        size_t rmax = 1;
-        for (auto &st : steps) {
-            std::stable_sort(st.begin(), st.end(), [&](int a, int b) { return deg(a) > deg(b); });   // heaviest first: uniform waves
-            rmax = std::max(rmax, st.size());
-        }
-        int T = (int)std::min<size_t>(csr_max_threads(s->dclass), (rmax + 63) / 64 * 64);
+        const CsrSteps steps = csr_layout_steps(c.N, c.row_ptr.data(), c.col_idx.data(), c.layer_ptr.data(), (int)c.layer_ptr.size() - 1);
+        int T = (int)std::min<size_t>(csr_max_threads(s->dclass), (steps.rmax + 63) / 64 * 64);
         s->lds = lds_bytes_for(c, dtype);
-        const void *kern = pick_kernel(s->dclass, dtype, s->has_rule);
+        s->inst[kPlain] = instance_of(kPlain, s->dclass, dtype, s->has_rule);
+        const void *kern = s->inst[kPlain].kern;
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds);
         // int8 lam: a frame of N = 64 800 takes 64.8 KB of LDS, so two workgroups fit a CU -- when the registers allow it.  1024 threads
         // at more than 64 VGPRs fill the CU's register files alone; 512 threads leave room for a second workgroup, whose rows run
@@ -686,50 +707,22 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
             const int t = atoi(force);
             if (t >= 64 && t % 64 == 0 && t <= csr_max_threads(s->dclass)) T = t;
         }
-        const int W = T / 64;
-        std::vector<uint16_t> cols;
-        std::vector<int32_t> slab, wdeg, step_ptr(1, 0);
-        for (auto &st : steps) {
-            for (size_t r0 = 0; r0 < st.size(); r0 += T) {
-                const int nr = (int)std::min<size_t>(T, st.size() - r0), D = deg(st[r0]);
-                slab.push_back((int32_t)cols.size()); slab.push_back(D);
-                const size_t base = cols.size();
-                cols.resize(base + (size_t)D * T, kNoEdge);
-                for (int i = 0; i < nr; i++) {
-                    const int m = st[r0 + i];
-                    for (int k = 0; k < deg(m); k++) cols[base + (size_t)k * T + i] = (uint16_t)c.col_idx[c.row_ptr[m] + k];
-                }
-                for (int w = 0; w < W; w++) {
-                    int wd = 0; bool uni = true;
-                    for (int i = 64 * w; i < 64 * w + 64; i++) {
-                        const int d = i < nr ? deg(st[r0 + i]) : 0;
-                        if (i == 64 * w) wd = d; else uni = uni && d == wd;
-                        wd = std::max(wd, d);
-                    }
-                    wdeg.push_back(wd | (uni ? 0x100 : 0));
-                }
-            }
-            step_ptr.push_back((int32_t)(slab.size() / 2));
-        }
-        s->nslab = (int)(slab.size() / 2);
-        s->g.N = c.N; s->g.T = T; s->g.nstep = (int)steps.size();
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t prop;
-        if (e == hipSuccess) e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, T, s->lds);
-        if (e == hipSuccess && per_cu <= 0) { set_error(LDPC_EHIP, "layered_csr: no workgroup of %d threads and %zu B of LDS is resident", T, s->lds); delete s; return nullptr; }
-        if (e == hipSuccess) s->grid = std::min(max_batch, per_cu * prop.multiProcessorCount);
-        if (e == hipSuccess) e = hipMalloc((void **)&s->d_cols, sizeof(uint16_t) * std::max<size_t>(cols.size(), 1));
-        if (e == hipSuccess) e = hipMalloc((void **)&s->d_slab, sizeof(int32_t) * std::max<size_t>(slab.size(), 2));
-        if (e == hipSuccess) e = hipMalloc((void **)&s->d_wdeg, sizeof(int32_t) * std::max<size_t>(wdeg.size(), 1));
-        if (e == hipSuccess) e = hipMalloc((void **)&s->d_step, sizeof(int32_t) * step_ptr.size());
+        const CsrLayout lay = csr_layout_pack(steps, c.row_ptr.data(), c.col_idx.data(), T);
+        s->nslab = lay.nslab;
+        s->g.N = c.N; s->g.T = T; s->g.nstep = (int)steps.rows.size();
+        if (e == hipSuccess) e = resident_workgroups(kern, T, s->lds, &s->resident[kPlain]);
+        if (e == hipSuccess && s->resident[kPlain] <= 0) { set_error(LDPC_EHIP, "layered_csr: no workgroup of %d threads and %zu B of LDS is resident", T, s->lds); delete s; return nullptr; }
+        if (e == hipSuccess) s->grid = std::min(max_batch, s->resident[kPlain]);
+        if (e == hipSuccess) e = hipMalloc((void **)&s->d_cols, sizeof(uint16_t) * std::max<size_t>(lay.cols.size(), 1));
+        if (e == hipSuccess) e = hipMalloc((void **)&s->d_slab, sizeof(int32_t) * std::max<size_t>(lay.slab.size(), 2));
+        if (e == hipSuccess) e = hipMalloc((void **)&s->d_wdeg, sizeof(int32_t) * std::max<size_t>(lay.wdeg.size(), 1));
+        if (e == hipSuccess) e = hipMalloc((void **)&s->d_step, sizeof(int32_t) * lay.step_ptr.size());
         if (e == hipSuccess) e = hipMalloc((void **)&s->d_counter, sizeof(int));
         if (e == hipSuccess) e = hipMalloc(&s->rec, rec_bytes(dtype) * (size_t)s->grid * std::max(s->nslab, 1) * T);
-        if (e == hipSuccess && !cols.empty()) e = hipMemcpy(s->d_cols, cols.data(), sizeof(uint16_t) * cols.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !slab.empty()) e = hipMemcpy(s->d_slab, slab.data(), sizeof(int32_t) * slab.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !wdeg.empty()) e = hipMemcpy(s->d_wdeg, wdeg.data(), sizeof(int32_t) * wdeg.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(s->d_step, step_ptr.data(), sizeof(int32_t) * step_ptr.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !lay.cols.empty()) e = hipMemcpy(s->d_cols, lay.cols.data(), sizeof(uint16_t) * lay.cols.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !lay.slab.empty()) e = hipMemcpy(s->d_slab, lay.slab.data(), sizeof(int32_t) * lay.slab.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !lay.wdeg.empty()) e = hipMemcpy(s->d_wdeg, lay.wdeg.data(), sizeof(int32_t) * lay.wdeg.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(s->d_step, lay.step_ptr.data(), sizeof(int32_t) * lay.step_ptr.size(), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             set_error(e == hipErrorOutOfMemory ? LDPC_ENOMEM : LDPC_EHIP, "layered_csr_create (%d workgroups x %zu bytes of records): %s", s->grid,
                       rec_bytes(dtype) * (size_t)s->nslab * T, hipGetErrorString(e));
@@ -737,114 +730,10 @@ Backend *layered_csr_create(const ldpc_code &c, int dtype, int max_batch, float 
             return nullptr;
         }
         s->g.cols = s->d_cols; s->g.slab = s->d_slab; s->g.wdeg = s->d_wdeg; s->g.step_ptr = s->d_step;
-        if (s->has_rule == kRuleAMinStar) snprintf(s->info.name, sizeof(s->info.name), "ldpc::layered_csr_kernel<%d, ldpc::MinStar<%s>>", s->dclass, dtype == LDPC_F32 ? "float" : "_Float16");
-        else if (s->has_rule) snprintf(s->info.name, sizeof(s->info.name), "ldpc::layered_csr_kernel<%d, ldpc::Ruled<%s>>", s->dclass, dtype == LDPC_I8 ? "signed char" : dtype == LDPC_F32 ? "float" : "_Float16");
-        else snprintf(s->info.name, sizeof(s->info.name), dtype == LDPC_I8 ? "ldpc::layered_csr_kernel<%d, signed char>" : dtype == LDPC_F32 ? "ldpc::layered_csr_kernel<%d, float>" : "ldpc::layered_csr_kernel<%d>", s->dclass);
-        snprintf(s->name_plain, sizeof(s->name_plain), "%s", s->info.name);
-        {   // "ldpc::layered_csr_kernel<...>" -> "ldpc::layered_csr_soft_kernel<...>"
-            const char *lt = strchr(s->info.name, '<');
-            snprintf(s->name_soft, sizeof(s->name_soft), "ldpc::layered_csr_soft_kernel%s", lt ? lt : "");
-            snprintf(s->name_cont, sizeof(s->name_cont), "ldpc::layered_csr_cont_kernel%s", lt ? lt : "");
-        }
+        memcpy(s->info.name, s->inst[kPlain].name, sizeof(s->info.name));
         s->info.threads = T; s->info.frames_per_wg = 1;
         return s;
     } catch (...) { delete s; set_error(LDPC_ENOMEM, "out of host memory"); return nullptr; }
-}
-
-int LayeredCsrState::decode(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
-                            uint8_t *d_conv, double *d_final, double *d_trace) {
-    if (d_trace) return set_error(LDPC_EUNSUPPORTED, has_rule == kRuleAMinStar ? "layered_csr: no per-sweep trace with a check-node rule (cn_rule = LDPC_CN_AMINSTAR; decode without one)" : has_rule ? "layered_csr: no per-sweep trace with a check-node rule (cn_scale / cn_offset; decode without one)" : "layered_csr: no per-sweep trace (decode without one)");
-    CsrLayArgs a{};
-    if (llr_fmt == LLR_I8 && dtype != LDPC_I8) return set_error(LDPC_EUNSUPPORTED, "int8 LLRs are taken by LDPC_I8 contexts only");
-    a.llr = d_llr; a.llr_fmt = llr_fmt; a.qscale = qscale; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = d_final;
-    a.batch = batch; a.max_iters = max_iters; a.work_counter = d_counter; a.rule = rule;
-    hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(int), st);
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
-    const dim3 grid(std::min(batch, this->grid)), block(g.T);
-    memcpy(info.name, name_plain, sizeof(info.name));
-    if (timer) timer->begin(st);
-    if (dtype == LDPC_I8) launch<int8_t>(dclass, has_rule, grid, block, lds, st, g, rec, a);
-    else if (dtype == LDPC_F32) launch<float>(dclass, has_rule, grid, block, lds, st, g, rec, a);
-    else launch<_Float16>(dclass, has_rule, grid, block, lds, st, g, rec, a);
-    if (timer) timer->end(st);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr launch: %s", hipGetErrorString(e));
-    return LDPC_OK;
-}
-
-// The soft instance of the context's kernel: same tables, records, counter and geometry.  It holds more registers than the plain one in
-// its epilogue only; its grid is bounded by the records the context owns (sized for the plain instance's resident workgroups) and by its
-// own residency, asked for once.
-int LayeredCsrState::decode_soft(hipStream_t st, int max_iters, int batch, const void *d_llr, int llr_fmt, uint8_t *d_bits, int32_t *d_iters,
-                                 uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) {
-    if (llr_fmt == LLR_I8 && dtype != LDPC_I8) return set_error(LDPC_EUNSUPPORTED, "int8 LLRs are taken by LDPC_I8 contexts only");
-    if (!soft_grid) {
-        const void *kern = pick_soft_kernel(dclass, dtype, has_rule);
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t prop;
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, g.T, lds);
-        if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr soft instance: %s", hipGetErrorString(e));
-        if (per_cu <= 0) return set_error(LDPC_EHIP, "layered_csr: no workgroup of %d threads and %zu B of LDS of the soft instance is resident", g.T, lds);
-        soft_grid = std::min(this->grid, per_cu * prop.multiProcessorCount);
-    }
-    CsrLayArgs a{};
-    a.llr = d_llr; a.llr_fmt = llr_fmt; a.qscale = qscale; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = nullptr;
-    a.batch = batch; a.max_iters = max_iters; a.work_counter = d_counter; a.rule = rule;
-    CsrSoftArgs so{};
-    so.out = d_soft; so.fmt = soft_fmt; so.kind = soft_kind; so.qscale = soft_qscale;
-    hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(int), st);
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
-    const dim3 grid(std::min(batch, soft_grid)), block(g.T);
-    memcpy(info.name, name_soft, sizeof(info.name));
-    if (timer) timer->begin(st);
-    if (dtype == LDPC_I8) launch_soft<int8_t>(dclass, has_rule, grid, block, lds, st, g, rec, a, so);
-    else if (dtype == LDPC_F32) launch_soft<float>(dclass, has_rule, grid, block, lds, st, g, rec, a, so);
-    else launch_soft<_Float16>(dclass, has_rule, grid, block, lds, st, g, rec, a, so);
-    if (timer) timer->end(st);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr soft launch: %s", hipGetErrorString(e));
-    return LDPC_OK;
-}
-
-// The continuing instance of the context's kernel: same tables, counter and geometry; its records and sums are the state's slots
-// first .. first + batch - 1 (st_rec, st_sum: slot 0), so its grid is bounded by its own residency alone, asked for once.
-int LayeredCsrState::decode_continue(hipStream_t st, void *st_rec, void *st_sum, int first, int max_iters, int batch, const void *d_llr, int llr_fmt,
-                                     uint8_t *d_bits, int32_t *d_iters, uint8_t *d_conv, void *d_soft, int soft_fmt, float soft_qscale, int soft_kind) {
-    if (llr_fmt == LLR_I8 && dtype != LDPC_I8) return set_error(LDPC_EUNSUPPORTED, "int8 LLRs are taken by LDPC_I8 contexts only");
-    if (!cont_grid) {
-        const void *kern = pick_cont_kernel(dclass, dtype, has_rule);
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t prop;
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, g.T, lds);
-        if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr continuing instance: %s", hipGetErrorString(e));
-        if (per_cu <= 0) return set_error(LDPC_EHIP, "layered_csr: no workgroup of %d threads and %zu B of LDS of the continuing instance is resident", g.T, lds);
-        cont_grid = per_cu * prop.multiProcessorCount;
-    }
-    CsrLayArgs a{};
-    a.llr = d_llr; a.llr_fmt = llr_fmt; a.qscale = qscale; a.bits = d_bits; a.iters = d_iters; a.conv = d_conv; a.final_lam = nullptr;
-    a.batch = batch; a.max_iters = max_iters; a.work_counter = d_counter; a.rule = rule;
-    CsrSoftArgs so{};
-    so.out = d_soft; so.fmt = soft_fmt; so.kind = soft_kind; so.qscale = soft_qscale;
-    CsrContArgs k{};
-    k.rec = st_rec; k.sum = st_sum; k.first = first;
-    hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(int), st);
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr: %s", hipGetErrorString(e));
-    const dim3 grid(std::min(batch, cont_grid)), block(g.T);
-    memcpy(info.name, name_cont, sizeof(info.name));
-    if (timer) timer->begin(st);
-    if (dtype == LDPC_I8) launch_cont<int8_t>(dclass, has_rule, grid, block, lds, st, g, a, so, k);
-    else if (dtype == LDPC_F32) launch_cont<float>(dclass, has_rule, grid, block, lds, st, g, a, so, k);
-    else launch_cont<_Float16>(dclass, has_rule, grid, block, lds, st, g, a, so, k);
-    if (timer) timer->end(st);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(LDPC_EHIP, "layered_csr continuing launch: %s", hipGetErrorString(e));
-    return LDPC_OK;
 }
 
 }  // namespace ldpc
